@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — the hot path's headline benchmark on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg2]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg2] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: segments, indexes, the loop's warm-up, the K timed steps, the result line
+(`value`, `ms_per_step`, and what the timed steps themselves measured: kernels_only, end_to_end, matches).  --full adds everything
+else described below — the diagnostic set and the roofline block, the scaling reference leg, the rotating and delivered legs, the
+gather check, the CPU baseline and its parity check.  --dump-outputs DIR writes what the last timed step delivered (dump_outputs()):
+the inputs are seeded, so two builds can be compared output for output.
 
 Default workload (BASELINE.json configs[1]): batched 2-term AND queries (Zipf-sampled terms, seed 1337,
 distinct within a query) over the 10M-document / 1M-term synthetic Zipf(1.0) segment (corpus seed 42, google_codec),
@@ -23,16 +29,16 @@ Multi-GPU: one process per GPU, the index replicated, the query stream sharded (
 default workload is cfg5, the mixed 100K-query batch BASELINE.json's scaling criterion is quoted on, STRONG scaling: the 100 000 queries
 split over the N ranks (N = 1: weak, the cfg2 headline).  At the end of every step the ranks all_gather their result blocks over RCCL straight from the engine's device buffers:
 per-query match counts and, for scored batches, the [Q/G][K] top-K docID/score blocks (trinity_amd/dist.py ResultGather — the
-only exchange the path has).  Every line carries `scaling_point` — the mixed 100 K-query batch, strong scaling: value, per_gpu_value,
+only exchange the path has).  Every line at N > 1, and with --full at N = 1, carries `scaling_point` — the mixed 100 K-query batch, strong scaling: value, per_gpu_value,
 gather_ms, hbm_bytes_in_use and `n1`, the SAME workload on one GPU measured in the same run (N = 1: this GPU runs the whole 100 K batch after
-the cfg2 headline; N > 1: rank 0 alone on the whole batch, the other ranks parked at a barrier) — so a curve can be read from the lines alone.
+the cfg2 headline; N > 1: rank 0 alone on the whole batch, the other ranks parked at a barrier; --full) — so a curve can be read from the lines alone.
 
-Rank 0 prints ONE JSON line: metric/value = queries/s over all GPUs.  `roofline`: bound "hbm"; `frac` is the BATCH-LEVEL bound — every
+Rank 0 prints ONE JSON line: metric/value = queries/s over all GPUs.  `roofline` (--full): bound "hbm"; `frac` is the BATCH-LEVEL bound — every
 distinct list the step's queries name read once + every output written once (tri_batch_info.bound_bytes) / the step's kernel time /
 peak — for the whole step and, under `kernels`, per kernel (HIP events on the engine's stream around each launch, inside the timed
 steps), next to `physical_frac` (committed rocprofv3 PMC traffic of the same workload / kernel time / peak) and SURVEY §8(d)'s per-query
 algorithmic bytes (`per_query_algorithmic`: a figure no kernel that shares decodes or skips reads, so it carries no fraction).
-`cpu_baseline` = a bounded sample of the same batch on the host's cores: the CPU oracle (a restatement of the reference's exec path, planning
+`cpu_baseline` (--full) = a bounded sample of the same batch on the host's cores: the CPU oracle (a restatement of the reference's exec path, planning
 included; kind "port"), which doubles as a per-query full-size parity check, and — for the Google-codec workloads, where oracle/_ref/ref_driver
 is there — the GENUINE reference's exec_query over the same queries (kind "reference": that figure leads, the port's stands under `port`).
 """
@@ -389,20 +395,24 @@ def main():
     ap.add_argument("--docs", type=int, default=10_000_000)
     ap.add_argument("--vocab", type=int, default=1_000_000)
     ap.add_argument("--queries", type=int, default=0, help="queries per GPU per step (default: 16384; cfg3: 8192; cfg5: 12500 = a 100K batch over 8 GPUs)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline sample budget (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU-baseline sample budget (0 = skip)")
     ap.add_argument("--workload", default=None, choices=["cfg1", "cfg2", "cfg3", "cfg4", "cfg5"],
                     help="SURVEY §8(d) query sets; default: cfg2 at one GPU (the configuration BASELINE.json's metric is quoted on), cfg5 (the mixed 100K batch) at N > 1")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"], help="weak: --queries per GPU; strong: --queries in all, split over the GPUs.  Default: weak at N = 1 (the cfg2 "
                     "headline), STRONG at N > 1 — north_star's target is ONE 100 K-query mixed batch sharded over the node's GPUs")
-    ap.add_argument("--scaling-total", type=int, default=SCALING_TOTAL_QUERIES, help="N = 1: queries of the mixed batch the scaling point's leg runs (north_star: 100000)")
-    ap.add_argument("--scaling-ref-steps", type=int, default=3, help="steps of the scaling reference leg (0 = skip): N = 1: one rank's cfg5 shard on this GPU; N > 1: rank 0 alone on its shard")
-    ap.add_argument("--rotating-sets", type=int, default=8, help="N = 1: distinct query sets (seeds 1337 ...) cycled through the loop in the rotating legs (0 / 1 = skip them)")
-    ap.add_argument("--rotating-steps", type=int, default=16, help="timed steps of each rotating leg")
-    ap.add_argument("--delivered-steps", type=int, default=3, help="N = 1: steps of the leg that also brings every docID set to pinned host memory (0 = skip)")
+    ap.add_argument("--scaling-total", type=int, default=SCALING_TOTAL_QUERIES, help="--full, N = 1: queries of the mixed batch the scaling point's leg runs (north_star: 100000)")
+    ap.add_argument("--scaling-ref-steps", type=int, default=3, help="--full: steps of the scaling reference leg (0 = skip): N = 1: one rank's cfg5 shard on this GPU; N > 1: rank 0 alone on its shard")
+    ap.add_argument("--rotating-sets", type=int, default=8, help="--full, N = 1: distinct query sets (seeds 1337 ...) cycled through the loop in the rotating legs (0 / 1 = skip them)")
+    ap.add_argument("--rotating-steps", type=int, default=16, help="--full: timed steps of each rotating leg")
+    ap.add_argument("--delivered-steps", type=int, default=3, help="--full, N = 1: steps of the leg that also brings every docID set to pinned host memory (0 = skip)")
     ap.add_argument("--compilers", type=int, default=2, help="host threads that compile sets side by side in the loop (the device handle has two planner contexts)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help="planner option (tri_dev_set_option), e.g. fused=0")
     ap.add_argument("--dry-run", action="store_true", help="launcher / sharding / gather plumbing WITHOUT a GPU (tests/test_bench_launch.py): the batches are planned by the real host "
                                                           "planner, nothing runs, the result blocks are zeros on CPU tensors gathered over gloo; the line says dry_run and measures nothing")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the diagnostic set (roofline bytes, materialised forms, pipelined == resident), the "
+                                                       "scaling reference leg, the rotating and delivered legs, the gather check and the CPU baseline with its per-query parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed loop's last step delivered (match counts, top-K blocks, docset hashes, a seeded "
+                                                                        "sample of docID sets) as DIR/<name>.npy, float32 / float64, 64 MB at most")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -466,31 +476,36 @@ def main():
     wl = Workload(DryEngine(T) if dry else T, W, dev, args.workload, docs, vocab, total_queries, rank, world, segs, ixs)
     parts, nq_rank = wl.parts, wl.nq
 
-    # ---- the diagnostic set: the same batches created once with account_needed_bytes (a directory walk per candidate-tile query and a
+    # ---- (--full) the diagnostic set: the same batches created once with account_needed_bytes (a directory walk per candidate-tile query and a
     #      pass over the plan: untimed) — its run gives the byte counts of the roofline block, its results are what the parity check,
     #      the CPU leg and the gather check read
-    dev.set_option("account_needed_bytes", 1)
-    batches = wl.create_set()
-    dev.set_option("account_needed_bytes", 0)
-    for b in batches:
-        b.run()
-    for b in batches:
-        b.sync()
-    infos = [b.info() for b in batches]
-    tot = {k: float(sum(i[k] for i in infos)) for k in TOT_KEYS}
+    full = args.full
+    batches = tot = None
+    if full:
+        dev.set_option("account_needed_bytes", 1)
+        batches = wl.create_set()
+        dev.set_option("account_needed_bytes", 0)
+        for b in batches:
+            b.run()
+        for b in batches:
+            b.sync()
+        infos = [b.info() for b in batches]
+        tot = {k: float(sum(i[k] for i in infos)) for k in TOT_KEYS}
 
     dev_t = torch.device("cpu") if dry else torch.device("cuda", local_rank)
     blocks_of = (lambda b: b.blocks()) if dry else (lambda b: TD.device_blocks(b, dev_t))
-    gathers = [TD.ResultGather(dist, blocks_of(b)) for b in batches] if dist is not None else None
     Pipeline.COMPILERS = max(1, args.compilers)
-    pipe = Pipeline(T, wl, gathers, blocks_of, sync_stream=not dry)
+    pipe = Pipeline(T, wl, None, blocks_of, sync_stream=not dry)
+    # (the gather's receive buffers take their shapes from one set of the workload: every set has the same)
+    gathers = [TD.ResultGather(dist, blocks_of(b)) for b in (batches or pipe.cur)] if dist is not None else None
+    pipe.gathers = gathers
 
     # ---- the scaling curve's N = 1 point, measured in THIS run (before the timed region; every rank takes part so that the ranks stay in step).  The curve
     #      north_star asks for is ONE mixed 100 K-query batch (cfg5) sharded over the node's GPUs: strong scaling.  N > 1: rank 0 alone runs the WHOLE
     #      batch of this run (the other ranks parked at a barrier) — the same workload on one GPU; N = 1 (the cfg2 headline): this GPU runs the whole
     #      100 K mixed batch.  Either way the line carries `scaling_point` with the same-workload one-GPU rate beside its own.
     n1 = None
-    if args.scaling_ref_steps > 0:
+    if full and args.scaling_ref_steps > 0:
         n1_total = total_queries if world > 1 else args.scaling_total
         n1_workload = args.workload if world > 1 else "cfg5"
         if world > 1 or (args.workload != "cfg5" and docs == 10_000_000) or dry:
@@ -518,10 +533,14 @@ def main():
     region = acc.pop("_region")
     walls = sorted(acc.pop("_walls"))
     cstats = create_stats(pipe, region, args.steps, elapsed * 1e3 / max(1, args.steps))
+    # what the last timed step delivered (pipe.done: the set it awaited and read back; its results stay readable until pipe.close())
+    last_infos = [b.info() for b in pipe.done] if pipe.done else []
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, T, parts, pipe.done or [], dry)
 
-    # ---- legs that make the headline harder to flatter (N = 1, after the timed region; none of them feeds `value`)
+    # ---- (--full) legs that make the headline harder to flatter (N = 1, after the timed region; none of them feeds `value`)
     rotating = delivered = None
-    if world == 1 and not dry and args.rotating_sets > 1 and args.rotating_steps > 0:
+    if full and world == 1 and not dry and args.rotating_sets > 1 and args.rotating_steps > 0:
         # (b) a query STREAM: args.rotating_sets distinct sets (query seeds 1337, 1338, ...) cycled through the same loop.  `warm`: every head term's
         #     plane row is in the index's cache (a cycle of warm-up built them).  `cold_planes`: option planes_rebuild — every run decodes the plane
         #     rows its batch names again, i.e. what the stream pays when each step's head terms have just been evicted (k_term_planes inside the step)
@@ -542,7 +561,7 @@ def main():
         rotating = {"sets": args.rotating_sets, "steps": args.rotating_steps, "unit": "queries/s", **legs,
                     "what": "the same create -> run -> sync -> read-back loop over a STREAM of distinct query sets (seeds 1337 ...; the headline loop replays ONE set): `warm` with every "
                             "head term's plane row cached with the index, `cold_planes` with the rows a step names decoded again in that step (planes_rebuild: every row evicted)"}  # fmt: skip
-    if world == 1 and not dry and args.delivered_steps > 0:
+    if full and world == 1 and not dry and args.delivered_steps > 0:
         # (c) delivery: the docID sets themselves brought to the host — what MatchedIndexDocumentsFilter::consider(ids, cnt) (matches.h:161-165) is fed — into PINNED
         #     memory, one device-side gather + one copy per batch.  Two legs: `as_docids` — tri_batch_docsets, every set as ascending 4-byte docIDs (dense results
         #     expanded on the device first), serial: create -> run -> sync -> deliver; and the leg `value` is taken from — tri_batch_docsets_mixed, every set in the
@@ -612,14 +631,17 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev_t)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        m = torch.tensor([tot["matches"], tot["algorithmic_bytes"]], dtype=torch.float64, device=dev_t)
+    # (the matches of one step: the diagnostic set's under --full, else those of the set the last timed step read back — the same queries)
+    matches_rank = tot["matches"] if full else float(sum(i["matches"] for i in last_infos))
+    if dist is not None:
+        m = torch.tensor([matches_rank], dtype=torch.float64, device=dev_t)
         dist.all_reduce(m, op=dist.ReduceOp.SUM)
-        matches_all, alg_all = float(m[0].item()), float(m[1].item())
+        matches_all = float(m[0].item())
     else:
-        matches_all, alg_all = tot["matches"], tot["algorithmic_bytes"]
+        matches_all = matches_rank
 
     gather_check = None
-    if dist is not None:
+    if full and dist is not None:
         # what arrived in this rank's slot of every gathered block is what the engine reports locally (host copies through the C-ABI)
         ok = True
         for b, g in zip(pipe.done, gathers):
@@ -636,7 +658,7 @@ def main():
         gather_check = {"ranks": world, "blocks": sorted({k for g in gathers for k in g.recv}), "equal_on_every_rank": bool(t.item() == 1.0)}
     # (c) how many of the step's matches exist as docIDs in HBM (4 bytes each) and how many as bits of a result bitmap (RESULT_BITMAP: dense results)
     mat_ids = mat_bits = bitmap_queries = bitmap_bytes = 0
-    for pt, b0 in zip(parts, batches):
+    for pt, b0 in zip(parts, batches or []):
         cnts = b0.counts()
         if (pt.flags & T.FLAG_ACCUMULATED_SCORE) and pt.topk:
             mat_ids += int(np.minimum(cnts, pt.topk).sum())  # (a scored top-K batch materialises its top-K lists)
@@ -649,7 +671,7 @@ def main():
         mat_ids += int(cnts[~forms].sum())
         bitmap_queries += int(forms.sum())
         bitmap_bytes += int(words.sum()) * 4  # (a RESULT_BITMAP region is one bit per document of the query's docID range, whatever it matches)
-    same_as_resident = all(bool(np.array_equal(b.counts(), b0.counts())) for b, b0 in zip(pipe.done, batches))
+    same_as_resident = all(bool(np.array_equal(b.counts(), b0.counts())) for b, b0 in zip(pipe.done, batches)) if full else None
 
     if rank == 0:
         steps = max(1, args.steps)
@@ -660,7 +682,7 @@ def main():
         rest_ms = acc["rest_ms"] / steps
         tp_ms = acc.get("term_planes_ms", 0.0) / steps
         dom = max(kms, key=kms.get)
-        traffic, traffic_src = pmc_traffic(args, world)
+        traffic, traffic_src = pmc_traffic(args, world) if full else (None, None)
 
         def gbs(b, ms):
             return b / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
@@ -724,15 +746,19 @@ def main():
             "matches_per_step": matches_all,
             **({"docids_materialised_per_sec": mat_ids * steps / elapsed, "docids_materialised_per_step": mat_ids, "matches_kept_as_bitmap_bits_per_step": mat_bits, "bitmap_queries_per_step": bitmap_queries, "bitmap_bytes_per_step": bitmap_bytes,
                 "materialised_what": "of this rank's matches per step: written to HBM as 4-byte docIDs (scored batches: their top-K lists) / kept as bits of a result bitmap "
-                                     "(tri_batch_docset_bitmap; tri_batch_docsets expands them on delivery)"} if world == 1 else {}),
-            "pipelined_results_equal_resident_batch": same_as_resident,
+                                     "(tri_batch_docset_bitmap; tri_batch_docsets expands them on delivery)"} if full and world == 1 else {}),
+            **({"pipelined_results_equal_resident_batch": same_as_resident} if full else {}),
             "kernels_only": {"value": nq_rank * world / (k_ms * 1e-3) if k_ms > 0 else None, "ms_per_step": k_ms, "unit": "queries/s",
                              "what": "the step's kernels alone (HIP events around tri_batch_run inside the timed steps): no planning, no read-back"},
             "end_to_end": {"batch_create_ms": acc["create_ms"] / steps, "batch_create_plan_ms": acc["create_plan_ms"] / steps, "readback_ms": readback_ms, **cstats,
                            "batch_create_ms_what": "engine-reported tri_batch_create time of the sets LAUNCHED in the timed steps (they may have been compiled before the region began, and the time includes waiting for the device lock the running thread holds): see create_wall_ms for the creates that ran inside the region",
                            "what": "per step, inside the timed region: tri_batch_create (all batches of the step; its host-planner share) and the read-back of the match counts" +
                                    (" + top-K blocks" if any(pt.topk for pt in parts) else "")},
-            "roofline": {
+            "segment_build_s": wl.build_s,
+            "index_upload_s": wl.upload_s,
+        }
+        if full:
+            out["roofline"] = {
                 "bound": "hbm",
                 "scope": "step",
                 # the batch-level bound: every DISTINCT list the step's queries name read once + every output written once
@@ -753,10 +779,7 @@ def main():
                                 "scratch_bytes": tot["plane_bytes"], "traffic": sum((traffic or {}).get(k) or 0 for k in ("k_term_planes", "k_term_plane0")) or None},  # fmt: skip
                 "per_query_algorithmic": {"bytes_per_step": tot["algorithmic_bytes"], "effective_GBps": gbs(tot["algorithmic_bytes"], k_ms),
                                           "what": "SURVEY §8(d): sum over queries of docbytes(t) + output; a list shared by n queries counts n times, skipped blocks count: no fraction"},
-            },
-            "segment_build_s": wl.build_s,
-            "index_upload_s": wl.upload_s,
-        }
+            }
         if rotating is not None:
             out["rotating"] = rotating
             out["value_rotating"] = rotating["cold_planes"]["value"]
@@ -777,12 +800,12 @@ def main():
                                             "batch bench.py --gpus N > 1 splits over N GPUs"}  # fmt: skip
         if gather_check is not None:
             out["gather_check"] = gather_check
-        if args.cpu_seconds > 0 and world == 1 and not dry:  # the CPU leg (and the per-query parity check that rides on it) runs at N = 1 only
+        if full and args.cpu_seconds > 0 and world == 1 and not dry:  # the CPU leg (and the per-query parity check that rides on it) runs at N = 1 only
             out["cpu_baseline"], out["parity_check"] = cpu_baseline(segs, parts, wl.progs, batches, args.cpu_seconds)
         print(json.dumps(out), flush=True)
 
     pipe.close()
-    for b in batches:
+    for b in batches or []:
         b.close()
     for ix in ixs.values():
         ix.close()
@@ -790,6 +813,57 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SAMPLE_QUERIES = 64  # DocumentsOnly parts: queries whose docID sets are written
+DUMP_SAMPLE_DOCS = 16384  # ... the first docIDs of each at most
+DUMP_SEED = 20240917
+
+
+def dump_outputs(out_dir, T, parts, bs, dry):
+    """--dump-outputs: what the last timed step handed its caller, one .npy per array (float64: integers stay exact; scores float32, as the
+    engine returns them), for part p of the step under part<p>_:
+      counts                 every query's match count
+      topk_docs / topk_scores / topk_counts   (scored top-K parts) the top-K blocks
+      docset_hash_lo / _hi   (DocumentsOnly parts) the two 32-bit halves of every query's FNV-1a docset hash (tri_batch_docset_hashes)
+      sample_queries / sample_docids   (DocumentsOnly parts) a seeded choice of DUMP_SAMPLE_QUERIES queries and the first DUMP_SAMPLE_DOCS docIDs
+                             of each set, padded with -1
+    Per-query arrays that would take the files past DUMP_BUDGET_BYTES are cut to the same seeded sample of rows, named by part<p>_rows."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    per_part, fixed = [], {}
+    for p, (pt, b) in enumerate(zip(parts, bs)):
+        rows = {"counts": b.counts().astype(np.float64)}
+        if (pt.flags & T.FLAG_ACCUMULATED_SCORE) and pt.topk:
+            d, s, c = b.topk_results()
+            rows.update(topk_docs=d.astype(np.float64), topk_scores=s.astype(np.float32), topk_counts=c.astype(np.float64))
+        elif not dry:
+            h = b.docset_hashes()
+            rows.update(docset_hash_lo=(h & 0xFFFFFFFF).astype(np.float64), docset_hash_hi=(h >> 32).astype(np.float64))
+            qs = np.sort(rng.choice(b.nq, min(DUMP_SAMPLE_QUERIES, b.nq), replace=False))
+            sample = np.full((len(qs), DUMP_SAMPLE_DOCS), -1.0)
+            for i, q in enumerate(qs):
+                ids = b.docset(int(q), int(rows["counts"][q]))[:DUMP_SAMPLE_DOCS]
+                sample[i, : len(ids)] = ids
+            fixed[f"part{p}_sample_queries"] = qs.astype(np.float64)
+            fixed[f"part{p}_sample_docids"] = sample
+        per_part.append(rows)
+    room = DUMP_BUDGET_BYTES - (64 << 10) - sum(a.nbytes for a in fixed.values())  # (64 KB: the files' headers)
+    row_bytes = sum(a.nbytes for rows in per_part for a in rows.values())
+    cut_bytes = row_bytes + 8 * sum(len(rows["counts"]) for rows in per_part)  # (a cut part also writes the indices of the rows it keeps)
+    files = dict(fixed)
+    for p, rows in enumerate(per_part):
+        nq = len(rows["counts"])
+        if row_bytes > room:  # (every part keeps the same share of its rows)
+            keep = np.sort(rng.choice(nq, max(1, int(nq * room / cut_bytes)), replace=False))
+            rows = {k: a[keep] for k, a in rows.items()}
+            files[f"part{p}_rows"] = keep.astype(np.float64)
+        files.update({f"part{p}_{k}": a for k, a in rows.items()})
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def pmc_traffic(args, world):
@@ -839,11 +913,12 @@ def program_text(prog):
     return t[1:-1] if t.startswith("(") and t.endswith(")") and t.count("(") == 1 else t
 
 
-def cpu_reference(seg, pt, progs, gcounts, budget_s):
+def cpu_reference(seg, pt, progs, gcounts, budget_s, exe=None):
     """The GENUINE reference on the same sample: oracle/_ref/ref_driver (the reference's own sources compiled where they lie, oracle/Makefile) indexes
     the same synthetic corpus with the reference's encoder and runs exec_query over the queries' text, one thread, the clock around exec_query only.
-    Google codec only (the Lucene side of the reference needs a library this image lacks).  Never fails the run: an error is reported in its place."""
-    exe = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
+    Google codec only (the Lucene side of the reference needs a library this image lacks).  Never fails the run: an error is reported in its place.
+    `exe`: another driver that speaks ref_driver's `timed` command (the tests' replay of stored answers)."""
+    exe = exe or os.path.join(ROOT, "oracle", "_ref", "ref_driver")
     try:
         if not os.path.exists(exe):
             return {"error": "oracle/_ref/ref_driver is not built (it is built where /root/reference exists: __graft_entry__.build())"}

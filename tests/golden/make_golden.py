@@ -10,6 +10,7 @@ usage: python tests/golden/make_golden.py
 """
 import json
 import os
+import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -388,7 +389,61 @@ def commit_fixture():
     print(path, len(res), "records", os.path.getsize(path), "bytes")
 
 
+LIVE_CORPUS = (50000, 3000, 10, 99)  # tests/test_oracle.py::test_live_reference_random_queries: a size the other fixtures do not hold
+LIVE_TEMPLATES = ["t{a} t{b}", "t{a} OR t{b} OR t{c}", "t{a} t{b} (t{c} OR t{d} OR t{e})", '"t{a} t{b}"', "(t{a} OR t{b}) (t{c} OR t{d}) t{e}"]
+
+
+def live_commands():
+    """Seeded random 2..5-term shapes over the live corpus, each unscored and BM25 top-10."""
+    cmds = ["index"]
+    for i, (a, b, c, d, e) in enumerate(O.gen_queries(LIVE_CORPUS[1], 4242, 40, 5).tolist()):
+        text = LIVE_TEMPLATES[i % len(LIVE_TEMPLATES)].format(a=a, b=b, c=c, d=d, e=e)
+        for fl in (1, 2):
+            cmds.append(f"query {fl} {10 if fl == 2 else 0} {text}")
+    return cmds
+
+
+def live_fixture():
+    D, V, slots, seed = LIVE_CORPUS
+    cmds = live_commands()
+    res = O.run_ref_driver(D, V, slots, seed, cmds)
+    assert len(res) == len(cmds), (len(res), len(cmds))
+    path = os.path.join(HERE, "ref_live.json")
+    with open(path, "w") as f:
+        json.dump({"corpus": {"D": D, "V": V, "slots": slots, "seed": seed}, "commands": cmds, "results": res}, f, separators=(",", ":"))
+    print(path, len(res), "records", os.path.getsize(path), "bytes")
+
+
+CPU_LEG_CORPUS = (20000, 2000, 10, 42)  # tests/test_bench_launch.py: bench.py's CPU leg of kind "reference"
+CPU_LEG_TEXTS = ["t0 t1", "t3 OR t5 OR t9", "t0 t1 (t2 OR t3 OR t4)", "t3 t5 NOT t1", '"t0 t1" t2', '"t4 t5 t6"', "t0 <t7>", "t1 NOT (t2 OR t3)", "t11 t400", "t1999 t3"]
+
+
+def cpu_leg_fixture():
+    """What ref_driver's `timed` command answers for the CPU-leg texts as bench.py hands them over (program_text of the parsed query), unscored
+    and scored: the match counts (and the timings of that one run)."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(os.path.dirname(os.path.dirname(HERE)), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    D, V, slots, seed = CPU_LEG_CORPUS
+    driver_texts = [bench.program_text(O.parse_query(t)) for t in CPU_LEG_TEXTS]
+    runs = []
+    for flags in (1, 2):
+        inp = f"timed {flags} 5.000 {len(driver_texts)} 4\n" + "\n".join(driver_texts) + "\n"
+        out = subprocess.run([O.REF_DRIVER, str(D), str(V), str(slots), str(seed)], input=inp, capture_output=True, text=True, check=True, timeout=300)
+        runs.append({"flags": flags, "lines": [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]})
+    path = os.path.join(HERE, "ref_cpu_leg.json")
+    with open(path, "w") as f:
+        json.dump({"corpus": {"D": D, "V": V, "slots": slots, "seed": seed}, "texts": CPU_LEG_TEXTS, "driver_texts": driver_texts, "runs": runs}, f, separators=(",", ":"))
+    print(path, os.path.getsize(path), "bytes")
+
+
 def main():
+    if "--live-only" in sys.argv:
+        return live_fixture()
+    if "--cpu-leg-only" in sys.argv:
+        return cpu_leg_fixture()
     if "--commit-only" in sys.argv:
         return commit_fixture()
     if "--merge-only" in sys.argv:

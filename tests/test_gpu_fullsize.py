@@ -198,7 +198,7 @@ def test_the_100k_mixed_batch_runs_whole_on_one_gpu():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scaling", "strong", "--workload", "cfg5", "--queries", "100000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "4",
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scaling", "strong", "--workload", "cfg5", "--queries", "100000", "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "4",
                           "--rotating-sets", "0", "--delivered-steps", "0", "--scaling-ref-steps", "0"], capture_output=True, text=True, timeout=1200)  # fmt: skip
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])

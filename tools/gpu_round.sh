@@ -29,7 +29,7 @@ for stage in "$@"; do
     bench:*)
       # bench:<name>:<args with , for spaces>
       name="$(echo "$stage" | cut -d: -f2)"; args="$(echo "$stage" | cut -d: -f3- | tr ',' ' ')"
-      timeout -k 10 900 python bench.py $args > "$out/bench_$name.json" 2> "$out/bench_$name.err"; rc=$?
+      timeout -k 10 900 python bench.py --full $args > "$out/bench_$name.json" 2> "$out/bench_$name.err"; rc=$?
       cat "$out/bench_$name.json"; tail -3 "$out/bench_$name.err"; log "bench $name rc=$rc" ;;
     prof:*)
       name="$(echo "$stage" | cut -d: -f2)"; args="$(echo "$stage" | cut -d: -f3- | tr ',' ' ')"
