@@ -177,6 +177,17 @@ namespace trip {
         constexpr uint64_t CAND_ROWS_MIN_LEAD = 1024;
         // launch order of the task kinds: TASK_DENSE, TASK_PSET, TASK_PROBE, TASK_CAND, then the one-pass kinds as numbered
         constexpr uint32_t SCHED_RANK[TASK_KINDS] = {3, 0, 4, 5, 6, 7, 8, 1, 2, 9};
+        // per task kind, the BatchPlan counter of its sched[] section
+        constexpr uint32_t BatchPlan::*const SCHED_COUNT[TASK_KINDS] = {&BatchPlan::n_cand, &BatchPlan::n_dense, &BatchPlan::n_fused, &BatchPlan::n_fused16, &BatchPlan::n_fusedgen,
+                                                                        &BatchPlan::n_planes, &BatchPlan::n_planes8, &BatchPlan::n_pset, &BatchPlan::n_probe, &BatchPlan::n_tree};
+        // the first sched[] index of a kind's section: the sections of the kinds that launch before it come first
+        inline uint32_t sched_first(const BatchPlan &P, const uint32_t kind) {
+                uint32_t at = 0;
+                for (uint32_t k = 0; k < TASK_KINDS; ++k)
+                        if (SCHED_RANK[k] < SCHED_RANK[kind])
+                                at += P.*SCHED_COUNT[k];
+                return at;
+        }
         inline uint32_t sched_key(const uint32_t kind, const uint64_t cost) {
                 if (kind == TASK_PSET) // by docID window range, ascending (`cost` holds the first window)
                         return SCHED_RANK[TASK_PSET] * SCHED_NB + (uint32_t)std::min<uint64_t>((cost & 0xffffffffull) / PSET_TASK_WINDOWS, SCHED_NB - 1);
@@ -2140,7 +2151,6 @@ inline int plan_batch(const HostIndex &ix, const PlanEnv &env, const PlanInput &
         //      other keep their order in the batch: all a longest-first dispatch needs; TASK_PSET goes by docID window range instead.  The
         //      fragments counted their tasks per bucket in the fill pass; their places are settled here, the scatter runs on the pool again
         {
-                uint32_t *const per_kernel[TASK_KINDS] = {&P.n_dense, &P.n_pset, &P.n_probe, &P.n_cand, &P.n_fused, &P.n_fused16, &P.n_fusedgen, &P.n_planes, &P.n_planes8, &P.n_tree};
                 uint32_t at = 0;
                 for (uint32_t r = 0; r < TASK_KINDS; ++r) {
                         const uint32_t before = at;
@@ -2164,16 +2174,18 @@ inline int plan_batch(const HostIndex &ix, const PlanEnv &env, const PlanInput &
                                                 cand_qat[(bk - CAND_KEY0) / CAND_SUBS] = at;
                                         place(bk);
                                 }
-                        *per_kernel[r] = at - before;
+                        for (uint32_t k = 0; k < TASK_KINDS; ++k)
+                                if (SCHED_RANK[k] == r)
+                                        P.*SCHED_COUNT[k] = at - before;
                 }
-                const uint32_t n_dense = P.n_dense, n_units_run = P.n_pset + P.n_probe;
+                const uint32_t units_first = sched_first(P, TASK_PSET), n_units_run = P.n_pset + P.n_probe;
                 run([&](unsigned k) {
                         Frag &f = frags[k];
                         for (size_t i = 0; i < f.tasks.size(); ++i) {
                                 const uint32_t pos = f.hist[f.keys[i]]++, ti = (uint32_t)(f.b_tasks + i);
                                 P.sched[pos] = ti;
-                                if (pos >= n_dense && pos - n_dense < n_units_run) // (a TASK_PSET / TASK_PROBE task: its unit record runs at the same place)
-                                        P.pset_sched[pos - n_dense] = unit_of_task[ti];
+                                if (pos >= units_first && pos - units_first < n_units_run) // (a TASK_PSET / TASK_PROBE task: its unit record runs at the same place)
+                                        P.pset_sched[pos - units_first] = unit_of_task[ti];
                         }
                 });
         }

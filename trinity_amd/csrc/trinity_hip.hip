@@ -82,7 +82,7 @@ struct tri_dev {
         } pool;
         // ... likewise the pinned host blocks the plans are laid out in (hipHostMalloc costs about a millisecond per megabyte) ...
         std::vector<std::pair<size_t, void *>> pinned_idle;
-        // ... and the HIP events of a batch (nine per batch)
+        // ... and the HIP events of a batch (EV_COUNT per batch)
         std::vector<hipEvent_t> events_idle;
         // The planner's host threads: PLAN_CTXS independent planner contexts — a pool of host threads and the per-fragment arrays it recycles, under a
         // lock of their own — so that TWO threads may compile batches of this device at the same time (a create is 0.6 - 1.1 ms of host planning for
@@ -102,8 +102,22 @@ struct tri_dev {
         std::recursive_mutex mu;
 };
 using DevLock = std::lock_guard<std::recursive_mutex>;
-constexpr size_t TICKET_SCAT_WORD = 44;        // ... k_psets_prep's cursor into the batch's scatter list
-constexpr size_t TICKET_CAND_WORD = 64;        // a batch's ticket words: [0, 64) one per kernel; then k_and's CAND_QUEUES, 64 bytes apart
+// a batch's ticket words (zeroed at every run): [0, TICKET_CAND_WORD) one per kernel; then k_and's CAND_QUEUES, 64 bytes apart
+constexpr size_t TICKET_DENSE_WORD = 16;      // k_and_dense
+constexpr size_t TICKET_PSET_WORD = 20;       // k_psets
+constexpr size_t TICKET_PROBE_WORD = 22;      // k_probe
+constexpr size_t TICKET_PLANES_WORD = 24;     // k_planes: + 2 for the wide instantiation
+constexpr size_t TICKET_SCORE_WORD = 32;      // k_score ...
+constexpr size_t TICKET_RICH_COUNT_WORD = TICKET_SCORE_WORD; // ... and k_rich's count pass share it: a batch is either scored or reports matched terms, never both
+                                                            // (tri_batch_create: the modes are mutually exclusive)
+constexpr size_t TICKET_RICH_WRITE_WORD = 40; // k_rich's write pass (cleared again before it)
+constexpr size_t TICKET_SCAT_WORD = 44;       // k_psets_prep's cursor into the batch's scatter list (+ 1: k_psets_prep_list's count of scatter queries)
+constexpr size_t TICKET_PHRASE_WORD = 48;     // k_phrase
+constexpr size_t TICKET_FUSED_WORD = 56;      // k_fused: + 2 * variant (32-bit window words, 16-bit ones, general trees)
+constexpr size_t TICKET_CAND_WORD = 64;
+static_assert(std::max({TICKET_DENSE_WORD, TICKET_PSET_WORD, TICKET_PROBE_WORD, TICKET_PLANES_WORD + 2, TICKET_SCORE_WORD, TICKET_RICH_COUNT_WORD, TICKET_RICH_WRITE_WORD,
+                        TICKET_SCAT_WORD + 1, TICKET_PHRASE_WORD, TICKET_FUSED_WORD + 2 * 2}) < TICKET_CAND_WORD,
+              "every kernel's ticket word lies below k_and's queues");
 constexpr size_t TICKET_BYTES = (TICKET_CAND_WORD + CAND_QUEUES * CAND_TICKET_STRIDE) * 4;
 constexpr size_t POOL_MIN_BYTES = 64u << 10;  // smaller buffers are not worth pooling
 constexpr size_t POOL_IDLE_CAP = 64ull << 30; // idle buffers beyond this are given back to the device (largest first)
@@ -342,6 +356,10 @@ struct tri_index : HostIndex {
         }
 };
 
+// a batch's HIP events, in the order they are recorded: EV_UP, the plan has arrived (upload stream); then on the engine stream the run's start,
+// the end of each of its stages (tri_batch_run), the run's end
+enum BatchEvent { EV_UP, EV_START, EV_PLANE_ROWS, EV_DENSE, EV_PSET, EV_PROBE, EV_CAND, EV_FUSED, EV_PLANES, EV_PHRASE, EV_TREE, EV_END, EV_COUNT };
+
 // a compiled batch: the plan (BatchPlan: the host block with every array the kernels read, laid out by the planner) and its device side —
 // ONE arena that holds the block's copy followed by the batch's small device-only arrays, plus the large pooled buffers
 struct tri_batch : BatchPlan {
@@ -359,9 +377,7 @@ struct tri_batch : BatchPlan {
         unsigned long long *d_qthr = nullptr; // k_planes: per query, the best k-th score any of its tasks has seen (cleared at every run)
         uint32_t *d_sparse = nullptr;      // k_planes: per resident workgroup, the lists of a task's decoded (non-plane) slots
         DevFused *d_fused = nullptr;
-        // HIP events on the engine stream: start, after k_term_planes, k_and_dense, k_and, k_fused, k_planes, k_phrase, end (owned by the
-        // batch: two batches in flight on one device keep their own timings); ev_up: the plan has arrived (upload stream)
-        hipEvent_t ev0 = nullptr, ev_a = nullptr, ev_s = nullptr, ev_r = nullptr, ev_b = nullptr, ev_c = nullptr, ev_p = nullptr, ev1 = nullptr, ev_pl = nullptr, ev_k = nullptr, ev_up = nullptr, ev_t = nullptr; // (ev_s: after k_psets; ev_r: after k_probe; ev_t: after the tree kernels)
+        hipEvent_t ev[EV_COUNT] = {}; // (owned by the batch: two batches in flight on one device keep their own timings)
         // TASK_TREE (k_tree.hpp): one scratch block — [tree rows: a PL_PLANES-plane row per distinct term leaf][phrase rows: a plane per hidden phrase query]
         // [a match bitmap per tree query][per query and chunk: matches][(term, row) pairs for k_term_planes]
         uint32_t *d_tree_scratch = nullptr, *d_tree_rows = nullptr, *d_tree_prows = nullptr, *d_tree_qbits = nullptr, *d_tree_cc = nullptr, *d_tree_build = nullptr;
@@ -407,17 +423,14 @@ struct tri_batch : BatchPlan {
                         hipSetDevice(dev->device);
                         if (ran && !synced) // (its large buffers go back to the device's pool: nothing of this batch may still be running on them)
                                 hipStreamSynchronize(dev->stream);
-                        if (ev_up)
-                                hipEventSynchronize(ev_up); // (the pinned block goes back to the pool: its copy must have left)
+                        if (ev[EV_UP])
+                                hipEventSynchronize(ev[EV_UP]); // (the pinned block goes back to the pool: its copy must have left)
                 }
-                for (hipEvent_t e : {ev0, ev_a, ev_s, ev_r, ev_b, ev_c, ev_p, ev1, ev_pl, ev_k, ev_up, ev_t})
-                        if (e) {
-                                if (dev) {
-                                        DevLock g(dev->mu);
-                                        dev->events_idle.push_back(e);
-                                } else
-                                        hipEventDestroy(e);
-                        }
+                for (hipEvent_t e : ev)
+                        if (dev)
+                                event_put(dev, e);
+                        else if (e)
+                                hipEventDestroy(e);
                 pinned_free(dev, block, block_cap);
                 pool_free(dev, d_arena);
                 pool_free(dev, d_sparse);
@@ -456,14 +469,17 @@ struct tri_batch : BatchPlan {
 #include "k_commit.hpp"
 #include "k_lencode.hpp"
 
-// launch the instantiation of a codec-templated kernel that matches the uploaded segment
-#define TRI_LAUNCH(K, codec, grid, block, stream, ...)                                              \
-        do {                                                                                        \
-                if ((codec) == TRI_CODEC_LUCENE)                                                    \
-                        hipLaunchKernelGGL(K<CODEC_LUCENE>, grid, block, 0, stream, __VA_ARGS__);   \
-                else                                                                                \
-                        hipLaunchKernelGGL(K<CODEC_GOOGLE>, grid, block, 0, stream, __VA_ARGS__);   \
-        } while (0)
+// launch the instantiation of a codec-templated kernel that matches the uploaded segment: `pick` maps the codec (a std::integral_constant: the
+// kernel template's first argument) to the kernel, and chooses the template's other arguments, if it has any
+template <class Pick, class... Args>
+static void tri_launch(const int codec, Pick pick, const dim3 grid, const dim3 block, const hipStream_t stream, Args... args) {
+        if (codec == TRI_CODEC_LUCENE)
+                hipLaunchKernelGGL(pick(std::integral_constant<int, CODEC_LUCENE>()), grid, block, 0, stream, args...);
+        else
+                hipLaunchKernelGGL(pick(std::integral_constant<int, CODEC_GOOGLE>()), grid, block, 0, stream, args...);
+}
+// ... of a kernel whose only template argument is the codec
+#define TRI_LAUNCH(K, codec, grid, block, stream, ...) tri_launch(codec, [](auto c_) { return K<c_.value>; }, grid, block, stream, __VA_ARGS__)
 
 // ------------------------------------------------------------------------------------------ host: device
 extern "C" int tri_dev_open(int device, tri_dev **out) {
@@ -741,6 +757,147 @@ extern "C" int tri_decode_terms(tri_index *ix, const uint32_t *terms, size_t n, 
 }
 
 // ------------------------------------------------------------------------------------------ host: batches
+// The index's plane cache holds a row for every term the batch could name (row = df rank < plane_rows), plus an all-zero row: what a
+// k_planes slot WITHOUT term planes reads (so its sweep needs no select).  Grown WITHOUT draining the engine stream (round 4 synchronised
+// it here: a stall in the serving loop whenever a batch was planned with more eligible terms): the rows move on the upload stream behind
+// everything the engine stream holds so far (runs that read or build the old rows), later runs wait for the move's event (tri_batch_run),
+// and the old buffers are retired — pooled again once that point has passed.  Everything a growth needs is taken before the index is
+// touched: when an allocation fails, what was taken goes back and the index is as it was.
+static int fit_plane_cache(tri_batch *b, const bool planes_tasks) {
+        tri_index *ix = b->ix;
+        tri_dev *dev = b->dev;
+        const uint32_t want = std::max<uint32_t>(1, b->plane_rows);
+        // (rows whose readers are through go back to the pool: no call here waits for the device)
+        for (size_t i = 0; i < ix->pc_retired.size();)
+                if (hipEventQuery(ix->pc_retired[i].second) == hipSuccess) {
+                        pool_free(dev, ix->pc_retired[i].first);
+                        event_put(dev, ix->pc_retired[i].second);
+                        ix->pc_retired.erase(ix->pc_retired.begin() + (long)i);
+                } else
+                        ++i;
+        // (does this batch read the rows' HIGH parts — a scored batch whose one-pass kernel or scorers read planes?)
+        b->planes_hi = planes_tasks || !b->splane.empty();
+        if (want <= ix->pc_cap && b->plw == ix->pc_plw && (!b->planes_hi || ix->d_pcache_hi))
+                return TRI_OK;
+        const size_t row = (size_t)b->plw * 4, row_hi = (size_t)PL_HI * b->plw * 4, groups = b->plw / 8;
+        const bool resize = want > ix->pc_cap || b->plw != ix->pc_plw; // (else: only the high region is new)
+        const bool new_hi = (b->planes_hi || ix->d_pcache_hi) && (resize || !ix->d_pcache_hi);
+        const bool same_plw = ix->d_pcache && b->plw == ix->pc_plw;
+        const uint32_t cap = std::max(want, b->plw == ix->pc_plw ? ix->pc_cap : 0u);
+        // the rank directories and hits entries of the rows (k_phrase's rank path): sized for every row the cache can hold, moved like the rows
+        std::vector<uint64_t> hs;
+        std::vector<uint32_t> rt;
+        if (resize) {
+                hs.assign(cap + 1, 0);
+                rt.assign(cap, 0xffffffffu);
+                for (size_t t = 0; t < ix->terms.size(); ++t)
+                        if (ix->df_rank[t] < cap)
+                                rt[ix->df_rank[t]] = (uint32_t)t;
+                for (uint32_t r = 0; r < cap; ++r)
+                        hs[r + 1] = hs[r] + (rt[r] != 0xffffffffu ? ix->terms[rt[r]].documents : 0u);
+        }
+        // the buffers this growth replaces: retired on events recorded on the UPLOAD stream, behind the copies that read them — that point is past
+        // the engine stream's earlier readers too (stream_up waits for `drained`).  (Round 5 retired them on events of the engine stream recorded
+        // BEFORE the copies were enqueued: the next tri_batch_create could pool a buffer the copy had not read yet.)
+        std::vector<void *> outgrown;
+        if (resize && ix->d_prank) // (retired with the rows: same readers, and the copies below read them)
+                outgrown = {ix->d_prank, ix->d_phs, ix->d_hs_off, ix->d_ph_pairs};
+        if (resize && ix->d_pcache)
+                outgrown.push_back(ix->d_pcache);
+        if (new_hi && ix->d_pcache_hi)
+                outgrown.push_back(ix->d_pcache_hi);
+        // ---- take every buffer and event first
+        uint32_t *fresh = nullptr, *fresh_hi = nullptr, *pairs = nullptr, *prank = nullptr, *term_row = nullptr;
+        unsigned long long *phs = nullptr;
+        uint64_t *hso = nullptr;
+        hipEvent_t drained = nullptr, ready = nullptr;
+        std::vector<hipEvent_t> retire(outgrown.size(), nullptr);
+        hipError_t e = hipSuccess;
+        auto take = [&](auto **buf, const size_t bytes) { e = e == hipSuccess ? pool_alloc(dev, (void **)buf, bytes) : e; };
+        if (resize)
+                take(&fresh, ((size_t)cap + 1) * row + 64);
+        if (new_hi)
+                take(&fresh_hi, ((size_t)cap + 1) * row_hi + 64);
+        if (resize) {
+                take(&pairs, (size_t)cap * 8 + POOL_MIN_BYTES);
+                take(&prank, (size_t)cap * groups * PL_RANK_WORDS * 4 + 64);
+                take(&phs, (hs[cap] + 8) * 8);
+                take(&hso, ((size_t)cap + 1) * 8 + POOL_MIN_BYTES);
+                if (e == hipSuccess && !ix->d_term_row)
+                        e = hipMalloc((void **)&term_row, (ix->terms.size() + 1) * 4);
+        }
+        if (e == hipSuccess)
+                e = event_get(dev, &drained);
+        if (e == hipSuccess && !ix->ev_pc_ready)
+                e = event_get(dev, &ready);
+        for (hipEvent_t &r : retire)
+                if (e == hipSuccess)
+                        e = event_get(dev, &r);
+        if (e != hipSuccess) {
+                for (void *p : {(void *)fresh, (void *)fresh_hi, (void *)pairs, (void *)prank, (void *)phs, (void *)hso})
+                        pool_free(dev, p);
+                hipFree(term_row);
+                event_put(dev, drained);
+                event_put(dev, ready);
+                for (hipEvent_t r : retire)
+                        event_put(dev, r);
+                return fail(e == hipErrorOutOfMemory ? TRI_ERR_NOMEM : TRI_ERR_DEVICE, "tri_batch_create: growing the plane cache: %s", hipGetErrorString(e));
+        }
+        // ---- then the rows move
+        if (ready)
+                ix->ev_pc_ready = ready;
+        HIP_TRY(hipEventRecord(drained, dev->stream));
+        HIP_TRY(hipStreamWaitEvent(dev->stream_up, drained, 0));
+        if (fresh) {
+                if (same_plw)
+                        HIP_TRY(hipMemcpyAsync(fresh, ix->d_pcache, (size_t)ix->pc_cap * row, hipMemcpyDeviceToDevice, dev->stream_up));
+                else
+                        ix->pc_built.clear();
+                HIP_TRY(hipMemsetAsync((uint8_t *)fresh + (size_t)cap * row, 0, row + 64, dev->stream_up));
+        }
+        if (fresh_hi) {
+                if (same_plw && ix->d_pcache_hi)
+                        HIP_TRY(hipMemcpyAsync(fresh_hi, ix->d_pcache_hi, (size_t)ix->pc_cap * row_hi, hipMemcpyDeviceToDevice, dev->stream_up));
+                else
+                        for (auto &bb : ix->pc_built)
+                                bb &= (uint8_t)~2u; // (no row has its high part yet)
+                HIP_TRY(hipMemsetAsync((uint8_t *)fresh_hi + (size_t)cap * row_hi, 0, row_hi + 64, dev->stream_up));
+        }
+        if (resize) {
+                if (same_plw && ix->d_prank) {
+                        HIP_TRY(hipMemcpyAsync(pairs, ix->d_ph_pairs, ix->ph_pairs_n * 8, hipMemcpyDeviceToDevice, dev->stream_up));
+                        HIP_TRY(hipMemcpyAsync(prank, ix->d_prank, (size_t)ix->pc_cap * groups * PL_RANK_WORDS * 4, hipMemcpyDeviceToDevice, dev->stream_up));
+                        HIP_TRY(hipMemcpyAsync(phs, ix->d_phs, ix->hs_off[ix->pc_cap] * 8, hipMemcpyDeviceToDevice, dev->stream_up));
+                } else {
+                        ix->ph_built.clear();
+                        ix->ph_pairs_n = 0;
+                }
+                ix->hs_off = std::move(hs); // (a row's offset depends on the rows before it alone: what was built stays where it was)
+                HIP_TRY(hipMemcpyAsync(hso, ix->hs_off.data(), ((size_t)cap + 1) * 8, hipMemcpyHostToDevice, dev->stream_up)); // (hs_off outlives the copy: a member)
+                if (term_row)
+                        ix->d_term_row = term_row;
+                if (term_row || !same_plw)
+                        HIP_TRY(hipMemsetAsync(ix->d_term_row, 0xff, (ix->terms.size() + 1) * 4, dev->stream_up));
+                ix->d_prank = prank, ix->d_phs = phs, ix->d_hs_off = hso, ix->d_ph_pairs = pairs;
+                ix->rank_term = std::move(rt);
+                ix->ph_built.resize(cap, 0);
+        }
+        HIP_TRY(hipEventRecord(ix->ev_pc_ready, dev->stream_up));
+        for (size_t i = 0; i < outgrown.size(); ++i) {
+                HIP_TRY(hipEventRecord(retire[i], dev->stream_up));
+                ix->pc_retired.emplace_back(outgrown[i], retire[i]);
+        }
+        event_put(dev, drained);
+        if (fresh)
+                ix->d_pcache = fresh;
+        if (fresh_hi)
+                ix->d_pcache_hi = fresh_hi;
+        ix->pc_cap = cap;
+        ix->pc_plw = b->plw;
+        ix->pc_built.resize(cap, 0);
+        return TRI_OK;
+}
+
 // tri_batch_create = the host planner (planner.hpp: lowering, execution classes, tasks, term planes, schedule — on the device handle's
 // host threads) + the plan's way to the device: ONE pinned block, ONE arena, ONE copy on the upload stream.  Everything a steady caller
 // needs per batch comes from the handle's pools (arena, pinned block, output regions, events): no hipMalloc, no hipFree, no device
@@ -897,128 +1054,16 @@ extern "C" int tri_batch_create(tri_index *ix, const uint32_t *prog, size_t prog
         b->d_top_counts = scored ? (uint32_t *)(A + a_top_counts) : nullptr;
         b->d_top_docs = scored ? (uint32_t *)(A + a_top_docs) : nullptr;
         b->d_top_scores = scored ? (float *)(A + a_top_scores) : nullptr;
-        for (hipEvent_t *e : {&b->ev0, &b->ev_a, &b->ev_s, &b->ev_r, &b->ev_b, &b->ev_c, &b->ev_p, &b->ev1, &b->ev_pl, &b->ev_k, &b->ev_up, &b->ev_t})
-                HIP_TRY(event_get(dev, e));
+        for (hipEvent_t &e : b->ev)
+                HIP_TRY(event_get(dev, &e));
         if (b->block_bytes)
                 HIP_TRY(hipMemcpyAsync(A, b->block, b->block_bytes, hipMemcpyHostToDevice, dev->stream_up));
         HIP_TRY(hipMemsetAsync(A + a_zero, 0, a - a_zero, dev->stream_up));
         dbg_lap(1);
         // ---- the large buffers (the device handle's pool)
-        if (!b->plane_terms.empty() || planes_tasks) {
-                // the index's plane cache holds a row for every term this batch could name (row = df rank < plane_rows), plus an all-zero row:
-                // what a k_planes slot WITHOUT term planes reads (so its sweep needs no select)
-                const uint32_t want = std::max<uint32_t>(1, b->plane_rows);
-                // (rows whose readers are through go back to the pool: no call here waits for the device)
-                for (size_t i = 0; i < ix->pc_retired.size();)
-                        if (hipEventQuery(ix->pc_retired[i].second) == hipSuccess) {
-                                pool_free(dev, ix->pc_retired[i].first);
-                                event_put(dev, ix->pc_retired[i].second);
-                                ix->pc_retired.erase(ix->pc_retired.begin() + (long)i);
-                        } else
-                                ++i;
-                // (does this batch read the rows' HIGH parts — a scored batch whose one-pass kernel or scorers read planes?)
-                b->planes_hi = planes_tasks || !b->splane.empty();
-                if (want > ix->pc_cap || b->plw != ix->pc_plw || (b->planes_hi && !ix->d_pcache_hi)) {
-                        // Grown WITHOUT draining the engine stream (round 4 synchronised it here: a stall in the serving loop whenever a batch was planned with more
-                        // eligible terms): the rows move on the upload stream behind everything the engine stream holds so far (runs that read or build the old
-                        // rows), later runs wait for the move's event (tri_batch_run), and the old buffer is retired — pooled again once that point has passed
-                        const size_t row = (size_t)b->plw * 4, row_hi = (size_t)PL_HI * b->plw * 4;
-                        const bool resize = want > ix->pc_cap || b->plw != ix->pc_plw; // (else: only the high region is new)
-                        const uint32_t cap = std::max(want, b->plw == ix->pc_plw ? ix->pc_cap : 0u);
-                        const bool with_hi = b->planes_hi || ix->d_pcache_hi;
-                        uint32_t *fresh = nullptr, *fresh_hi = nullptr;
-                        if (resize)
-                                HIP_TRY(pool_alloc(dev, (void **)&fresh, ((size_t)cap + 1) * row + 64));
-                        if (with_hi && (resize || !ix->d_pcache_hi))
-                                HIP_TRY(pool_alloc(dev, (void **)&fresh_hi, ((size_t)cap + 1) * row_hi + 64));
-                        hipEvent_t drained = nullptr;
-                        std::vector<void *> outgrown; // the buffers this growth replaces
-                        HIP_TRY(event_get(dev, &drained));
-                        if (!ix->ev_pc_ready)
-                                HIP_TRY(event_get(dev, &ix->ev_pc_ready));
-                        HIP_TRY(hipEventRecord(drained, dev->stream));
-                        HIP_TRY(hipStreamWaitEvent(dev->stream_up, drained, 0));
-                        const bool same_plw = ix->d_pcache && b->plw == ix->pc_plw;
-                        if (fresh) {
-                                if (same_plw)
-                                        HIP_TRY(hipMemcpyAsync(fresh, ix->d_pcache, (size_t)ix->pc_cap * row, hipMemcpyDeviceToDevice, dev->stream_up));
-                                else
-                                        ix->pc_built.clear();
-                                HIP_TRY(hipMemsetAsync((uint8_t *)fresh + (size_t)cap * row, 0, row + 64, dev->stream_up));
-                        }
-                        if (fresh_hi) {
-                                if (same_plw && ix->d_pcache_hi)
-                                        HIP_TRY(hipMemcpyAsync(fresh_hi, ix->d_pcache_hi, (size_t)ix->pc_cap * row_hi, hipMemcpyDeviceToDevice, dev->stream_up));
-                                else
-                                        for (auto &bb : ix->pc_built)
-                                                bb &= (uint8_t)~2u; // (no row has its high part yet)
-                                HIP_TRY(hipMemsetAsync((uint8_t *)fresh_hi + (size_t)cap * row_hi, 0, row_hi + 64, dev->stream_up));
-                        }
-                        if (resize) {
-                                // the rank directories and hits entries of the rows (k_phrase's rank path): sized for every row the cache can hold, moved like the rows
-                                const bool same = same_plw;
-                                std::vector<uint64_t> hs(cap + 1, 0);
-                                std::vector<uint32_t> rt(cap, 0xffffffffu);
-                                for (size_t t = 0; t < ix->terms.size(); ++t)
-                                        if (ix->df_rank[t] < cap)
-                                                rt[ix->df_rank[t]] = (uint32_t)t;
-                                for (uint32_t r = 0; r < cap; ++r)
-                                        hs[r + 1] = hs[r] + (rt[r] != 0xffffffffu ? ix->terms[rt[r]].documents : 0u);
-                                uint32_t *prank = nullptr;
-                                unsigned long long *phs = nullptr;
-                                uint64_t *hso = nullptr;
-                                uint32_t *pairs = nullptr;
-                                const size_t groups = b->plw / 8;
-                                HIP_TRY(pool_alloc(dev, (void **)&pairs, (size_t)cap * 8 + POOL_MIN_BYTES));
-                                HIP_TRY(pool_alloc(dev, (void **)&prank, (size_t)cap * groups * PL_RANK_WORDS * 4 + 64));
-                                HIP_TRY(pool_alloc(dev, (void **)&phs, (hs[cap] + 8) * 8));
-                                HIP_TRY(pool_alloc(dev, (void **)&hso, ((size_t)cap + 1) * 8 + POOL_MIN_BYTES));
-                                if (same && ix->d_prank) {
-                                        HIP_TRY(hipMemcpyAsync(pairs, ix->d_ph_pairs, ix->ph_pairs_n * 8, hipMemcpyDeviceToDevice, dev->stream_up));
-                                        HIP_TRY(hipMemcpyAsync(prank, ix->d_prank, (size_t)ix->pc_cap * groups * PL_RANK_WORDS * 4, hipMemcpyDeviceToDevice, dev->stream_up));
-                                        HIP_TRY(hipMemcpyAsync(phs, ix->d_phs, ix->hs_off[ix->pc_cap] * 8, hipMemcpyDeviceToDevice, dev->stream_up));
-                                } else {
-                                        ix->ph_built.clear();
-                                        ix->ph_pairs_n = 0;
-                                }
-                                ix->hs_off = hs; // (a row's offset depends on the rows before it alone: what was built stays where it was)
-                                HIP_TRY(hipMemcpyAsync(hso, ix->hs_off.data(), ((size_t)cap + 1) * 8, hipMemcpyHostToDevice, dev->stream_up)); // (hs_off outlives the copy: a member)
-                                if (!ix->d_term_row) {
-                                        HIP_TRY(hipMalloc((void **)&ix->d_term_row, (ix->terms.size() + 1) * 4));
-                                        HIP_TRY(hipMemsetAsync(ix->d_term_row, 0xff, (ix->terms.size() + 1) * 4, dev->stream_up));
-                                } else if (!same)
-                                        HIP_TRY(hipMemsetAsync(ix->d_term_row, 0xff, (ix->terms.size() + 1) * 4, dev->stream_up));
-                                if (ix->d_prank) // (retired with the rows: same readers, and the copies above read them)
-                                        for (void *old : {(void *)ix->d_prank, (void *)ix->d_phs, (void *)ix->d_hs_off, (void *)ix->d_ph_pairs})
-                                                outgrown.push_back(old);
-                                ix->d_prank = prank, ix->d_phs = phs, ix->d_hs_off = hso, ix->d_ph_pairs = pairs;
-                                ix->rank_term = rt;
-                                ix->ph_built.resize(cap, 0);
-                        }
-                        HIP_TRY(hipEventRecord(ix->ev_pc_ready, dev->stream_up));
-                        // The outgrown buffers are retired on events recorded on the UPLOAD stream, behind the copies that read them: that point is past
-                        // the engine stream's earlier readers too (stream_up waited for `drained`).  (Round 5 retired them on events of the engine
-                        // stream recorded BEFORE the copies were enqueued: the next tri_batch_create could pool a buffer the copy had not read yet.)
-                        if (fresh && ix->d_pcache)
-                                outgrown.push_back(ix->d_pcache);
-                        if (fresh_hi && ix->d_pcache_hi)
-                                outgrown.push_back(ix->d_pcache_hi);
-                        for (void *old : outgrown) {
-                                hipEvent_t e2 = nullptr;
-                                HIP_TRY(event_get(dev, &e2));
-                                HIP_TRY(hipEventRecord(e2, dev->stream_up));
-                                ix->pc_retired.emplace_back(old, e2);
-                        }
-                        event_put(dev, drained);
-                        if (fresh)
-                                ix->d_pcache = fresh;
-                        if (fresh_hi)
-                                ix->d_pcache_hi = fresh_hi;
-                        ix->pc_cap = cap;
-                        ix->pc_plw = b->plw;
-                        ix->pc_built.resize(cap, 0);
-                }
-        }
+        if (!b->plane_terms.empty() || planes_tasks)
+                if (const int rc = fit_plane_cache(b.get(), planes_tasks))
+                        return rc;
         if (planes_tasks) {
                 const uint64_t wgs = std::min<uint64_t>(std::max(b->n_planes, b->n_planes8), (uint64_t)dev->cus * PLK_WGS_PER_CU);
                 HIP_TRY(pool_alloc(dev, (void **)&b->d_sparse, (2 * wgs * b->sparse_cap + 64) * 4)); // (per workgroup: the lists' entries, then their frequencies)
@@ -1062,7 +1107,7 @@ extern "C" int tri_batch_create(tri_index *ix, const uint32_t *prog, size_t prog
                 if (scored && topk)
                         HIP_TRY(pool_alloc(dev, (void **)&b->d_tree_scores, (off + 64) * 8));
         }
-        HIP_TRY(hipEventRecord(b->ev_up, dev->stream_up));
+        HIP_TRY(hipEventRecord(b->ev[EV_UP], dev->stream_up));
         b->info.nqueries = nq;
         b->info.tree_queries = b->tree_queries;
         b->info.bitmap_queries = b->bitmap_queries;
@@ -1075,9 +1120,9 @@ extern "C" int tri_batch_create(tri_index *ix, const uint32_t *prog, size_t prog
         b->info.unsupported_queries = b->unsupported_queries;
         b->info.plane_terms = b->plane_terms.size();
         b->info.plane_bytes = (uint64_t)b->plane_terms.size() * (b->planes_hi ? PL_PLANES : 1u) * b->plw * 4; // (what this batch reads of its rows of the index's plane cache: plane 0, a scored batch the high parts too)
-        b->info.launches = (b->n_dense != 0) + (b->n_pset != 0) + (b->n_probe != 0) + (b->n_cand != 0) + (b->n_fused != 0) + (b->n_fused16 != 0) + (b->n_fusedgen != 0) + (b->n_planes != 0) + (b->n_planes8 != 0) + (!b->plane_terms.empty()) +
-                           (!b->ptasks.empty()) + (rich ? 2 : 0) +
-                           ((scored && b->n_dense + b->n_pset + b->n_probe + b->n_cand) ? 1 : 0) + ((scored && topk) ? 1 : 0);
+        b->info.launches = (!b->plane_terms.empty()) + (!b->ptasks.empty()) + (rich ? 2 : 0) + ((scored && trip::sched_first(*b, TASK_FUSED)) ? 1 : 0) + ((scored && topk) ? 1 : 0);
+        for (uint32_t kind = 0; kind < TASK_KINDS; ++kind) // (a launch per schedule section; the tree kernels are not counted)
+                b->info.launches += kind != TASK_TREE && b.get()->*trip::SCHED_COUNT[kind];
         b->info.create_plan_ms = (float)(b->plan_ms[0] + b->plan_ms[1] + b->plan_ms[2] + b->plan_ms[3]);
         b->info.create_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count();
         if (dbg_create)
@@ -1087,9 +1132,346 @@ extern "C" int tri_batch_create(tri_index *ix, const uint32_t *prog, size_t prog
         return TRI_OK;
 }
 
-
 extern "C" void tri_batch_destroy(tri_batch *b) {
         delete b; // ~tri_batch releases the device buffers
+}
+
+// ---- tri_batch_run's stages, in launch order: each ends with the event that closes its time (EV_PLANE_ROWS .. EV_TREE)
+
+// the head terms the batch's queries share: the rows of the index's plane cache that no earlier run has built are decoded now — once for the
+// index, not once per batch (every word of a row is written: no memset)
+static int run_plane_rows(tri_batch *b) {
+        tri_dev *dev = b->dev;
+        tri_index *ix = b->ix;
+        b->info.term_planes_decoded_bytes = 0;
+        if (!b->plane_terms.empty()) {
+                std::vector<uint32_t> build;
+                const uint8_t needs = b->planes_hi ? 3u : 1u; // (bit 0: plane 0; bit 1: the row's high part — scored batches only)
+                for (const uint32_t term : b->plane_terms) {
+                        const uint32_t row = ix->df_rank[term];
+                        if (row < ix->pc_cap && ((ix->pc_built[row] & needs) != needs || dev->opt.planes_rebuild)) {
+                                build.push_back(term);
+                                build.push_back(row);
+                                b->info.term_planes_decoded_bytes += ix->docbytes[term];
+                        }
+                }
+                if (!build.empty()) {
+                        HIP_TRY(hipMemcpyAsync(b->d_build, build.data(), build.size() * 4, hipMemcpyHostToDevice, dev->stream)); // (pageable source: staged before the call returns)
+                        const uint32_t nrows = (uint32_t)(build.size() / 2), nwin = b->plw / PL_WORDS;
+                        for (uint32_t y0 = 0; y0 < nrows; y0 += 65535u) { // (gridDim.y <= 65535)
+                                const uint32_t ny = std::min(65535u, nrows - y0);
+                                if (b->planes_hi) // (a row that gains its high part is decoded whole again: plane 0 is rewritten with the words it holds)
+                                        TRI_LAUNCH(k_term_planes, ix->codec, dim3(nwin, ny), dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
+                                                   ix->d_blk_doff, ix->d_win, ix->d_terms, (const uint32_t *)b->d_build + 2 * (size_t)y0, ix->d_pcache, (size_t)b->plw, ix->d_pcache_hi,
+                                                   (size_t)PL_HI * b->plw, b->plw, (uint32_t *)nullptr);
+                                else // plane 0 alone, P0_GROUP windows to a workgroup (the rank records: built when a phrase batch asks for them, run_phrases)
+                                        TRI_LAUNCH(k_term_plane0, ix->codec, dim3((nwin + P0_GROUP - 1) / P0_GROUP, ny), dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off,
+                                                   ix->d_blk_rec, ix->d_blk_doff, ix->d_win, ix->d_terms, (const uint32_t *)b->d_build + 2 * (size_t)y0, ix->d_pcache, b->plw, (uint32_t *)nullptr);
+                                HIP_TRY(hipGetLastError());
+                        }
+                        for (size_t i = 1; i < build.size(); i += 2)
+                                ix->pc_built[build[i]] |= needs;
+                }
+        }
+        HIP_TRY(hipEventRecord(b->ev[EV_PLANE_ROWS], dev->stream));
+        return TRI_OK;
+}
+
+// the docset-materialising kernels: the window kernels (k_and_dense, k_psets, k_probe), then the candidate tiles (k_and) — persistent kernels back
+// to back on the engine stream, or k_and on the second stream beside the others (options overlap, overlap_dense_wgs / overlap_cand_wgs)
+static int run_matching(tri_batch *b) {
+        tri_dev *dev = b->dev;
+        tri_index *ix = b->ix;
+        // GOOGLE: matching reads the contiguous delta streams, not the chunks (see tri_index::d_dstream)
+        const uint8_t *match_bytes = ix->codec == TRI_CODEC_GOOGLE ? ix->d_dstream : ix->d_index;
+        const uint32_t *match_off = ix->codec == TRI_CODEC_GOOGLE ? ix->d_blk_doff : ix->d_blk_off;
+        uint32_t dense_wgs = TRI_DENSE_WAVES * 256 / DENSE_WG, cand_wgs = 4; // workgroups per CU
+        bool overlap = false;
+        if (dev->opt.overlap_dense_wgs && dev->opt.overlap_cand_wgs && (b->n_dense || b->n_pset) && b->n_cand) { // the window kernels and the candidate-tile kernel side by side
+                overlap = true;
+                dense_wgs = (uint32_t)dev->opt.overlap_dense_wgs;
+                cand_wgs = (uint32_t)dev->opt.overlap_cand_wgs;
+        } else if (dev->opt.overlap && b->n_cand && trip::sched_first(*b, TASK_CAND)) // (any window kernel's tasks)
+                overlap = true; // (full grids: the second kernel's workgroups take the slots the first one's tail leaves)
+        hipStream_t cand_stream = dev->stream;
+        if (overlap) {
+                HIP_TRY(hipEventRecord(dev->ev_fork, dev->stream));
+                HIP_TRY(hipStreamWaitEvent(dev->stream2, dev->ev_fork, 0));
+                cand_stream = dev->stream2;
+        }
+        const DevPsetUnit *units = (const DevPsetUnit *)(b->d_arena + b->off_units);
+        const uint32_t *pset_sched = (const uint32_t *)(b->d_arena + b->off_pset_sched);
+        // unions with terms that have no plane (PSET_UNIT_SCATTER): those terms' documents listed task by task, a workgroup per query (units[] holds the TASK_PROBE units
+        // too) — on the second stream, beside k_and_dense, where that stream is not k_and's (option overlap)
+        const bool prep = b->n_pset && b->pscatter_queries, prep_forked = prep && !overlap && b->n_dense;
+        if (prep) {
+                if (prep_forked) {
+                        HIP_TRY(hipEventRecord(dev->ev_fork, dev->stream));
+                        HIP_TRY(hipStreamWaitEvent(dev->stream2, dev->ev_fork, 0));
+                }
+                hipStream_t prep_stream = prep_forked ? dev->stream2 : dev->stream;
+                const uint32_t nunits = b->n_pset + b->n_probe, nscat = (uint32_t)b->pscatter_queries;
+                hipLaunchKernelGGL(k_psets_prep_list, dim3((nunits + 255) / 256), dim3(256), 0, prep_stream, units, nunits, b->d_ticket + TICKET_SCAT_WORD + 1, b->d_scat_list, nscat);
+                HIP_TRY(hipGetLastError());
+                TRI_LAUNCH(k_psets_prep, ix->codec, dim3(nscat), dim3(PSCAT_WG), prep_stream, units, (const uint32_t *)b->d_scat_list, (const uint32_t *)(b->d_ticket + TICKET_SCAT_WORD + 1),
+                           b->d_plan, b->d_tasks, (const uint32_t *)b->d_qterms, (const uint32_t *)b->d_qplane, ix->d_masked, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
+                           ix->d_blk_doff, ix->d_terms, b->d_ticket + TICKET_SCAT_WORD, b->d_scat_off, b->d_scat_cnt, b->d_scat_docs, b->scat_cap);
+                HIP_TRY(hipGetLastError());
+                if (prep_forked)
+                        HIP_TRY(hipEventRecord(dev->ev_join, dev->stream2));
+        }
+        if (b->n_dense) {
+                TRI_LAUNCH(k_and_dense, ix->codec, dim3(std::min<uint32_t>(b->n_dense, (uint32_t)dev->cus * dense_wgs)), dim3(DENSE_WG), dev->stream, match_bytes, ix->d_blk_last,
+                           match_off, ix->d_win, ix->d_terms, b->d_plan, b->d_tasks, b->d_sched + trip::sched_first(*b, TASK_DENSE), b->d_qterms, b->n_dense,
+                           b->d_ticket + TICKET_DENSE_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->d_qplane, (const uint32_t *)ix->d_pcache, b->plw);
+                HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(b->ev[EV_DENSE], dev->stream));
+        if (prep_forked) // (k_psets reads the lists k_psets_prep made beside k_and_dense)
+                HIP_TRY(hipStreamWaitEvent(dev->stream, dev->ev_join, 0));
+        if (b->n_pset) {
+                // the queries all of whose terms have planes: word-wise algebra over the planes + expansion (k_psets.hpp)
+                const uint32_t pset_wgs = TRI_PSET_WAVES * 256 / PSET_WG;
+                TRI_LAUNCH(k_psets, ix->codec, dim3(std::min<uint32_t>(b->n_pset, (uint32_t)dev->cus * (overlap && dev->opt.overlap_dense_wgs ? std::min<uint32_t>(dense_wgs, pset_wgs) : pset_wgs))),
+                           dim3(PSET_WG), dev->stream, units, pset_sched, b->n_pset, b->d_ticket + TICKET_PSET_WORD, (const uint32_t *)b->d_qterms, (const uint32_t *)b->d_qplane, b->d_out,
+                           b->d_counts, ix->d_masked, (const uint32_t *)ix->d_pcache, b->plw, (const uint32_t *)b->d_scat_off, (const uint32_t *)b->d_scat_cnt,
+                           (const uint32_t *)b->d_scat_docs);
+                HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(b->ev[EV_PSET], dev->stream));
+        if (b->n_probe) {
+                // one short lead list against lists that all have planes: a wave per task, the lead's documents probed from registers (k_probe.hpp);
+                // its units run behind k_psets' in pset_sched[]
+                TRI_LAUNCH(k_probe, ix->codec, dim3(std::min<uint32_t>((b->n_probe + PROBE_WG / 64 - 1) / (PROBE_WG / 64), (uint32_t)dev->cus * (TRI_PROBE_WAVES * 256 / PROBE_WG))),
+                           dim3(PROBE_WG), dev->stream, match_bytes, ix->d_blk_last, match_off, ix->d_terms, units, pset_sched + b->n_pset, b->n_probe, b->d_ticket + TICKET_PROBE_WORD,
+                           (const uint32_t *)b->d_qterms, (const uint32_t *)b->d_qplane, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)ix->d_pcache, b->plw);
+                HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(b->ev[EV_PROBE], dev->stream));
+        if (b->n_cand)
+                TRI_LAUNCH(k_and, ix->codec, dim3(std::min<uint32_t>(b->n_cand, (uint32_t)dev->cus * cand_wgs)), dim3(AND_WG), cand_stream, match_bytes, ix->d_blk_last, match_off,
+                           ix->d_win, ix->d_terms, b->d_plan, b->d_tasks, b->d_sched + trip::sched_first(*b, TASK_CAND), b->d_qterms, (const uint32_t *)(b->d_arena + b->off_cand_q),
+                           b->d_ticket + TICKET_CAND_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->d_qplane, (const uint32_t *)ix->d_pcache, b->plw);
+        HIP_TRY(hipGetLastError());
+        if (overlap) {
+                HIP_TRY(hipEventRecord(dev->ev_join, dev->stream2));
+                HIP_TRY(hipStreamWaitEvent(dev->stream, dev->ev_join, 0));
+        }
+        HIP_TRY(hipEventRecord(b->ev[EV_CAND], dev->stream));
+        return TRI_OK;
+}
+
+// AccumulatedScore top-K of the dense queries: decode -> match -> score -> select in one pass; as many workgroups per CU as its LDS holds.
+// Three instantiations: 32-bit window words, 16-bit ones (queries of <= 5 distinct terms: windows twice as long), general trees (32-bit words)
+static int run_fused(tri_batch *b) {
+        tri_dev *dev = b->dev;
+        tri_index *ix = b->ix;
+        for (uint32_t kind = TASK_FUSED; kind <= TASK_FUSED_GEN; ++kind) {
+                const uint32_t nf = b->*trip::SCHED_COUNT[kind], variant = kind - TASK_FUSED;
+                if (!nf)
+                        continue;
+                tri_launch(ix->codec, [&](auto c) { return std::array{k_fused<c.value, 0, 0>, k_fused<c.value, 1, 0>, k_fused<c.value, 0, 1>}[variant]; },
+                           dim3(std::min<uint32_t>(nf, (uint32_t)dev->cus * FUS_WGS_PER_CU)), dim3(FUS_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
+                           ix->d_blk_doff, ix->d_win, ix->d_terms, b->d_plan, b->d_fused, b->d_tasks, (const uint32_t *)b->d_sched + trip::sched_first(*b, kind), b->d_sterms,
+                           b->d_sweights, nf, b->d_ticket + TICKET_FUSED_WORD + 2 * variant, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, ix->d_masked,
+                           b->similarity, b->d_out, b->d_all_scores, b->d_rich_allow);
+                HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(b->ev[EV_FUSED], dev->stream));
+        return TRI_OK;
+}
+
+// AccumulatedScore top-K of the CNF queries over bit planes: the head terms' planes from k_term_planes, the other lists decoded per window into
+// LDS planes; union / conjunction predicates and the candidate filter 32 documents per word (two instantiations: queries of up to five slots,
+// wider ones)
+static int run_planes(tri_batch *b) {
+        tri_dev *dev = b->dev;
+        tri_index *ix = b->ix;
+        if (b->d_qthr)
+                HIP_TRY(hipMemsetAsync(b->d_qthr, 0, (b->plan.size() + 1) * 8, dev->stream));
+        for (uint32_t kind = TASK_PLANES; kind <= TASK_PLANES8; ++kind) {
+                const uint32_t np = b->*trip::SCHED_COUNT[kind], wide = kind - TASK_PLANES;
+                if (!np)
+                        continue;
+                tri_launch(ix->codec, [&](auto c) { return wide ? k_planes<c.value, FUS_MAX_SLOTS> : k_planes<c.value, PLK_NS_SMALL>; },
+                           dim3(std::min<uint32_t>(np, (uint32_t)dev->cus * PLK_WGS_PER_CU)), dim3(PLK_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
+                           ix->d_blk_doff, ix->d_win, ix->d_terms, b->d_plan, b->d_fused, b->d_tasks, (const uint32_t *)b->d_sched + trip::sched_first(*b, kind), b->d_sterms,
+                           b->d_sweights, np, b->d_ticket + TICKET_PLANES_WORD + 2 * wide, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, ix->d_masked,
+                           b->similarity, (const uint32_t *)ix->d_pcache, (const uint32_t *)ix->d_pcache_hi, b->plw, ix->pc_cap, b->d_sparse, b->sparse_cap, b->d_qthr);
+                HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(b->ev[EV_PLANES], dev->stream));
+        return TRI_OK;
+}
+
+// positional constraints: filter + compact the match segments of the queries that hold phrases
+static int run_phrases(tri_batch *b) {
+        tri_dev *dev = b->dev;
+        tri_index *ix = b->ix;
+        if (!b->ptasks.empty() && ix->codec == TRI_CODEC_GOOGLE && ix->d_prank && ix->pc_cap) {
+                // the phrases' head terms are located by RANK in plane 0 (k_phrase.hpp): rows (plane 0 + rank directory) and per-posting hits entries of the
+                // phrase terms that have none yet are built now — once for the index
+                std::vector<uint32_t> hits_build, hits_only; // (term, row) pairs: the rows that also need their rank records FIRST, then the ones that have them
+                uint32_t max_blocks = 0;
+                for (size_t i = 0; i < b->pterms.size(); ++i) {
+                        const uint32_t term = b->pterms[i], r = ix->df_rank[term];
+                        if (r >= ix->pc_cap || ix->ph_built[r])
+                                continue;
+                        const DevTerm &t = ix->terms[term];
+                        if (!(t.flags & TERM_FULL_BLOCKS) || !t.documents)
+                                continue;
+                        ix->ph_built[r] = 1;
+                        max_blocks = std::max(max_blocks, t.nblocks);
+                        std::vector<uint32_t> &dst = (ix->pc_built[r] & 4u) ? hits_only : hits_build; // (bit 2: the row's rank records — with them plane 0, if it is not there yet)
+                        ix->pc_built[r] |= 5u;
+                        dst.push_back(term);
+                        dst.push_back(r);
+                }
+                const uint32_t nrows_build = (uint32_t)(hits_build.size() / 2);
+                hits_build.insert(hits_build.end(), hits_only.begin(), hits_only.end());
+                if (!hits_build.empty()) {
+                        uint32_t *d_pairs = ix->d_ph_pairs + 2 * ix->ph_pairs_n; // (every row is built once: the pairs of all runs fit 2 * pc_cap words)
+                        HIP_TRY(hipMemcpyAsync(d_pairs, hits_build.data(), hits_build.size() * 4, hipMemcpyHostToDevice, dev->stream)); // (pageable source: staged before the call returns)
+                        ix->ph_pairs_n += hits_build.size() / 2;
+                        // the rows without rank records: plane 0 + records in ONE launch over the list's head (round 5 launched a grid per row: 711 launches, 11 ms, the
+                        // first time cfg4's phrases met an index)
+                        for (uint32_t y0 = 0; y0 < nrows_build; y0 += 65535u) {
+                                const dim3 grid((b->plw / PL_WORDS + P0_GROUP - 1) / P0_GROUP, std::min(65535u, nrows_build - y0));
+                                TRI_LAUNCH(k_term_plane0, ix->codec, grid, dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec, ix->d_blk_doff, ix->d_win,
+                                           ix->d_terms, (const uint32_t *)d_pairs + 2 * (size_t)y0, ix->d_pcache, b->plw, ix->d_prank);
+                                HIP_TRY(hipGetLastError());
+                        }
+                        const uint32_t npairs = (uint32_t)(hits_build.size() / 2);
+                        for (uint32_t y0 = 0; y0 < npairs; y0 += 65535u) { // (gridDim.y <= 65535: a small index at a high plane_div makes almost every term eligible)
+                                hipLaunchKernelGGL(k_term_hits, dim3((max_blocks + 255) / 256, std::min(65535u, npairs - y0)), dim3(256), 0, dev->stream, ix->d_index, ix->d_blk_off,
+                                                   ix->d_blk_hits, ix->d_terms, (const uint32_t *)d_pairs + 2 * (size_t)y0, (const uint64_t *)ix->d_hs_off, ix->d_phs, ix->d_term_row);
+                                HIP_TRY(hipGetLastError());
+                        }
+                }
+        }
+        if (!b->ptasks.empty()) {
+                const uint32_t np = (uint32_t)b->ptasks.size();
+                TRI_LAUNCH(k_phrase, ix->codec, dim3(std::min<uint32_t>(np, (uint32_t)dev->cus * PHRASE_WGS_PER_CU)), dim3(AND_WG), dev->stream, ix->d_index, ix->d_hits,
+                           ix->d_blk_hits, ix->d_hdir, ix->d_blk_last, ix->d_blk_off, ix->d_win, ix->d_terms, b->d_plan, b->d_tasks, b->d_ptasks, np, b->d_phrases, b->d_pterms,
+                           b->d_ticket + TICKET_PHRASE_WORD, b->d_out, b->d_counts, b->d_pscore,
+                           (b->flags & TRI_FLAG_ACCUMULATED_SCORE) ? 65535u : 1u, // exec.cpp:296 trackCnt
+                           b->similarity, (const uint32_t *)ix->d_pcache, ix->pc_plw, (const uint32_t *)ix->d_prank, (const unsigned long long *)ix->d_phs,
+                           (const uint64_t *)ix->d_hs_off, (const uint32_t *)(ix->codec == TRI_CODEC_GOOGLE ? ix->d_term_row : nullptr));
+                HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(b->ev[EV_PHRASE], dev->stream));
+        return TRI_OK;
+}
+
+// the queries no other kernel takes (k_tree.hpp): leaf bitmaps — the distinct term leaves decoded once, the phrase leaves from their hidden
+// queries' match lists (k_phrase has just filtered them) —, the trees word by word, the match bitmaps expanded
+static int run_trees(tri_batch *b) {
+        tri_dev *dev = b->dev;
+        tri_index *ix = b->ix;
+        if (b->n_tree) {
+                const uint32_t plw = b->plw, nterms = (uint32_t)b->tree_terms.size(), nhid = (uint32_t)b->tree_hidden.size();
+                const uint32_t nchunks = (plw + TREE_CHUNK_WORDS - 1) / TREE_CHUNK_WORDS;
+                const uint32_t *tsched = b->d_sched + trip::sched_first(*b, TASK_TREE);
+                const uint32_t *d_tree = (const uint32_t *)(b->d_arena + b->off_tree);
+                for (uint32_t y0 = 0; y0 < nterms; y0 += 65535u) { // (gridDim.y <= 65535)
+                        const dim3 grid(plw / PL_WORDS, std::min(65535u, nterms - y0));
+                        TRI_LAUNCH(k_term_planes, ix->codec, grid, dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec, ix->d_blk_doff, ix->d_win,
+                                   ix->d_terms, (const uint32_t *)b->d_tree_build + 2 * (size_t)y0, b->d_tree_rows, (size_t)PL_PLANES * plw, b->d_tree_rows + plw,
+                                   (size_t)PL_PLANES * plw, plw, (uint32_t *)nullptr); // (a tree row keeps its two parts side by side: plane k at k * plw)
+                        HIP_TRY(hipGetLastError());
+                }
+                if (nhid) {
+                        HIP_TRY(hipMemsetAsync(b->d_tree_prows, 0, (size_t)nhid * plw * 4, dev->stream));
+                        hipLaunchKernelGGL(k_tree_gather, dim3(nhid), dim3(TREE_WG), 0, dev->stream, b->d_plan, b->d_tasks, (const uint32_t *)(b->d_arena + b->off_tree_hidden), b->d_out,
+                                           b->d_counts, b->d_pscore, b->d_tree_prows, plw);
+                        HIP_TRY(hipGetLastError());
+                }
+                const bool scored_run = b->flags & TRI_FLAG_ACCUMULATED_SCORE, rich_run = b->flags & TRI_FLAG_MATCHED_TERMS;
+                double *tscores = scored_run ? (b->topk ? b->d_tree_scores : b->d_all_scores) : nullptr;
+                for (uint32_t y0 = 0; y0 < b->n_tree; y0 += 65535u) {
+                        const dim3 grid(nchunks, std::min(65535u, b->n_tree - y0));
+                        uint32_t *qbits = b->d_tree_qbits + (size_t)y0 * plw, *cc = b->d_tree_cc + (size_t)y0 * nchunks;
+                        hipLaunchKernelGGL(k_tree_eval, grid, dim3(TREE_WG), 0, dev->stream, b->d_plan, b->d_tasks, tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows,
+                                           (const uint32_t *)b->d_tree_prows, (const uint32_t *)ix->d_masked, qbits, cc, plw);
+                        hipLaunchKernelGGL(k_tree_expand, grid, dim3(TREE_WG), 0, dev->stream, b->d_plan, b->d_tasks, tsched + y0, (const uint32_t *)qbits, (const uint32_t *)cc,
+                                           b->d_out, b->d_counts, plw);
+                        if (scored_run || rich_run)
+                                TRI_LAUNCH(k_tree_leaves, ix->codec, grid, dim3(TREE_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->d_plan, b->d_tasks,
+                                           tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows, (const uint32_t *)b->d_tree_prows, (const uint32_t *)cc, (const uint32_t *)b->d_out,
+                                           (const uint32_t *)b->d_counts, (const double *)b->d_sweights, (const double *)b->d_pscore, tscores, rich_run ? b->d_rich_allow : nullptr,
+                                           plw, b->similarity);
+                        HIP_TRY(hipGetLastError());
+                }
+                if (scored_run && b->topk) {
+                        hipLaunchKernelGGL(k_tree_topk, dim3(b->n_tree), dim3(AND_WG), 0, dev->stream, tsched, b->d_tasks, (const uint32_t *)b->d_out, (const uint32_t *)b->d_counts,
+                                           (const double *)tscores, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts);
+                        HIP_TRY(hipGetLastError());
+                }
+        }
+        HIP_TRY(hipEventRecord(b->ev[EV_TREE], dev->stream));
+        return TRI_OK;
+}
+
+// TRI_FLAG_MATCHED_TERMS, over every task: the COUNT pass (which reportable terms hold each match, with what frequency; hit totals per task) or
+// the WRITE pass (the positions, into the pool at the offsets tri_batch_sync made of the totals)
+template <bool WRITE>
+static int launch_rich(tri_batch *b) {
+        tri_dev *dev = b->dev;
+        tri_index *ix = b->ix;
+        const uint32_t n = (uint32_t)b->tasks.size();
+        tri_launch(ix->codec, [](auto c) { return k_rich<c.value, WRITE>; }, dim3(std::min<uint32_t>(n, (uint32_t)dev->cus * 3)), dim3(AND_WG), dev->stream, ix->d_index,
+                   ix->d_hits, ix->d_blk_hits, ix->d_hdir, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->d_plan, b->d_tasks, b->d_sched, b->d_sterms, n,
+                   b->d_ticket + (WRITE ? TICKET_RICH_WRITE_WORD : TICKET_RICH_COUNT_WORD), b->d_out, b->d_counts, b->rich_R, b->d_rich_present, b->d_rich_freq, b->d_task_hits,
+                   WRITE ? (const uint64_t *)b->d_task_pos_base : nullptr, WRITE ? b->d_rich_pool : nullptr, (const uint32_t *)b->d_rich_allow, WRITE ? b->d_rich_plen : nullptr,
+                   WRITE ? b->d_rich_payload : nullptr);
+        HIP_TRY(hipGetLastError());
+        return TRI_OK;
+}
+
+static int run_rich_count(tri_batch *b) {
+        if (!(b->flags & TRI_FLAG_MATCHED_TERMS))
+                return TRI_OK;
+        tri_dev *dev = b->dev;
+        HIP_TRY(hipMemsetAsync(b->d_rich_present, 0, (b->out_capacity + 64) * 4, dev->stream));
+        HIP_TRY(hipMemsetAsync(b->d_rich_freq, 0, (b->out_capacity + 64) * 2 * b->rich_R, dev->stream));
+        HIP_TRY(hipMemsetAsync(b->d_task_hits, 0, (b->tasks.size() + 1) * 4, dev->stream));
+        return launch_rich<false>(b);
+}
+
+// AccumulatedScore: the sets k_and_dense / k_psets / k_probe / k_and materialised — the schedule's sections before the one-pass kinds', which
+// have scored themselves — scored heaviest first; then the queries' top-K merged from their tasks'
+static int run_scores(tri_batch *b) {
+        if (!(b->flags & TRI_FLAG_ACCUMULATED_SCORE))
+                return TRI_OK;
+        tri_dev *dev = b->dev;
+        tri_index *ix = b->ix;
+        const uint32_t nlegacy = trip::sched_first(*b, TASK_FUSED);
+        if (nlegacy) {
+                hipLaunchKernelGGL(k_score_order, dim3(1), dim3(SORD_WG), 0, dev->stream, (const uint32_t *)b->d_sched, (const uint32_t *)b->d_counts, nlegacy, b->d_score_order);
+                HIP_TRY(hipGetLastError());
+                TRI_LAUNCH(k_score, ix->codec, dim3(std::min<uint32_t>(nlegacy, (uint32_t)dev->cus * SCORE_WGS_PER_CU)), dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last,
+                           ix->d_blk_off, ix->d_terms, b->d_plan, b->d_tasks, (const uint32_t *)b->d_score_order, b->d_sterms, b->d_sweights, nlegacy,
+                           b->d_ticket + TICKET_SCORE_WORD, b->d_out, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, b->d_all_scores, b->d_pscore,
+                           b->similarity, ix->d_win, b->splane.empty() ? (const uint32_t *)nullptr : (const uint32_t *)(b->d_arena + b->off_splane),
+                           (const uint32_t *)ix->d_pcache_hi, b->plw); // (the scorers read the level words: the rows' high parts)
+        }
+        HIP_TRY(hipGetLastError());
+        const uint32_t nqs = (uint32_t)b->plan.size();
+        if (b->topk)
+                hipLaunchKernelGGL(k_topk_merge, dim3(std::min<uint32_t>(nqs, (uint32_t)dev->cus * 8)), dim3(AND_WG), 0, dev->stream, b->d_plan, nqs, b->topk, b->d_part_docs,
+                                   b->d_part_scores, b->d_part_counts, b->d_top_docs, b->d_top_scores, b->d_top_counts);
+        HIP_TRY(hipGetLastError());
+        return TRI_OK;
+}
+
+// per caller query: the matches of its tasks
+static int run_query_counts(tri_batch *b) {
+        if (!b->plan.empty()) {
+                const uint32_t nqs = (uint32_t)b->plan.size();
+                hipLaunchKernelGGL(k_query_counts, dim3((nqs + 255) / 256), dim3(256), 0, b->dev->stream, b->d_plan, b->d_counts, nqs, b->d_qcounts);
+                HIP_TRY(hipGetLastError());
+        }
+        return TRI_OK;
 }
 
 extern "C" int tri_batch_run(tri_batch *b) {
@@ -1099,7 +1481,6 @@ extern "C" int tri_batch_run(tri_batch *b) {
         DevLock dev_lock(dev->mu);
         HIP_TRY(hipSetDevice(dev->device));
         b->synced = false;
-        const uint32_t n = (uint32_t)b->tasks.size();
 #ifdef TRI_TRACE
         if (!g_trace_host) {
                 HIP_TRY(hipHostMalloc((void **)&g_trace_host, 64 * 16, hipHostMallocMapped | hipHostMallocCoherent));
@@ -1124,333 +1505,300 @@ extern "C" int tri_batch_run(tri_batch *b) {
                 memset(g_tt_host, 0, g_tt_cap * 8);
         }
 #endif
-        HIP_TRY(hipStreamWaitEvent(dev->stream, b->ev_up, 0)); // the plan's copy (upload stream) has arrived
+        HIP_TRY(hipStreamWaitEvent(dev->stream, b->ev[EV_UP], 0)); // the plan's copy (upload stream) has arrived
         if (b->ix->ev_pc_ready)
                 HIP_TRY(hipStreamWaitEvent(dev->stream, b->ix->ev_pc_ready, 0)); // ... and so have the plane cache's rows, should it have been grown since
-        HIP_TRY(hipEventRecord(b->ev0, dev->stream));
-        if (n) {
-                HIP_TRY(hipMemsetAsync(b->d_ticket, 0, TICKET_BYTES, dev->stream));
-                // two persistent kernels back to back on the engine stream: bitmap windows (512 threads), then candidate tiles.
-                // GOOGLE: matching reads the contiguous delta streams, not the chunks (see tri_index::d_dstream)
-                const uint8_t *match_bytes = b->ix->codec == TRI_CODEC_GOOGLE ? b->ix->d_dstream : b->ix->d_index;
-                const uint32_t *match_off = b->ix->codec == TRI_CODEC_GOOGLE ? b->ix->d_blk_doff : b->ix->d_blk_off;
-                uint32_t dense_wgs = TRI_DENSE_WAVES * 256 / DENSE_WG, cand_wgs = 4; // workgroups per CU
-                bool overlap = false;
-                if (dev->opt.overlap_dense_wgs && dev->opt.overlap_cand_wgs && (b->n_dense || b->n_pset) && b->n_cand) { // the window kernels and the candidate-tile kernel side by side
-                        overlap = true;
-                        dense_wgs = (uint32_t)dev->opt.overlap_dense_wgs;
-                        cand_wgs = (uint32_t)dev->opt.overlap_cand_wgs;
-                } else if (dev->opt.overlap && b->n_cand && b->n_dense + b->n_pset + b->n_probe)
-                        overlap = true; // (full grids: the second kernel's workgroups take the slots the first one's tail leaves)
-                b->info.term_planes_decoded_bytes = 0;
-                if (!b->plane_terms.empty()) {
-                        // the head terms the batch's queries share: the rows of the index's plane cache that no earlier run has built are decoded now
-                        // — once for the index, not once per batch (every word of a row is written: no memset)
-                        tri_index *ix = b->ix;
-                        std::vector<uint32_t> build;
-                        const uint8_t needs = b->planes_hi ? 3u : 1u; // (bit 0: plane 0; bit 1: the row's high part — scored batches only)
-                        for (const uint32_t term : b->plane_terms) {
-                                const uint32_t row = ix->df_rank[term];
-                                if (row < ix->pc_cap && ((ix->pc_built[row] & needs) != needs || dev->opt.planes_rebuild)) {
-                                        build.push_back(term);
-                                        build.push_back(row);
-                                        b->info.term_planes_decoded_bytes += ix->docbytes[term];
-                                }
-                        }
-                        if (!build.empty()) {
-                                HIP_TRY(hipMemcpyAsync(b->d_build, build.data(), build.size() * 4, hipMemcpyHostToDevice, dev->stream)); // (pageable source: staged before the call returns)
-                                const uint32_t nrows = (uint32_t)(build.size() / 2), nwin = b->plw / PL_WORDS;
-                                for (uint32_t y0 = 0; y0 < nrows; y0 += 65535u) { // (gridDim.y <= 65535)
-                                        const uint32_t ny = std::min(65535u, nrows - y0);
-                                        if (b->planes_hi) // (a row that gains its high part is decoded whole again: plane 0 is rewritten with the words it holds)
-                                                TRI_LAUNCH(k_term_planes, ix->codec, dim3(nwin, ny), dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
-                                                           ix->d_blk_doff, ix->d_win, ix->d_terms, (const uint32_t *)b->d_build + 2 * (size_t)y0, ix->d_pcache, (size_t)b->plw, ix->d_pcache_hi,
-                                                           (size_t)PL_HI * b->plw, b->plw, (uint32_t *)nullptr);
-                                        else // plane 0 alone, P0_GROUP windows to a workgroup (the rank records: built when a phrase batch asks for them, below)
-                                                TRI_LAUNCH(k_term_plane0, ix->codec, dim3((nwin + P0_GROUP - 1) / P0_GROUP, ny), dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off,
-                                                           ix->d_blk_rec, ix->d_blk_doff, ix->d_win, ix->d_terms, (const uint32_t *)b->d_build + 2 * (size_t)y0, ix->d_pcache, b->plw, (uint32_t *)nullptr);
-                                        HIP_TRY(hipGetLastError());
-                                }
-                                for (size_t i = 1; i < build.size(); i += 2)
-                                        ix->pc_built[build[i]] |= needs;
-                        }
+        HIP_TRY(hipEventRecord(b->ev[EV_START], dev->stream));
+        if (b->tasks.empty()) {
+                for (int e = EV_PLANE_ROWS; e <= EV_TREE; ++e)
+                        HIP_TRY(hipEventRecord(b->ev[e], dev->stream));
+        } else {
+                HIP_TRY(hipMemsetAsync(b->d_ticket, 0, TICKET_BYTES, dev->stream)); // (timed with the plane rows)
+                for (int (*stage)(tri_batch *) : {run_plane_rows, run_matching, run_fused, run_planes, run_phrases, run_trees, run_rich_count, run_scores})
+                        if (const int rc = stage(b))
+                                return rc;
+        }
+        if (const int rc = run_query_counts(b))
+                return rc;
+        HIP_TRY(hipEventRecord(b->ev[EV_END], dev->stream));
+        return TRI_OK;
+}
+
+#ifdef TRI_TASKTIMES
+// -DTRI_TASKTIMES[=n] probe builds, with TRINITY_TASKTIMES set: the start and end stamps of one kernel's tasks, summarised on stderr
+static void report_tasktimes(tri_batch *b) {
+        const tri_dev *dev = b->dev;
+        if (!b->tasks.size() || !getenv("TRINITY_TASKTIMES"))
+                return;
+#if TRI_TASKTIMES == 2 // (k_score: tickets run over the docset-materialising tasks, sched[0 ..))
+        const uint32_t nc = trip::sched_first(*b, TASK_FUSED), first = 0;
+#elif TRI_TASKTIMES == 5 // (k_phrase: tickets run over ptasks[])
+        const uint32_t nc = (uint32_t)b->ptasks.size(), first = 0;
+#elif TRI_TASKTIMES == 4 // (k_and_dense)
+        const uint32_t nc = b->n_dense, first = trip::sched_first(*b, TASK_DENSE);
+#elif TRI_TASKTIMES == 3 // (k_planes, the narrow instantiation)
+        const uint32_t nc = b->n_planes, first = trip::sched_first(*b, TASK_PLANES);
+#else
+        const uint32_t nc = b->n_cand, first = trip::sched_first(*b, TASK_CAND);
+#endif
+        unsigned long long t0 = ~0ull, t1 = 0, busy = 0;
+        std::vector<std::pair<unsigned long long, uint32_t>> by;
+        for (uint32_t i = 0; i < nc; ++i) {
+                const unsigned long long s = g_tt_host[8 * i], e = g_tt_host[8 * i + 1];
+                if (!s || !e)
+                        continue;
+                t0 = std::min(t0, s), t1 = std::max(t1, e);
+                busy += e - s;
+                by.emplace_back(e - s, i);
+        }
+        std::sort(by.rbegin(), by.rend());
+        const double span_us = (double)(t1 - t0) / 100.0;
+        const unsigned wgs = std::min<uint32_t>(nc, (uint32_t)dev->cus * (TRI_TASKTIMES == 3 ? PLK_WGS_PER_CU : TRI_TASKTIMES == 2 ? SCORE_WGS_PER_CU : TRI_TASKTIMES == 5 ? PHRASE_WGS_PER_CU : 4));
+        fprintf(stderr, "[tri tasktimes] k_and: %u tasks, span %.1f us, busy %.1f %% of %u workgroups; mean task %.2f us\n", nc, span_us,
+                100.0 * (double)busy / ((double)(t1 - t0) * wgs), wgs, (double)busy / 100.0 / std::max<size_t>(1, by.size()));
+        if (!by.empty()) { // (by: descending) the distribution, and what share of the workgroups' time the longest tasks take
+                auto at = [&](double f) { return (double)by[std::min(by.size() - 1, (size_t)(f * by.size()))].first / 100.0; };
+                unsigned long long top1 = 0, top5 = 0, top20 = 0;
+                for (size_t i = 0; i < by.size(); ++i) {
+                        if (i < by.size() / 100)
+                                top1 += by[i].first;
+                        if (i < by.size() / 20)
+                                top5 += by[i].first;
+                        if (i < by.size() / 5)
+                                top20 += by[i].first;
                 }
-                HIP_TRY(hipEventRecord(b->ev_pl, dev->stream));
-                hipStream_t cand_stream = dev->stream;
-                if (overlap) {
-                        HIP_TRY(hipEventRecord(dev->ev_fork, dev->stream));
-                        HIP_TRY(hipStreamWaitEvent(dev->stream2, dev->ev_fork, 0));
-                        cand_stream = dev->stream2;
-                }
-                // unions with terms that have no plane (PSET_UNIT_SCATTER): those terms' documents listed task by task, a workgroup per query (units[] holds the TASK_PROBE units
-                // too) — on the second stream, beside k_and_dense, where that stream is not k_and's (option overlap)
-                const bool prep = b->n_pset && b->pscatter_queries, prep_forked = prep && !overlap && b->n_dense;
-                if (prep) {
-                        if (prep_forked) {
-                                HIP_TRY(hipEventRecord(dev->ev_fork, dev->stream));
-                                HIP_TRY(hipStreamWaitEvent(dev->stream2, dev->ev_fork, 0));
-                        }
-                        hipStream_t prep_stream = prep_forked ? dev->stream2 : dev->stream;
-                        const uint32_t nunits = b->n_pset + b->n_probe, nscat = (uint32_t)b->pscatter_queries;
-                        hipLaunchKernelGGL(k_psets_prep_list, dim3((nunits + 255) / 256), dim3(256), 0, prep_stream, (const DevPsetUnit *)(b->d_arena + b->off_units), nunits,
-                                           b->d_ticket + TICKET_SCAT_WORD + 1, b->d_scat_list, nscat);
-                        HIP_TRY(hipGetLastError());
-                        TRI_LAUNCH(k_psets_prep, b->ix->codec, dim3(nscat), dim3(PSCAT_WG), prep_stream, (const DevPsetUnit *)(b->d_arena + b->off_units), (const uint32_t *)b->d_scat_list,
-                                   (const uint32_t *)(b->d_ticket + TICKET_SCAT_WORD + 1), b->d_plan, b->d_tasks, (const uint32_t *)b->d_qterms, (const uint32_t *)b->d_qplane, b->ix->d_masked, b->ix->d_index, b->ix->d_blk_last, b->ix->d_blk_off,
-                                   b->ix->d_blk_rec, b->ix->d_blk_doff, b->ix->d_terms, b->d_ticket + TICKET_SCAT_WORD, b->d_scat_off, b->d_scat_cnt, b->d_scat_docs, b->scat_cap);
-                        HIP_TRY(hipGetLastError());
-                        if (prep_forked)
-                                HIP_TRY(hipEventRecord(dev->ev_join, dev->stream2));
-                }
-                if (b->n_dense) {
-                        TRI_LAUNCH(k_and_dense, b->ix->codec, dim3(std::min<uint32_t>(b->n_dense, (uint32_t)dev->cus * dense_wgs)), dim3(DENSE_WG), dev->stream, match_bytes,
-                                           b->ix->d_blk_last, match_off, b->ix->d_win, b->ix->d_terms, b->d_plan, b->d_tasks, b->d_sched, b->d_qterms, b->n_dense,
-                                           b->d_ticket + 16, b->d_out, b->d_counts, b->ix->d_masked, (const uint32_t *)b->d_qplane, (const uint32_t *)b->ix->d_pcache, b->plw);
-                        HIP_TRY(hipGetLastError());
-                }
-                HIP_TRY(hipEventRecord(b->ev_a, dev->stream));
-                if (prep_forked) // (k_psets reads the lists k_psets_prep made beside k_and_dense)
-                        HIP_TRY(hipStreamWaitEvent(dev->stream, dev->ev_join, 0));
-                if (b->n_pset) {
-                        // the queries all of whose terms have planes: word-wise algebra over the planes + expansion (k_psets.hpp)
-                        TRI_LAUNCH(k_psets, b->ix->codec, dim3(std::min<uint32_t>(b->n_pset, (uint32_t)dev->cus * (overlap && dev->opt.overlap_dense_wgs ? std::min<uint32_t>(dense_wgs, TRI_PSET_WAVES * 256 / PSET_WG) : TRI_PSET_WAVES * 256 / PSET_WG))), dim3(PSET_WG), dev->stream,
-                                   (const DevPsetUnit *)(b->d_arena + b->off_units), (const uint32_t *)(b->d_arena + b->off_pset_sched), b->n_pset, b->d_ticket + 20,
-                                   (const uint32_t *)b->d_qterms, (const uint32_t *)b->d_qplane, b->d_out, b->d_counts, b->ix->d_masked, (const uint32_t *)b->ix->d_pcache, b->plw,
-                                   (const uint32_t *)b->d_scat_off, (const uint32_t *)b->d_scat_cnt, (const uint32_t *)b->d_scat_docs);
-                        HIP_TRY(hipGetLastError());
-                }
-                HIP_TRY(hipEventRecord(b->ev_s, dev->stream));
-                if (b->n_probe) {
-                        // one short lead list against lists that all have planes: a wave per task, the lead's documents probed from registers (k_probe.hpp)
-                        TRI_LAUNCH(k_probe, b->ix->codec, dim3(std::min<uint32_t>((b->n_probe + PROBE_WG / 64 - 1) / (PROBE_WG / 64), (uint32_t)dev->cus * (TRI_PROBE_WAVES * 256 / PROBE_WG))),
-                                   dim3(PROBE_WG), dev->stream, match_bytes, b->ix->d_blk_last, match_off, b->ix->d_terms, (const DevPsetUnit *)(b->d_arena + b->off_units),
-                                   (const uint32_t *)(b->d_arena + b->off_pset_sched) + b->n_pset, b->n_probe, b->d_ticket + 22, (const uint32_t *)b->d_qterms,
-                                   (const uint32_t *)b->d_qplane, b->d_out, b->d_counts, b->ix->d_masked, (const uint32_t *)b->ix->d_pcache, b->plw);
-                        HIP_TRY(hipGetLastError());
-                }
-                HIP_TRY(hipEventRecord(b->ev_r, dev->stream));
-                if (b->n_cand)
-                        TRI_LAUNCH(k_and, b->ix->codec, dim3(std::min<uint32_t>(b->n_cand, (uint32_t)dev->cus * cand_wgs)), dim3(AND_WG), cand_stream, match_bytes,
-                                           b->ix->d_blk_last, match_off, b->ix->d_win, b->ix->d_terms, b->d_plan, b->d_tasks, b->d_sched + b->n_dense + b->n_pset + b->n_probe, b->d_qterms,
-                                           (const uint32_t *)(b->d_arena + b->off_cand_q), b->d_ticket + TICKET_CAND_WORD, b->d_out, b->d_counts, b->ix->d_masked, (const uint32_t *)b->d_qplane, (const uint32_t *)b->ix->d_pcache, b->plw);
-                HIP_TRY(hipGetLastError());
-                if (overlap) {
-                        HIP_TRY(hipEventRecord(dev->ev_join, dev->stream2));
-                        HIP_TRY(hipStreamWaitEvent(dev->stream, dev->ev_join, 0));
-                }
-                HIP_TRY(hipEventRecord(b->ev_b, dev->stream));
-                // AccumulatedScore top-K of the dense queries: decode -> match -> score -> select in one pass; as many workgroups per CU as its
-                // LDS holds.  Two instantiations: 32-bit window words, and 16-bit ones (queries of <= 5 distinct terms: windows twice as long)
-                for (int variant = 0; variant < 3; ++variant) { // 0: 32-bit words, 1: 16-bit words, 2: general trees (32-bit words)
-                        const uint32_t nf = variant == 0 ? b->n_fused : variant == 1 ? b->n_fused16 : b->n_fusedgen;
-                        if (!nf)
-                                continue;
-                        const uint32_t *fsched = b->d_sched + b->n_dense + b->n_pset + b->n_probe + b->n_cand + (variant >= 1 ? b->n_fused : 0) + (variant == 2 ? b->n_fused16 : 0);
-                        const dim3 grid(std::min<uint32_t>(nf, (uint32_t)dev->cus * FUS_WGS_PER_CU));
-#define TRI_FUSED_ARGS                                                                                                                                 \
-        b->ix->d_index, b->ix->d_blk_last, b->ix->d_blk_off, b->ix->d_blk_rec, b->ix->d_blk_doff, b->ix->d_win, b->ix->d_terms, b->d_plan, b->d_fused, b->d_tasks, fsched, \
-                b->d_sterms, b->d_sweights, nf, b->d_ticket + 56 + 2 * variant, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores,                \
-                b->d_part_counts, b->ix->d_masked, b->similarity, b->d_out, b->d_all_scores, b->d_rich_allow
-                        if (b->ix->codec == TRI_CODEC_LUCENE) {
-                                if (variant == 0)
-                                        hipLaunchKernelGGL((k_fused<CODEC_LUCENE, 0, 0>), grid, dim3(FUS_WG), 0, dev->stream, TRI_FUSED_ARGS);
-                                else if (variant == 1)
-                                        hipLaunchKernelGGL((k_fused<CODEC_LUCENE, 1, 0>), grid, dim3(FUS_WG), 0, dev->stream, TRI_FUSED_ARGS);
-                                else
-                                        hipLaunchKernelGGL((k_fused<CODEC_LUCENE, 0, 1>), grid, dim3(FUS_WG), 0, dev->stream, TRI_FUSED_ARGS);
-                        } else {
-                                if (variant == 0)
-                                        hipLaunchKernelGGL((k_fused<CODEC_GOOGLE, 0, 0>), grid, dim3(FUS_WG), 0, dev->stream, TRI_FUSED_ARGS);
-                                else if (variant == 1)
-                                        hipLaunchKernelGGL((k_fused<CODEC_GOOGLE, 1, 0>), grid, dim3(FUS_WG), 0, dev->stream, TRI_FUSED_ARGS);
-                                else
-                                        hipLaunchKernelGGL((k_fused<CODEC_GOOGLE, 0, 1>), grid, dim3(FUS_WG), 0, dev->stream, TRI_FUSED_ARGS);
-                        }
-#undef TRI_FUSED_ARGS
-                        HIP_TRY(hipGetLastError());
-                }
-                HIP_TRY(hipEventRecord(b->ev_c, dev->stream));
-                if (b->d_qthr)
-                        HIP_TRY(hipMemsetAsync(b->d_qthr, 0, (b->plan.size() + 1) * 8, dev->stream));
-                for (int wide = 0; wide < 2; ++wide) {
-                        // AccumulatedScore top-K of the CNF queries over bit planes: the head terms' planes from k_term_planes, the other lists
-                        // decoded per window into LDS planes; union / conjunction predicates and the candidate filter 32 documents per word
-                        // (two instantiations: queries of up to five slots, wider ones)
-                        const uint32_t np = wide ? b->n_planes8 : b->n_planes;
-                        if (!np)
-                                continue;
-                        const uint32_t *psched = b->d_sched + b->n_dense + b->n_pset + b->n_probe + b->n_cand + b->n_fused + b->n_fused16 + b->n_fusedgen + (wide ? b->n_planes : 0);
-                        const dim3 grid(std::min<uint32_t>(np, (uint32_t)dev->cus * PLK_WGS_PER_CU));
-#define TRI_PLANES_ARGS                                                                                                                                      \
-        b->ix->d_index, b->ix->d_blk_last, b->ix->d_blk_off, b->ix->d_blk_rec, b->ix->d_blk_doff, b->ix->d_win, b->ix->d_terms, b->d_plan, b->d_fused, b->d_tasks, psched, \
-                b->d_sterms, b->d_sweights, np, b->d_ticket + 24 + 2 * wide, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, b->ix->d_masked,     \
-                b->similarity, (const uint32_t *)b->ix->d_pcache, (const uint32_t *)b->ix->d_pcache_hi, b->plw, b->ix->pc_cap, b->d_sparse, b->sparse_cap, b->d_qthr
-                        if (b->ix->codec == TRI_CODEC_LUCENE) {
-                                if (wide)
-                                        hipLaunchKernelGGL((k_planes<CODEC_LUCENE, FUS_MAX_SLOTS>), grid, dim3(PLK_WG), 0, dev->stream, TRI_PLANES_ARGS);
-                                else
-                                        hipLaunchKernelGGL((k_planes<CODEC_LUCENE, PLK_NS_SMALL>), grid, dim3(PLK_WG), 0, dev->stream, TRI_PLANES_ARGS);
-                        } else {
-                                if (wide)
-                                        hipLaunchKernelGGL((k_planes<CODEC_GOOGLE, FUS_MAX_SLOTS>), grid, dim3(PLK_WG), 0, dev->stream, TRI_PLANES_ARGS);
-                                else
-                                        hipLaunchKernelGGL((k_planes<CODEC_GOOGLE, PLK_NS_SMALL>), grid, dim3(PLK_WG), 0, dev->stream, TRI_PLANES_ARGS);
-                        }
-#undef TRI_PLANES_ARGS
-                        HIP_TRY(hipGetLastError());
-                }
-                HIP_TRY(hipEventRecord(b->ev_k, dev->stream));
-                if (!b->ptasks.empty() && b->ix->codec == TRI_CODEC_GOOGLE && b->ix->d_prank && b->ix->pc_cap) {
-                        // the phrases' head terms are located by RANK in plane 0 (k_phrase.hpp): rows (plane 0 + rank directory) and per-posting hits entries of the
-                        // phrase terms that have none yet are built now — once for the index
-                        tri_index *ix = b->ix;
-                        std::vector<uint32_t> hits_build, hits_only; // (term, row) pairs: the rows that also need their rank records FIRST, then the ones that have them
-                        uint32_t max_blocks = 0;
-                        for (size_t i = 0; i < b->pterms.size(); ++i) {
-                                const uint32_t term = b->pterms[i], r = ix->df_rank[term];
-                                if (r >= ix->pc_cap || ix->ph_built[r])
+                fprintf(stderr, "   task us: max %.1f  p99 %.1f  p90 %.1f  p50 %.1f  p10 %.1f; the longest 1 %% / 5 %% / 20 %% of the tasks take %.1f / %.1f / %.1f %% of the time\n", at(0), at(0.01), at(0.1),
+                        at(0.5), at(0.9), 100.0 * top1 / busy, 100.0 * top5 / busy, 100.0 * top20 / busy);
+        }
+        // the finish-time profile: tasks still running at 25 / 50 / 75 / 90 % of the span
+        for (const double f : {0.25, 0.5, 0.75, 0.9}) {
+                const unsigned long long at = t0 + (unsigned long long)((double)(t1 - t0) * f);
+                unsigned running = 0;
+                for (uint32_t i = 0; i < nc; ++i)
+                        running += g_tt_host[8 * i] <= at && g_tt_host[8 * i + 1] > at;
+                fprintf(stderr, "   at %2.0f %% of the span: %u tasks running\n", f * 100, running);
+        }
+#if TRI_TASKTIMES == 3 // (k_planes: stamps 2 .. 6 = lists decoded + filter filled, phase A done, tables ready, sweep done, queue drained; 1 = end)
+        {
+                const char *nm[8] = {"", "", "setup+lists", "phase A", "prune+tables", "sweep", "drain", "end"};
+                double sum[8] = {0};
+                std::vector<double> span[8];
+                for (uint32_t i = 0; i < nc; ++i) {
+                        unsigned long long prev = g_tt_host[8 * i];
+                        for (int j = 2; j <= 7; ++j) {
+                                const unsigned long long at = j == 7 ? g_tt_host[8 * i + 1] : g_tt_host[8 * i + j];
+                                if (!at || !prev)
                                         continue;
-                                const DevTerm &t = ix->terms[term];
-                                if (!(t.flags & TERM_FULL_BLOCKS) || !t.documents)
-                                        continue;
-                                ix->ph_built[r] = 1;
-                                max_blocks = std::max(max_blocks, t.nblocks);
-                                std::vector<uint32_t> &dst = (ix->pc_built[r] & 4u) ? hits_only : hits_build; // (bit 2: the row's rank records — with them plane 0, if it is not there yet)
-                                ix->pc_built[r] |= 5u;
-                                dst.push_back(term);
-                                dst.push_back(r);
-                        }
-                        const uint32_t nrows_build = (uint32_t)(hits_build.size() / 2);
-                        hits_build.insert(hits_build.end(), hits_only.begin(), hits_only.end());
-                        if (!hits_build.empty()) {
-                                uint32_t *d_pairs = ix->d_ph_pairs + 2 * ix->ph_pairs_n; // (every row is built once: the pairs of all runs fit 2 * pc_cap words)
-                                HIP_TRY(hipMemcpyAsync(d_pairs, hits_build.data(), hits_build.size() * 4, hipMemcpyHostToDevice, dev->stream)); // (pageable source: staged before the call returns)
-                                ix->ph_pairs_n += hits_build.size() / 2;
-                                // the rows without rank records: plane 0 + records in ONE launch over the list's head (round 5 launched a grid per row: 711 launches, 11 ms, the
-                                // first time cfg4's phrases met an index)
-                                for (uint32_t y0 = 0; y0 < nrows_build; y0 += 65535u) {
-                                        const dim3 grid((b->plw / PL_WORDS + P0_GROUP - 1) / P0_GROUP, std::min(65535u, nrows_build - y0));
-                                        TRI_LAUNCH(k_term_plane0, ix->codec, grid, dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec, ix->d_blk_doff, ix->d_win,
-                                                   ix->d_terms, (const uint32_t *)d_pairs + 2 * (size_t)y0, ix->d_pcache, b->plw, ix->d_prank);
-                                        HIP_TRY(hipGetLastError());
-                                }
-                                const uint32_t npairs = (uint32_t)(hits_build.size() / 2);
-                                for (uint32_t y0 = 0; y0 < npairs; y0 += 65535u) { // (gridDim.y <= 65535: a small index at a high plane_div makes almost every term eligible)
-                                        hipLaunchKernelGGL(k_term_hits, dim3((max_blocks + 255) / 256, std::min(65535u, npairs - y0)), dim3(256), 0, dev->stream, ix->d_index, ix->d_blk_off,
-                                                           ix->d_blk_hits, ix->d_terms, (const uint32_t *)d_pairs + 2 * (size_t)y0, (const uint64_t *)ix->d_hs_off, ix->d_phs, ix->d_term_row);
-                                        HIP_TRY(hipGetLastError());
-                                }
+                                const double d = (double)(at - prev) / 100.0;
+                                sum[j] += d;
+                                span[j].push_back(d);
+                                prev = at;
                         }
                 }
-                if (!b->ptasks.empty()) {
-                        // positional constraints: filter + compact the match segments of the queries that hold phrases
-                        const uint32_t np = (uint32_t)b->ptasks.size();
-                        TRI_LAUNCH(k_phrase, b->ix->codec, dim3(std::min<uint32_t>(np, (uint32_t)dev->cus * PHRASE_WGS_PER_CU)), dim3(AND_WG), dev->stream, b->ix->d_index,
-                                           b->ix->d_hits, b->ix->d_blk_hits, b->ix->d_hdir, b->ix->d_blk_last, b->ix->d_blk_off, b->ix->d_win, b->ix->d_terms, b->d_plan, b->d_tasks, b->d_ptasks, np, b->d_phrases, b->d_pterms,
-                                           b->d_ticket + 48, b->d_out, b->d_counts, b->d_pscore,
-                                           (b->flags & TRI_FLAG_ACCUMULATED_SCORE) ? 65535u : 1u, // exec.cpp:296 trackCnt
-                                           b->similarity, (const uint32_t *)b->ix->d_pcache, b->ix->pc_plw, (const uint32_t *)b->ix->d_prank, (const unsigned long long *)b->ix->d_phs,
-                                           (const uint64_t *)b->ix->d_hs_off, (const uint32_t *)(b->ix->codec == TRI_CODEC_GOOGLE ? b->ix->d_term_row : nullptr));
-                        HIP_TRY(hipGetLastError());
+                fprintf(stderr, "   phases (us per task: mean / median / p90):");
+                for (int j = 2; j <= 7; ++j)
+                        if (!span[j].empty()) {
+                                std::sort(span[j].begin(), span[j].end());
+                                fprintf(stderr, "  %s %.1f / %.1f / %.1f", nm[j], sum[j] / span[j].size(), span[j][span[j].size() / 2], span[j][span[j].size() * 9 / 10]);
+                        }
+                fprintf(stderr, "\n");
+                // ... and by the query's DENSE slots (the sweep's instantiation) and whether it holds sparse ones: where the kernel's time goes
+                double tsum[9][2] = {}, ssum[9][2] = {}, asum[9][2] = {};
+                unsigned tcnt[9][2] = {};
+                for (uint32_t i = 0; i < nc; ++i) {
+                        const unsigned long long s0 = g_tt_host[8 * i], e0 = g_tt_host[8 * i + 1];
+                        if (!s0 || !e0)
+                                continue;
+                        const DevTask &tk = b->tasks[b->sched[first + i]];
+                        const DevFused &z = b->fused[b->plan[tk.slot].fused_idx];
+                        uint32_t nd = 0;
+                        for (uint32_t k = 0; k < z.nslots; ++k)
+                                nd += z.plane[k] != PL_NONE;
+                        const int sp = nd < z.nslots;
+                        nd = std::min(nd, 8u);
+                        tsum[nd][sp] += (double)(e0 - s0) / 100.0;
+                        if (g_tt_host[8 * i + 5] > g_tt_host[8 * i + 4] && g_tt_host[8 * i + 4])
+                                ssum[nd][sp] += (double)(g_tt_host[8 * i + 5] - g_tt_host[8 * i + 4]) / 100.0;
+                        if (g_tt_host[8 * i + 3] > g_tt_host[8 * i + 2] && g_tt_host[8 * i + 2])
+                                asum[nd][sp] += (double)(g_tt_host[8 * i + 3] - g_tt_host[8 * i + 2]) / 100.0;
+                        ++tcnt[nd][sp];
                 }
-                HIP_TRY(hipEventRecord(b->ev_p, dev->stream));
-                if (b->n_tree) {
-                        // the queries no other kernel takes (k_tree.hpp): leaf bitmaps — the distinct term leaves decoded once, the phrase leaves from their
-                        // hidden queries' match lists (k_phrase has just filtered them) —, the trees word by word, the match bitmaps expanded
-                        const uint32_t plw = b->plw, nterms = (uint32_t)b->tree_terms.size(), nhid = (uint32_t)b->tree_hidden.size();
-                        const uint32_t nchunks = (plw + TREE_CHUNK_WORDS - 1) / TREE_CHUNK_WORDS;
-                        const uint32_t *tsched = b->d_sched + (n - b->n_tree);
-                        const uint32_t *d_tree = (const uint32_t *)(b->d_arena + b->off_tree);
-                        tri_index *ix = b->ix;
-                        for (uint32_t y0 = 0; y0 < nterms; y0 += 65535u) { // (gridDim.y <= 65535)
-                                const dim3 grid(plw / PL_WORDS, std::min(65535u, nterms - y0));
-                                TRI_LAUNCH(k_term_planes, ix->codec, grid, dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec, ix->d_blk_doff, ix->d_win,
-                                           ix->d_terms, (const uint32_t *)b->d_tree_build + 2 * (size_t)y0, b->d_tree_rows, (size_t)PL_PLANES * plw, b->d_tree_rows + plw,
-                                           (size_t)PL_PLANES * plw, plw, (uint32_t *)nullptr); // (a tree row keeps its two parts side by side: plane k at k * plw)
-                                HIP_TRY(hipGetLastError());
+                for (uint32_t nd = 0; nd <= 8; ++nd)
+                        for (int sp = 0; sp < 2; ++sp)
+                                if (tcnt[nd][sp])
+                                        fprintf(stderr, "   %u dense slots%s: %u tasks, %.1f %% of the time; per task %.1f us (sweep %.1f, phase A %.1f)\n", nd, sp ? " + sparse" : "          ",
+                                                tcnt[nd][sp], 100.0 * tsum[nd][sp] * 100.0 / (double)busy, tsum[nd][sp] / tcnt[nd][sp], ssum[nd][sp] / tcnt[nd][sp], asum[nd][sp] / tcnt[nd][sp]);
+        }
+#endif
+#if TRI_TASKTIMES == 1 // (k_and: the mean of every stamp over all tasks, relative to the task's start)
+        {
+                double sum[8] = {0}, cnt[8] = {0};
+                for (uint32_t i = 0; i < nc; ++i)
+                        for (int j = 1; j < 8; ++j)
+                                if (g_tt_host[8 * i + j] && g_tt_host[8 * i])
+                                        sum[j] += (double)(g_tt_host[8 * i + j] - g_tt_host[8 * i]) / 100.0, cnt[j] += 1;
+                fprintf(stderr, "   means over the tasks (us after the task's start): end %.1f  last tile's lead decoded %.1f", sum[1] / std::max(1.0, cnt[1]), sum[2] / std::max(1.0, cnt[2]));
+                for (int j = 3; j < 8; ++j)
+                        if (cnt[j])
+                                fprintf(stderr, "  term %d %.1f (%.0f tasks)", j - 2, sum[j] / cnt[j], cnt[j]);
+                fprintf(stderr, "\n");
+        }
+#endif
+        for (size_t k = 0; k < std::min<size_t>(12, by.size()); ++k) {
+#if TRI_TASKTIMES == 5
+                const uint32_t ti = b->ptasks[by[k].second];
+#else
+                const uint32_t ti = b->sched[first + by[k].second];
+#endif
+                const DevTask &tk = b->tasks[ti];
+                const DevQuery &q = b->plan[tk.slot];
+                std::string tt;
+                char buf[96];
+                if (task_onepass(tk.kind)) {
+                        const DevFused &z = b->fused[q.fused_idx];
+                        for (uint32_t j = 0; j < z.nslots; ++j) {
+                                snprintf(buf, sizeof buf, " %u(df %u%s)", z.term[j], b->ix->terms[z.term[j]].documents, z.plane[j] != PL_NONE ? " plane" : "");
+                                tt += buf;
                         }
-                        if (nhid) {
-                                HIP_TRY(hipMemsetAsync(b->d_tree_prows, 0, (size_t)nhid * plw * 4, dev->stream));
-                                hipLaunchKernelGGL(k_tree_gather, dim3(nhid), dim3(TREE_WG), 0, dev->stream, b->d_plan, b->d_tasks, (const uint32_t *)(b->d_arena + b->off_tree_hidden), b->d_out,
-                                                   b->d_counts, b->d_pscore, b->d_tree_prows, plw);
-                                HIP_TRY(hipGetLastError());
-                        }
-                        const bool scored_run = b->flags & TRI_FLAG_ACCUMULATED_SCORE, rich_run = b->flags & TRI_FLAG_MATCHED_TERMS;
-                        double *tscores = scored_run ? (b->topk ? b->d_tree_scores : b->d_all_scores) : nullptr;
-                        for (uint32_t y0 = 0; y0 < b->n_tree; y0 += 65535u) {
-                                const dim3 grid(nchunks, std::min(65535u, b->n_tree - y0));
-                                uint32_t *qbits = b->d_tree_qbits + (size_t)y0 * plw, *cc = b->d_tree_cc + (size_t)y0 * nchunks;
-                                hipLaunchKernelGGL(k_tree_eval, grid, dim3(TREE_WG), 0, dev->stream, b->d_plan, b->d_tasks, tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows,
-                                                   (const uint32_t *)b->d_tree_prows, (const uint32_t *)ix->d_masked, qbits, cc, plw);
-                                hipLaunchKernelGGL(k_tree_expand, grid, dim3(TREE_WG), 0, dev->stream, b->d_plan, b->d_tasks, tsched + y0, (const uint32_t *)qbits, (const uint32_t *)cc,
-                                                   b->d_out, b->d_counts, plw);
-                                if (scored_run || rich_run)
-                                        TRI_LAUNCH(k_tree_leaves, ix->codec, grid, dim3(TREE_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->d_plan, b->d_tasks,
-                                                   tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows, (const uint32_t *)b->d_tree_prows, (const uint32_t *)cc, (const uint32_t *)b->d_out,
-                                                   (const uint32_t *)b->d_counts, (const double *)b->d_sweights, (const double *)b->d_pscore, tscores, rich_run ? b->d_rich_allow : nullptr,
-                                                   plw, b->similarity);
-                                HIP_TRY(hipGetLastError());
-                        }
-                        if (scored_run && b->topk) {
-                                hipLaunchKernelGGL(k_tree_topk, dim3(b->n_tree), dim3(AND_WG), 0, dev->stream, tsched, b->d_tasks, (const uint32_t *)b->d_out, (const uint32_t *)b->d_counts,
-                                                   (const double *)tscores, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts);
-                                HIP_TRY(hipGetLastError());
-                        }
+                        snprintf(buf, sizeof buf, " nreq %u", z.nreq);
+                        tt += buf;
+                } else
+                for (uint32_t j = 0; j < q.nterms; ++j) {
+                        const uint32_t term = b->qterms[q.term_base + j] & QT_TERM;
+                        snprintf(buf, sizeof buf, " %s%u(df %u%s)", (b->qterms[q.term_base + j] & QT_GROUP) ? "|" : "", term, b->ix->terms[term].documents,
+                                 (!b->qplane.empty() && b->qplane[q.term_base + j] != PL_NONE) ? " plane" : "");
+                        tt += buf;
                 }
-                HIP_TRY(hipEventRecord(b->ev_t, dev->stream));
-                if (b->flags & TRI_FLAG_MATCHED_TERMS) {
-                        // COUNT pass: which reportable terms hold each match, with what frequency; hit totals per task
-                        HIP_TRY(hipMemsetAsync(b->d_rich_present, 0, (b->out_capacity + 64) * 4, dev->stream));
-                        HIP_TRY(hipMemsetAsync(b->d_rich_freq, 0, (b->out_capacity + 64) * 2 * b->rich_R, dev->stream));
-                        HIP_TRY(hipMemsetAsync(b->d_task_hits, 0, (b->tasks.size() + 1) * 4, dev->stream));
-                        if (b->ix->codec == TRI_CODEC_LUCENE)
-                                hipLaunchKernelGGL((k_rich<CODEC_LUCENE, false>), dim3(std::min<uint32_t>(n, (uint32_t)dev->cus * 3)), dim3(AND_WG), 0, dev->stream, b->ix->d_index,
-                                                   b->ix->d_hits, b->ix->d_blk_hits, b->ix->d_hdir, b->ix->d_blk_last, b->ix->d_blk_off, b->ix->d_terms, b->d_plan, b->d_tasks, b->d_sched,
-                                                   b->d_sterms, n, b->d_ticket + 32, b->d_out, b->d_counts, b->rich_R, b->d_rich_present, b->d_rich_freq, b->d_task_hits,
-                                                   (const uint64_t *)nullptr, (uint16_t *)nullptr, (const uint32_t *)b->d_rich_allow, (uint8_t *)nullptr, (uint64_t *)nullptr);
-                        else
-                                hipLaunchKernelGGL((k_rich<CODEC_GOOGLE, false>), dim3(std::min<uint32_t>(n, (uint32_t)dev->cus * 3)), dim3(AND_WG), 0, dev->stream, b->ix->d_index,
-                                                   b->ix->d_hits, b->ix->d_blk_hits, b->ix->d_hdir, b->ix->d_blk_last, b->ix->d_blk_off, b->ix->d_terms, b->d_plan, b->d_tasks, b->d_sched,
-                                                   b->d_sterms, n, b->d_ticket + 32, b->d_out, b->d_counts, b->rich_R, b->d_rich_present, b->d_rich_freq, b->d_task_hits,
-                                                   (const uint64_t *)nullptr, (uint16_t *)nullptr, (const uint32_t *)b->d_rich_allow, (uint8_t *)nullptr, (uint64_t *)nullptr);
-                        HIP_TRY(hipGetLastError());
-                }
-                if (b->flags & TRI_FLAG_ACCUMULATED_SCORE) {
-                        const uint32_t nlegacy = b->n_dense + b->n_pset + b->n_probe + b->n_cand; // (the sets k_and_dense / k_psets / k_probe / k_and materialised; the one-pass tasks have scored themselves)
-                        if (nlegacy) {
-                        hipLaunchKernelGGL(k_score_order, dim3(1), dim3(SORD_WG), 0, dev->stream, (const uint32_t *)b->d_sched, (const uint32_t *)b->d_counts, nlegacy, b->d_score_order);
-                        HIP_TRY(hipGetLastError());
-                        TRI_LAUNCH(k_score, b->ix->codec, dim3(std::min<uint32_t>(nlegacy, (uint32_t)dev->cus * SCORE_WGS_PER_CU)), dim3(AND_WG), dev->stream, b->ix->d_index,
-                                           b->ix->d_blk_last, b->ix->d_blk_off, b->ix->d_terms, b->d_plan, b->d_tasks, (const uint32_t *)b->d_score_order, b->d_sterms, b->d_sweights, nlegacy,
-                                           b->d_ticket + 32, b->d_out, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts,
-                                           b->d_all_scores, b->d_pscore, b->similarity, b->ix->d_win, b->splane.empty() ? (const uint32_t *)nullptr : (const uint32_t *)(b->d_arena + b->off_splane),
-                                           (const uint32_t *)b->ix->d_pcache_hi, b->plw); // (the scorers read the level words: the rows' high parts)
-                        }
-                        HIP_TRY(hipGetLastError());
-                        const uint32_t nqs = (uint32_t)b->plan.size();
-                        if (b->topk)
-                                hipLaunchKernelGGL(k_topk_merge, dim3(std::min<uint32_t>(nqs, (uint32_t)dev->cus * 8)), dim3(AND_WG), 0, dev->stream, b->d_plan, nqs,
-                                           b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, b->d_top_docs, b->d_top_scores, b->d_top_counts);
-                        HIP_TRY(hipGetLastError());
+                snprintf(buf, sizeof buf, "  matches %u phrases %u", b->h_counts.empty() ? 0u : b->h_counts[ti], q.nphrases);
+                tt += buf;
+                fprintf(stderr, "   %.1f us (started %.1f us in)  ticket %u  tiles [%u, %u)  query %u:%s\n", (double)by[k].first / 100.0,
+                        (double)(g_tt_host[8 * by[k].second] - t0) / 100.0, by[k].second, tk.tile_begin, tk.tile_end, q.qid, tt.c_str());
+                fprintf(stderr, "        last tile: lead decoded +%.1f us", ((double)g_tt_host[8 * by[k].second + 2] - (double)g_tt_host[8 * by[k].second]) / 100.0);
+                for (int j = 3; j < 8; ++j)
+                        if (g_tt_host[8 * by[k].second + j])
+                                fprintf(stderr, "  term %d +%.1f", j - 2, ((double)g_tt_host[8 * by[k].second + j] - (double)g_tt_host[8 * by[k].second]) / 100.0);
+                fprintf(stderr, "\n");
+        }
+}
+#endif
+
+// the run's HIP-event times: last_run_ms from start to end, and per stage the interval between two neighbouring events (term_planes_ms includes the
+// ticket memset that precedes the plane rows)
+static void read_stage_times(tri_batch *b) {
+        static const struct { BatchEvent from; float tri_batch_info::*ms; } STAGES[] = { // (from event `from` to the next one)
+                {EV_START, &tri_batch_info::term_planes_ms}, {EV_PLANE_ROWS, &tri_batch_info::dense_ms}, {EV_DENSE, &tri_batch_info::pset_ms}, {EV_PSET, &tri_batch_info::probe_ms},
+                {EV_PROBE, &tri_batch_info::cand_ms}, {EV_CAND, &tri_batch_info::fused_ms}, {EV_FUSED, &tri_batch_info::planes_ms}, {EV_PLANES, &tri_batch_info::phrase_ms},
+                {EV_PHRASE, &tri_batch_info::tree_ms}, {EV_TREE, &tri_batch_info::rest_ms}};
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, b->ev[EV_START], b->ev[EV_END]) == hipSuccess)
+                b->info.last_run_ms = ms;
+        for (const auto &s : STAGES) {
+                b->info.*s.ms = 0;
+                if (!b->tasks.empty() && hipEventElapsedTime(&ms, b->ev[s.from], b->ev[s.from + 1]) == hipSuccess)
+                        b->info.*s.ms = ms;
+        }
+}
+
+// the matches per task and per query, and the SURVEY §8(d) byte counts the batch's info reports
+static int account_matches(tri_batch *b) {
+        b->h_counts.resize(b->tasks.size());
+        if (!b->tasks.empty())
+                HIP_TRY(hipMemcpy(b->h_counts.data(), b->d_counts, b->tasks.size() * 4, hipMemcpyDeviceToHost));
+        const bool sc = b->flags & TRI_FLAG_ACCUMULATED_SCORE;
+        // per task kind (that of the query's first task): the matches, and the bytes the results take in the form they are delivered in — a
+        // bitmap: its words; a one-pass query: 8 B x min(matches, K) (the docIDs of a DocumentsOnly general tree); the docset-materialising
+        // kinds of a top-K batch: 8 B x min(matches, K) as well (counted by the bound alone)
+        uint64_t m = 0, m_kind[TASK_KINDS] = {}, out_kind[TASK_KINDS] = {};
+        b->h_query_counts.assign(b->plan.size(), 0);
+        for (size_t sidx = 0; sidx < b->plan.size(); ++sidx) {
+                const DevQuery &q = b->plan[sidx];
+                for (uint32_t t = 0; t < q.ntasks; ++t)
+                        b->h_query_counts[sidx] += b->h_counts[q.first_task + t];
+                if (q.qid == 0xffffffffu) // (a hidden phrase query: its matches are a leaf of a TASK_TREE query, not a result)
+                        continue;
+                const uint64_t c = b->h_query_counts[sidx];
+                m += c;
+                if (!q.ntasks)
+                        continue;
+                const uint32_t kind = b->tasks[q.first_task].kind;
+                m_kind[kind] += c;
+                if (task_onepass(kind))
+                        out_kind[kind] += q.out_cap ? 4 * c : 8 * std::min<uint64_t>(c, b->topk);
+                else if (kind != TASK_TREE)
+                        out_kind[kind] += sc && b->topk ? 8 * std::min<uint64_t>(c, b->topk) : (kind == TASK_DENSE || kind == TASK_PSET) && q.form == RESULT_BITMAP ? 4ull * q.out_cap : 4 * c;
+        }
+        const uint64_t out_fused = out_kind[TASK_FUSED] + out_kind[TASK_FUSED16] + out_kind[TASK_FUSED_GEN], out_planes = out_kind[TASK_PLANES] + out_kind[TASK_PLANES8];
+        b->info.dense_algorithmic_bytes = b->term_bytes_dense + 4 * m_kind[TASK_DENSE];
+        b->info.pset_algorithmic_bytes = b->term_bytes_pset + 4 * m_kind[TASK_PSET];
+        b->info.pset_queries = b->pset_queries;
+        b->info.probe_algorithmic_bytes = b->term_bytes_probe + 4 * m_kind[TASK_PROBE];
+        b->info.probe_queries = b->probe_queries;
+        b->info.cand_algorithmic_bytes = (b->term_bytes - b->term_bytes_dense - b->term_bytes_pset - b->term_bytes_probe - b->term_bytes_fused - b->term_bytes_planes - b->term_bytes_phrase_hits) + 4 * m_kind[TASK_CAND];
+        b->info.planes_algorithmic_bytes = b->term_bytes_planes + out_planes; // SURVEY §8(d): docbytes + 8 B x min(matches, K), per query — the lists
+                                                                              // the batch's queries share are nevertheless decoded once per launch
+        // (term_planes_decoded_bytes: set by tri_batch_run — the list bytes of the plane rows THAT run had to build; 0 once the index's cache holds them)
+        b->info.phrase_algorithmic_bytes = b->term_bytes_phrase_hits; // what k_phrase streams by the SURVEY §8(d) count: the hit bytes of the phrases' terms
+        b->info.phrase_queries = 0;
+        for (const DevQuery &q : b->plan)
+                b->info.phrase_queries += q.nphrases != 0;
+        b->info.cand_needed_bytes = b->cand_needed_term_bytes ? b->cand_needed_term_bytes + 4 * (m_kind[TASK_CAND] + m_kind[TASK_PROBE]) : 0; // (the candidate-tile AND the probe queries: what a perfect gallop reads)
+        b->info.fused_algorithmic_bytes = b->term_bytes_fused + out_fused; // SURVEY §8(d): docbytes + 8 B x min(matches, K)
+        b->info.matches = m;
+        if (b->distinct_bytes) { // (option account_needed_bytes: the batch-level bound — every distinct list once + every output once)
+                b->info.pset_bound_bytes = b->distinct_bytes_kind[TASK_PSET] + out_kind[TASK_PSET];
+                b->info.probe_bound_bytes = b->distinct_bytes_kind[TASK_PROBE] + out_kind[TASK_PROBE];
+                b->info.dense_bound_bytes = b->distinct_bytes_kind[TASK_DENSE] + out_kind[TASK_DENSE];
+                b->info.cand_bound_bytes = b->distinct_bytes_kind[TASK_CAND] + out_kind[TASK_CAND];
+                b->info.fused_bound_bytes = b->distinct_bytes_kind[TASK_FUSED] + b->distinct_bytes_kind[TASK_FUSED16] + b->distinct_bytes_kind[TASK_FUSED_GEN] + out_fused;
+                b->info.planes_bound_bytes = b->distinct_bytes_kind[TASK_PLANES] + b->distinct_bytes_kind[TASK_PLANES8] + out_planes;
+                b->info.phrase_bound_bytes = b->distinct_bytes_kind[TASK_KINDS];
+                b->info.bound_bytes = b->distinct_bytes;
+                for (const uint64_t o : out_kind)
+                        b->info.bound_bytes += o;
+        }
+        if (sc) {
+                uint64_t outb = 0; // SURVEY §8(d): 8 B x min(matches, K) per query
+                for (uint64_t c : b->h_query_counts)
+                        outb += 8 * std::min<uint64_t>(c, b->topk);
+                b->info.algorithmic_bytes = b->term_bytes + outb;
+        } else
+                b->info.algorithmic_bytes = b->term_bytes + 4 * m; // SURVEY §8(d): docbytes + 4 B per match (docs-only)
+        return TRI_OK;
+}
+
+// TRI_FLAG_MATCHED_TERMS: the COUNT pass left every task's hit total — turned into pool offsets here (the pool is packed: task after task in
+// query order, inside a task match-major then term-minor) —, then the WRITE pass fills in the positions
+static int rich_write_pass(tri_batch *b) {
+        if (!(b->flags & TRI_FLAG_MATCHED_TERMS) || b->tasks.empty())
+                return TRI_OK;
+        tri_dev *dev = b->dev;
+        const size_t nt = b->tasks.size();
+        std::vector<uint32_t> th(nt);
+        HIP_TRY(hipMemcpy(th.data(), b->d_task_hits, nt * 4, hipMemcpyDeviceToHost));
+        b->h_task_pos_base.assign(nt + 1, 0);
+        for (size_t i = 0; i < nt; ++i)
+                b->h_task_pos_base[i + 1] = b->h_task_pos_base[i] + th[i];
+        const size_t total = b->h_task_pos_base[nt];
+        if (total + 64 > b->rich_pool_cap) {
+                hipFree(b->d_rich_pool);
+                b->d_rich_pool = nullptr;
+                b->rich_pool_cap = total + total / 8 + 64;
+                HIP_TRY(hipMalloc((void **)&b->d_rich_pool, b->rich_pool_cap * 2));
+                if (b->flags & TRI_FLAG_HIT_PAYLOADS) {
+                        hipFree(b->d_rich_plen);
+                        hipFree(b->d_rich_payload);
+                        b->d_rich_plen = nullptr;
+                        b->d_rich_payload = nullptr;
+                        HIP_TRY(hipMalloc((void **)&b->d_rich_plen, b->rich_pool_cap));
+                        HIP_TRY(hipMalloc((void **)&b->d_rich_payload, b->rich_pool_cap * 8));
                 }
         }
-        else {
-                HIP_TRY(hipEventRecord(b->ev_pl, dev->stream));
-                HIP_TRY(hipEventRecord(b->ev_a, dev->stream));
-                HIP_TRY(hipEventRecord(b->ev_s, dev->stream));
-                HIP_TRY(hipEventRecord(b->ev_r, dev->stream));
-                HIP_TRY(hipEventRecord(b->ev_b, dev->stream));
-                HIP_TRY(hipEventRecord(b->ev_c, dev->stream));
-                HIP_TRY(hipEventRecord(b->ev_k, dev->stream));
-                HIP_TRY(hipEventRecord(b->ev_p, dev->stream));
-                HIP_TRY(hipEventRecord(b->ev_t, dev->stream));
-        }
-        if (!b->plan.empty()) {
-                const uint32_t nqs = (uint32_t)b->plan.size();
-                hipLaunchKernelGGL(k_query_counts, dim3((nqs + 255) / 256), dim3(256), 0, dev->stream, b->d_plan, b->d_counts, nqs, b->d_qcounts);
-                HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(b->ev1, dev->stream));
+        HIP_TRY(hipMemcpy(b->d_task_pos_base, b->h_task_pos_base.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(b->d_ticket + TICKET_RICH_WRITE_WORD, 0, 4, dev->stream));
+        if (const int rc = launch_rich<true>(b))
+                return rc;
+        HIP_TRY(hipStreamSynchronize(dev->stream));
+        b->info.algorithmic_bytes += 2 * total + 4 * b->info.matches; // + the positions handed over and a present mask per match
         return TRI_OK;
 }
 
@@ -1466,7 +1814,7 @@ extern "C" int tri_batch_sync(tri_batch *b) {
                 const char *w = getenv("TRINITY_WATCHDOG_S");
                 const double limit = w ? atof(w) : 10.0;
                 double waited = 0;
-                while (hipEventQuery(b->ev1) == hipErrorNotReady) {
+                while (hipEventQuery(b->ev[EV_END]) == hipErrorNotReady) {
                         struct timespec ts = {0, 50 * 1000 * 1000};
                         nanosleep(&ts, nullptr);
                         waited += 0.05;
@@ -1486,314 +1834,15 @@ extern "C" int tri_batch_sync(tri_batch *b) {
 #endif
         // THIS batch's last event, not the engine stream: a caller that keeps the stream fed (the next batch launched before this one is
         // awaited — bench.py's loop) gets this batch's results when THEY are ready, not when everything queued behind them is
-        HIP_TRY(hipEventSynchronize(b->ev1));
+        HIP_TRY(hipEventSynchronize(b->ev[EV_END]));
         DevLock dev_lock(dev->mu); // (the wait above stands outside the lock; what follows may enqueue on the engine stream)
 #ifdef TRI_TASKTIMES
-        if (b->tasks.size() && getenv("TRINITY_TASKTIMES")) {
-#if TRI_TASKTIMES == 2 // (k_score: tickets run over the docset-materialising tasks, sched[0 ..))
-                const uint32_t nc = b->n_dense + b->n_pset + b->n_probe + b->n_cand, first = 0;
-#elif TRI_TASKTIMES == 5 // (k_phrase: tickets run over ptasks[])
-                const uint32_t nc = (uint32_t)b->ptasks.size(), first = 0;
-#elif TRI_TASKTIMES == 4 // (k_and_dense)
-                const uint32_t nc = b->n_dense, first = 0;
-#elif TRI_TASKTIMES == 3 // (k_planes, the narrow instantiation)
-                const uint32_t nc = b->n_planes, first = b->n_dense + b->n_pset + b->n_probe + b->n_cand + b->n_fused + b->n_fused16 + b->n_fusedgen;
-#else
-                const uint32_t nc = b->n_cand, first = b->n_dense + b->n_pset + b->n_probe;
+        report_tasktimes(b);
 #endif
-                unsigned long long t0 = ~0ull, t1 = 0, busy = 0;
-                std::vector<std::pair<unsigned long long, uint32_t>> by;
-                for (uint32_t i = 0; i < nc; ++i) {
-                        const unsigned long long s = g_tt_host[8 * i], e = g_tt_host[8 * i + 1];
-                        if (!s || !e)
-                                continue;
-                        t0 = std::min(t0, s), t1 = std::max(t1, e);
-                        busy += e - s;
-                        by.emplace_back(e - s, i);
-                }
-                std::sort(by.rbegin(), by.rend());
-                const double span_us = (double)(t1 - t0) / 100.0;
-                const unsigned wgs = std::min<uint32_t>(nc, (uint32_t)dev->cus * (TRI_TASKTIMES == 3 ? PLK_WGS_PER_CU : TRI_TASKTIMES == 2 ? SCORE_WGS_PER_CU : TRI_TASKTIMES == 5 ? PHRASE_WGS_PER_CU : 4));
-                fprintf(stderr, "[tri tasktimes] k_and: %u tasks, span %.1f us, busy %.1f %% of %u workgroups; mean task %.2f us\n", nc, span_us,
-                        100.0 * (double)busy / ((double)(t1 - t0) * wgs), wgs, (double)busy / 100.0 / std::max<size_t>(1, by.size()));
-                if (!by.empty()) { // (by: descending) the distribution, and what share of the workgroups' time the longest tasks take
-                        auto at = [&](double f) { return (double)by[std::min(by.size() - 1, (size_t)(f * by.size()))].first / 100.0; };
-                        unsigned long long top1 = 0, top5 = 0, top20 = 0;
-                        for (size_t i = 0; i < by.size(); ++i) {
-                                if (i < by.size() / 100)
-                                        top1 += by[i].first;
-                                if (i < by.size() / 20)
-                                        top5 += by[i].first;
-                                if (i < by.size() / 5)
-                                        top20 += by[i].first;
-                        }
-                        fprintf(stderr, "   task us: max %.1f  p99 %.1f  p90 %.1f  p50 %.1f  p10 %.1f; the longest 1 %% / 5 %% / 20 %% of the tasks take %.1f / %.1f / %.1f %% of the time\n", at(0), at(0.01), at(0.1),
-                                at(0.5), at(0.9), 100.0 * top1 / busy, 100.0 * top5 / busy, 100.0 * top20 / busy);
-                }
-                // the finish-time profile: tasks still running at 25 / 50 / 75 / 90 % of the span
-                for (const double f : {0.25, 0.5, 0.75, 0.9}) {
-                        const unsigned long long at = t0 + (unsigned long long)((double)(t1 - t0) * f);
-                        unsigned running = 0;
-                        for (uint32_t i = 0; i < nc; ++i)
-                                running += g_tt_host[8 * i] <= at && g_tt_host[8 * i + 1] > at;
-                        fprintf(stderr, "   at %2.0f %% of the span: %u tasks running\n", f * 100, running);
-                }
-#if TRI_TASKTIMES == 3 // (k_planes: stamps 2 .. 6 = lists decoded + filter filled, phase A done, tables ready, sweep done, queue drained; 1 = end)
-                {
-                        const char *nm[8] = {"", "", "setup+lists", "phase A", "prune+tables", "sweep", "drain", "end"};
-                        double sum[8] = {0};
-                        std::vector<double> span[8];
-                        for (uint32_t i = 0; i < nc; ++i) {
-                                unsigned long long prev = g_tt_host[8 * i];
-                                for (int j = 2; j <= 7; ++j) {
-                                        const unsigned long long at = j == 7 ? g_tt_host[8 * i + 1] : g_tt_host[8 * i + j];
-                                        if (!at || !prev)
-                                                continue;
-                                        const double d = (double)(at - prev) / 100.0;
-                                        sum[j] += d;
-                                        span[j].push_back(d);
-                                        prev = at;
-                                }
-                        }
-                        fprintf(stderr, "   phases (us per task: mean / median / p90):");
-                        for (int j = 2; j <= 7; ++j)
-                                if (!span[j].empty()) {
-                                        std::sort(span[j].begin(), span[j].end());
-                                        fprintf(stderr, "  %s %.1f / %.1f / %.1f", nm[j], sum[j] / span[j].size(), span[j][span[j].size() / 2], span[j][span[j].size() * 9 / 10]);
-                                }
-                        fprintf(stderr, "\n");
-                        // ... and by the query's DENSE slots (the sweep's instantiation) and whether it holds sparse ones: where the kernel's time goes
-                        double tsum[9][2], ssum[9][2], asum[9][2];
-                        unsigned tcnt[9][2];
-                        for (int x = 0; x < 9; ++x)
-                                for (int y = 0; y < 2; ++y)
-                                        tsum[x][y] = ssum[x][y] = asum[x][y] = 0.0, tcnt[x][y] = 0;
-                        for (uint32_t i = 0; i < nc; ++i) {
-                                const unsigned long long s0 = g_tt_host[8 * i], e0 = g_tt_host[8 * i + 1];
-                                if (!s0 || !e0)
-                                        continue;
-                                const DevTask &tk = b->tasks[b->sched[first + i]];
-                                const DevFused &z = b->fused[b->plan[tk.slot].fused_idx];
-                                uint32_t nd = 0;
-                                for (uint32_t k = 0; k < z.nslots; ++k)
-                                        nd += z.plane[k] != PL_NONE;
-                                const int sp = nd < z.nslots;
-                                nd = std::min(nd, 8u);
-                                tsum[nd][sp] += (double)(e0 - s0) / 100.0;
-                                if (g_tt_host[8 * i + 5] > g_tt_host[8 * i + 4] && g_tt_host[8 * i + 4])
-                                        ssum[nd][sp] += (double)(g_tt_host[8 * i + 5] - g_tt_host[8 * i + 4]) / 100.0;
-                                if (g_tt_host[8 * i + 3] > g_tt_host[8 * i + 2] && g_tt_host[8 * i + 2])
-                                        asum[nd][sp] += (double)(g_tt_host[8 * i + 3] - g_tt_host[8 * i + 2]) / 100.0;
-                                ++tcnt[nd][sp];
-                        }
-                        for (uint32_t nd = 0; nd <= 8; ++nd)
-                                for (int sp = 0; sp < 2; ++sp)
-                                        if (tcnt[nd][sp])
-                                                fprintf(stderr, "   %u dense slots%s: %u tasks, %.1f %% of the time; per task %.1f us (sweep %.1f, phase A %.1f)\n", nd, sp ? " + sparse" : "          ",
-                                                        tcnt[nd][sp], 100.0 * tsum[nd][sp] * 100.0 / (double)busy, tsum[nd][sp] / tcnt[nd][sp], ssum[nd][sp] / tcnt[nd][sp], asum[nd][sp] / tcnt[nd][sp]);
-                }
-#endif
-#if TRI_TASKTIMES == 1 // (k_and: the mean of every stamp over all tasks, relative to the task's start)
-                {
-                        double sum[8] = {0}, cnt[8] = {0};
-                        for (uint32_t i = 0; i < nc; ++i)
-                                for (int j = 1; j < 8; ++j)
-                                        if (g_tt_host[8 * i + j] && g_tt_host[8 * i])
-                                                sum[j] += (double)(g_tt_host[8 * i + j] - g_tt_host[8 * i]) / 100.0, cnt[j] += 1;
-                        fprintf(stderr, "   means over the tasks (us after the task's start): end %.1f  last tile's lead decoded %.1f", sum[1] / std::max(1.0, cnt[1]), sum[2] / std::max(1.0, cnt[2]));
-                        for (int j = 3; j < 8; ++j)
-                                if (cnt[j])
-                                        fprintf(stderr, "  term %d %.1f (%.0f tasks)", j - 2, sum[j] / cnt[j], cnt[j]);
-                        fprintf(stderr, "\n");
-                }
-#endif
-                for (size_t k = 0; k < std::min<size_t>(12, by.size()); ++k) {
-#if TRI_TASKTIMES == 5
-                        const uint32_t ti = b->ptasks[by[k].second];
-#else
-                        const uint32_t ti = b->sched[first + by[k].second];
-#endif
-                        const DevTask &tk = b->tasks[ti];
-                        const DevQuery &q = b->plan[tk.slot];
-                        std::string tt;
-                        if (task_onepass(tk.kind)) {
-                                const DevFused &z = b->fused[q.fused_idx];
-                                char buf[96];
-                                for (uint32_t j = 0; j < z.nslots; ++j) {
-                                        snprintf(buf, sizeof buf, " %u(df %u%s)", z.term[j], b->ix->terms[z.term[j]].documents, z.plane[j] != PL_NONE ? " plane" : "");
-                                        tt += buf;
-                                }
-                                snprintf(buf, sizeof buf, " nreq %u", z.nreq);
-                                tt += buf;
-                        } else
-                        for (uint32_t j = 0; j < q.nterms; ++j) {
-                                const uint32_t term = b->qterms[q.term_base + j] & QT_TERM;
-                                char buf[96];
-                                snprintf(buf, sizeof buf, " %s%u(df %u%s)", (b->qterms[q.term_base + j] & QT_GROUP) ? "|" : "", term, b->ix->terms[term].documents,
-                                         (!b->qplane.empty() && b->qplane[q.term_base + j] != PL_NONE) ? " plane" : "");
-                                tt += buf;
-                        }
-                        {
-                                char buf[64];
-                                snprintf(buf, sizeof buf, "  matches %u phrases %u", b->h_counts.empty() ? 0u : b->h_counts[ti], q.nphrases);
-                                tt += buf;
-                        }
-                        fprintf(stderr, "   %.1f us (started %.1f us in)  ticket %u  tiles [%u, %u)  query %u:%s\n", (double)by[k].first / 100.0,
-                                (double)(g_tt_host[8 * by[k].second] - t0) / 100.0, by[k].second, tk.tile_begin, tk.tile_end, q.qid, tt.c_str());
-                        fprintf(stderr, "        last tile: lead decoded +%.1f us", ((double)g_tt_host[8 * by[k].second + 2] - (double)g_tt_host[8 * by[k].second]) / 100.0);
-                        for (int j = 3; j < 8; ++j)
-                                if (g_tt_host[8 * by[k].second + j])
-                                        fprintf(stderr, "  term %d +%.1f", j - 2, ((double)g_tt_host[8 * by[k].second + j] - (double)g_tt_host[8 * by[k].second]) / 100.0);
-                        fprintf(stderr, "\n");
-                }
-        }
-#endif
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, b->ev0, b->ev1) == hipSuccess)
-                b->info.last_run_ms = ms;
-        b->info.dense_ms = b->info.pset_ms = b->info.probe_ms = b->info.cand_ms = b->info.fused_ms = b->info.phrase_ms = b->info.tree_ms = b->info.rest_ms = b->info.term_planes_ms = b->info.planes_ms = 0;
-        if (!b->tasks.empty()) {
-                if (hipEventElapsedTime(&ms, b->ev0, b->ev_pl) == hipSuccess)
-                        b->info.term_planes_ms = ms; // includes the ticket memset that precedes it
-                if (hipEventElapsedTime(&ms, b->ev_pl, b->ev_a) == hipSuccess)
-                        b->info.dense_ms = ms;
-                if (hipEventElapsedTime(&ms, b->ev_a, b->ev_s) == hipSuccess)
-                        b->info.pset_ms = ms;
-                if (hipEventElapsedTime(&ms, b->ev_s, b->ev_r) == hipSuccess)
-                        b->info.probe_ms = ms;
-                if (hipEventElapsedTime(&ms, b->ev_r, b->ev_b) == hipSuccess)
-                        b->info.cand_ms = ms;
-                if (hipEventElapsedTime(&ms, b->ev_b, b->ev_c) == hipSuccess)
-                        b->info.fused_ms = ms;
-                if (hipEventElapsedTime(&ms, b->ev_c, b->ev_k) == hipSuccess)
-                        b->info.planes_ms = ms;
-                if (hipEventElapsedTime(&ms, b->ev_k, b->ev_p) == hipSuccess)
-                        b->info.phrase_ms = ms;
-                if (hipEventElapsedTime(&ms, b->ev_p, b->ev_t) == hipSuccess)
-                        b->info.tree_ms = ms;
-                if (hipEventElapsedTime(&ms, b->ev_t, b->ev1) == hipSuccess)
-                        b->info.rest_ms = ms;
-        }
-        b->h_counts.resize(b->tasks.size());
-        if (!b->tasks.empty())
-                HIP_TRY(hipMemcpy(b->h_counts.data(), b->d_counts, b->tasks.size() * 4, hipMemcpyDeviceToHost));
-        uint64_t m = 0;
-        b->h_query_counts.assign(b->plan.size(), 0);
-        uint64_t m_dense = 0, m_pset = 0, m_probe = 0, m_fused = 0, out_fused = 0, out_planes = 0, m_tree = 0;
-        uint64_t outb_dense = 0, outb_pset = 0; // bytes the bitmap-window queries' results take in the form they are delivered in (a bitmap: its words)
-        for (size_t sidx = 0; sidx < b->plan.size(); ++sidx) {
-                const DevQuery &q = b->plan[sidx];
-                for (uint32_t t = 0; t < q.ntasks; ++t)
-                        b->h_query_counts[sidx] += b->h_counts[q.first_task + t];
-                if (q.qid == 0xffffffffu) // (a hidden phrase query: its matches are a leaf of a TASK_TREE query, not a result)
-                        continue;
-                m += b->h_query_counts[sidx];
-                if (q.ntasks && b->tasks[q.first_task].kind == TASK_TREE)
-                        m_tree += b->h_query_counts[sidx];
-                if (q.ntasks && b->tasks[q.first_task].kind == TASK_DENSE) {
-                        m_dense += b->h_query_counts[sidx];
-                        outb_dense += q.form == RESULT_BITMAP ? 4ull * q.out_cap : 4 * b->h_query_counts[sidx];
-                }
-                if (q.ntasks && b->tasks[q.first_task].kind == TASK_PSET) {
-                        m_pset += b->h_query_counts[sidx];
-                        outb_pset += q.form == RESULT_BITMAP ? 4ull * q.out_cap : 4 * b->h_query_counts[sidx];
-                }
-                if (q.ntasks && b->tasks[q.first_task].kind == TASK_PROBE)
-                        m_probe += b->h_query_counts[sidx];
-                if (q.ntasks && task_onepass(b->tasks[q.first_task].kind)) {
-                        m_fused += b->h_query_counts[sidx]; // (every one-pass kind, k_planes' included)
-                        (b->tasks[q.first_task].kind >= TASK_PLANES ? out_planes : out_fused) += // (one-pass kinds only: TASK_PLANES / TASK_PLANES8 are the last two of them)
-                                q.out_cap ? 4 * b->h_query_counts[sidx] : 8 * std::min<uint64_t>(b->h_query_counts[sidx], b->topk); // (docIDs of a DocumentsOnly general tree)
-                }
-        }
-        b->info.dense_algorithmic_bytes = b->term_bytes_dense + 4 * m_dense;
-        b->info.pset_algorithmic_bytes = b->term_bytes_pset + 4 * m_pset;
-        b->info.pset_queries = b->pset_queries;
-        b->info.probe_algorithmic_bytes = b->term_bytes_probe + 4 * m_probe;
-        b->info.probe_queries = b->probe_queries;
-        b->info.cand_queries = b->cand_queries;
-        b->info.cand_algorithmic_bytes = (b->term_bytes - b->term_bytes_dense - b->term_bytes_pset - b->term_bytes_probe - b->term_bytes_fused - b->term_bytes_planes - b->term_bytes_phrase_hits) + 4 * (m - m_dense - m_pset - m_probe - m_fused - m_tree);
-        b->info.planes_algorithmic_bytes = b->term_bytes_planes + out_planes; // SURVEY §8(d): docbytes + 8 B x min(matches, K), per query — the lists
-                                                                              // the batch's queries share are nevertheless decoded once per launch
-        // (term_planes_decoded_bytes: set by tri_batch_run — the list bytes of the plane rows THAT run had to build; 0 once the index's cache holds them)
-        b->info.phrase_algorithmic_bytes = b->term_bytes_phrase_hits; // what k_phrase streams by the SURVEY §8(d) count: the hit bytes of the phrases' terms
-        b->info.phrase_queries = 0;
-        for (const DevQuery &q : b->plan)
-                b->info.phrase_queries += q.nphrases != 0;
-        b->info.cand_needed_bytes = b->cand_needed_term_bytes ? b->cand_needed_term_bytes + 4 * (m - m_dense - m_pset - m_fused - m_tree) : 0; // (the candidate-tile AND the probe queries: what a perfect gallop reads)
-        b->info.fused_algorithmic_bytes = b->term_bytes_fused + out_fused; // SURVEY §8(d): docbytes + 8 B x min(matches, K)
-        b->info.matches = m;
-        if (b->distinct_bytes) { // (option account_needed_bytes: the batch-level bound — every distinct list once + every output once)
-                const uint64_t m_cand = m - m_dense - m_pset - m_probe - m_fused - m_tree;
-                const bool sc = b->flags & TRI_FLAG_ACCUMULATED_SCORE;
-                uint64_t out_legacy_dense = outb_dense, out_legacy_pset = outb_pset, out_legacy_probe = 4 * m_probe, out_legacy_cand = 4 * m_cand; // (the bound counts a result in the form it is delivered in)
-                if (sc && b->topk) { // (queries matched by k_and_dense / k_psets / k_and of a top-K batch deliver 8 B x min(matches, K))
-                        out_legacy_dense = out_legacy_pset = out_legacy_probe = out_legacy_cand = 0;
-                        for (size_t sidx = 0; sidx < b->plan.size(); ++sidx) {
-                                const DevQuery &q = b->plan[sidx];
-                                if (!q.ntasks || task_onepass(b->tasks[q.first_task].kind) || b->tasks[q.first_task].kind == TASK_TREE || q.qid == 0xffffffffu)
-                                        continue;
-                                const uint32_t kd = b->tasks[q.first_task].kind;
-                                (kd == TASK_DENSE ? out_legacy_dense : kd == TASK_PSET ? out_legacy_pset : kd == TASK_PROBE ? out_legacy_probe : out_legacy_cand) += 8 * std::min<uint64_t>(b->h_query_counts[sidx], b->topk);
-                        }
-                }
-                b->info.pset_bound_bytes = b->distinct_bytes_kind[TASK_PSET] + out_legacy_pset;
-                b->info.probe_bound_bytes = b->distinct_bytes_kind[TASK_PROBE] + out_legacy_probe;
-                b->info.dense_bound_bytes = b->distinct_bytes_kind[TASK_DENSE] + out_legacy_dense;
-                b->info.cand_bound_bytes = b->distinct_bytes_kind[TASK_CAND] + out_legacy_cand;
-                b->info.fused_bound_bytes = b->distinct_bytes_kind[TASK_FUSED] + b->distinct_bytes_kind[TASK_FUSED16] + b->distinct_bytes_kind[TASK_FUSED_GEN] + out_fused;
-                b->info.planes_bound_bytes = b->distinct_bytes_kind[TASK_PLANES] + b->distinct_bytes_kind[TASK_PLANES8] + out_planes;
-                b->info.phrase_bound_bytes = b->distinct_bytes_kind[TASK_KINDS];
-                b->info.bound_bytes = b->distinct_bytes + out_legacy_dense + out_legacy_pset + out_legacy_probe + out_legacy_cand + out_fused + out_planes;
-        }
-        if (b->flags & TRI_FLAG_ACCUMULATED_SCORE) {
-                uint64_t outb = 0; // SURVEY §8(d): 8 B x min(matches, K) per query
-                for (uint64_t c : b->h_query_counts)
-                        outb += 8 * std::min<uint64_t>(c, b->topk);
-                b->info.algorithmic_bytes = b->term_bytes + outb;
-        } else
-                b->info.algorithmic_bytes = b->term_bytes + 4 * m; // SURVEY §8(d): docbytes + 4 B per match (docs-only)
-        if ((b->flags & TRI_FLAG_MATCHED_TERMS) && !b->tasks.empty()) {
-                // the COUNT pass left every task's hit total: turn them into pool offsets (the pool is packed: task after task in
-                // query order, inside a task match-major then term-minor), then the WRITE pass fills in the positions
-                const size_t nt = b->tasks.size();
-                std::vector<uint32_t> th(nt);
-                HIP_TRY(hipMemcpy(th.data(), b->d_task_hits, nt * 4, hipMemcpyDeviceToHost));
-                b->h_task_pos_base.assign(nt + 1, 0);
-                for (size_t i = 0; i < nt; ++i)
-                        b->h_task_pos_base[i + 1] = b->h_task_pos_base[i] + th[i];
-                const size_t total = b->h_task_pos_base[nt];
-                if (total + 64 > b->rich_pool_cap) {
-                        hipFree(b->d_rich_pool);
-                        b->d_rich_pool = nullptr;
-                        b->rich_pool_cap = total + total / 8 + 64;
-                        HIP_TRY(hipMalloc((void **)&b->d_rich_pool, b->rich_pool_cap * 2));
-                        if (b->flags & TRI_FLAG_HIT_PAYLOADS) {
-                                hipFree(b->d_rich_plen);
-                                hipFree(b->d_rich_payload);
-                                b->d_rich_plen = nullptr;
-                                b->d_rich_payload = nullptr;
-                                HIP_TRY(hipMalloc((void **)&b->d_rich_plen, b->rich_pool_cap));
-                                HIP_TRY(hipMalloc((void **)&b->d_rich_payload, b->rich_pool_cap * 8));
-                        }
-                }
-                HIP_TRY(hipMemcpy(b->d_task_pos_base, b->h_task_pos_base.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
-                HIP_TRY(hipMemsetAsync(b->d_ticket + 40, 0, 4, dev->stream));
-                const uint32_t n = (uint32_t)nt;
-                if (b->ix->codec == TRI_CODEC_LUCENE)
-                        hipLaunchKernelGGL((k_rich<CODEC_LUCENE, true>), dim3(std::min<uint32_t>(n, (uint32_t)dev->cus * 3)), dim3(AND_WG), 0, dev->stream, b->ix->d_index, b->ix->d_hits,
-                                           b->ix->d_blk_hits, b->ix->d_hdir, b->ix->d_blk_last, b->ix->d_blk_off, b->ix->d_terms, b->d_plan, b->d_tasks, b->d_sched, b->d_sterms, n,
-                                           b->d_ticket + 40, b->d_out, b->d_counts, b->rich_R, b->d_rich_present, b->d_rich_freq, b->d_task_hits,
-                                           (const uint64_t *)b->d_task_pos_base, b->d_rich_pool, (const uint32_t *)b->d_rich_allow, b->d_rich_plen, b->d_rich_payload);
-                else
-                        hipLaunchKernelGGL((k_rich<CODEC_GOOGLE, true>), dim3(std::min<uint32_t>(n, (uint32_t)dev->cus * 3)), dim3(AND_WG), 0, dev->stream, b->ix->d_index, b->ix->d_hits,
-                                           b->ix->d_blk_hits, b->ix->d_hdir, b->ix->d_blk_last, b->ix->d_blk_off, b->ix->d_terms, b->d_plan, b->d_tasks, b->d_sched, b->d_sterms, n,
-                                           b->d_ticket + 40, b->d_out, b->d_counts, b->rich_R, b->d_rich_present, b->d_rich_freq, b->d_task_hits,
-                                           (const uint64_t *)b->d_task_pos_base, b->d_rich_pool, (const uint32_t *)b->d_rich_allow, b->d_rich_plen, b->d_rich_payload);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipStreamSynchronize(dev->stream));
-                b->info.algorithmic_bytes += 2 * total + 4 * m; // + the positions handed over and a present mask per match
-        }
+        read_stage_times(b);
+        int rc;
+        if ((rc = account_matches(b)) || (rc = rich_write_pass(b)))
+                return rc;
         b->synced = true;
         return TRI_OK;
 }
