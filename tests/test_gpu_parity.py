@@ -1675,6 +1675,44 @@ def test_commit_on_the_device(T, dev, payloads):
     assert got.size == 0 and gtids.size == 0 and stats["total_terms"] == 0
 
 
+def test_write_side_hands_its_temporaries_back(T, dev):
+    """Every write-side call draws its device temporaries from the handle's buffer pool and hands all of them back when it returns — a call that is refused
+    AFTER its allocations (the same (term, document) twice: found on the device, once the session is sorted) included: the pool's bytes in use are what they
+    were before the call.  The postings are large enough for several of a call's buffers to lie above the 64 KiB the pool starts at."""
+    rng = np.random.default_rng(41)
+    nterms = 400
+    docs, freqs, pos, tf = random_postings(rng, nterms)
+    assert docs.size * 4 > 2 * 65536 and pos.size * 2 > 65536
+    plen = rng.integers(0, 9, size=pos.size).astype(np.uint8)
+    pval = rng.integers(0, 2**63, size=pos.size, dtype=np.uint64)
+    tids = np.repeat(np.arange(1, nterms + 1, dtype=np.uint32), np.diff(tf).astype(np.int64))  # (a session that inserts term after term)
+    gi, gt = dev.encode_google(docs, freqs, pos, tf)
+    li, lh, lt = dev.encode_lucene(docs, freqs, pos, tf)
+    gix = T.Index(dev, gi, gt, int(docs.max()))
+    lix = T.Index(dev, li, lt, int(docs.max()), codec=2, hits=lh)
+    only = np.arange(nterms, dtype=np.uint32).reshape(-1, 1)
+
+    def refused_commit():
+        with pytest.raises(T.TrinityError, match="twice"):
+            dev.commit_google([7, 7], [5, 5], [1, 1], [3, 4])
+
+    calls = [
+        ("encode_google", lambda: dev.encode_google(docs, freqs, pos, tf, plen, pval)),
+        ("encode_lucene", lambda: dev.encode_lucene(docs, freqs, pos, tf)),
+        ("commit_google", lambda: dev.commit_google(tids, docs, freqs, pos)),
+        ("commit_lucene", lambda: dev.commit_lucene(tids, docs, freqs, pos)),
+        ("merge_google", lambda: dev.merge_google([gix], only)),
+        ("merge_lucene", lambda: dev.merge_lucene([lix], only)),
+        ("refused commit_google", refused_commit),
+    ]
+    for name, call in calls:
+        before = dev.memory()["pool_in_use_bytes"]
+        call()
+        assert dev.memory()["pool_in_use_bytes"] == before, name
+    gix.close()
+    lix.close()
+
+
 def test_merge_on_the_device(T, dev):
     """tri_merge_google — Codecs::Google::IndexSession::merge (google_codec.cpp:186-438) over a whole dictionary: three segments with overlapping
     dictionaries and documentIDs, each masked by its own set; per output term the union of the documents, a document from the MOST RECENT participant that

@@ -16,6 +16,9 @@
 //                    block-driven (dense) or candidate-driven galloping (sparse) over the block directory,
 //                    one lane per needed block, merging the decoded docs against the candidates in LDS
 //                    (Conjuction::next_impl leapfrog, docset_iterators.cpp:308-348, as a set operation)
+//
+// The write side — the encoders, commit and merge on the device (tri_encode_*, tri_commit_*, tri_merge_*) — is write_side.hpp, included
+// at the end of this file: the same translation unit, as the k_*.hpp kernel files are.
 #include "../../include/trinity_hip.h"
 #include <chrono>
 #include <hip/hip_runtime.h>
@@ -2513,649 +2516,8 @@ extern "C" int tri_gather_results(tri_batch *b, tri_comm *c, void *counts_all, v
 }
 
 // ------------------------------------------------------------------------------------------ write side
-// Codecs::Google::Encoder (google_codec.cpp:9-176) on the device: postings in, the segment's `index` bytes and term table out —
-// byte for byte what the reference's encoder writes for the same begin_term / begin_document / new_hit / end_document / end_term
-// calls (payload-less hits).  See k_encode.hpp.
-extern "C" int tri_encode_google(tri_dev *dev, const uint32_t *docs, const uint32_t *freqs, const uint16_t *positions, size_t npositions, const uint64_t *term_first,
-                                 size_t nterms, uint8_t *index_out, size_t cap, size_t *index_len, tri_term *terms_out) {
-        return tri_encode_google_payloads(dev, docs, freqs, positions, nullptr, nullptr, npositions, term_first, nterms, index_out, cap, index_len, terms_out);
-}
-
-// ---- the device side of the Google encoder, shared by tri_encode_google[_payloads] (postings uploaded from the host) and tri_commit_google
-//      (postings sorted and gathered on the device): d.docs / d.freqs / d.pos (/ d.plens, d.payloads) hold np postings and nhits hits grouped by term as
-//      term_first (host) says, validated by the caller
-namespace {
-struct EncBufs {
-        uint32_t *docs = nullptr, *freqs = nullptr, *blk_first = nullptr, *blk_term = nullptr, *sizes = nullptr, *tails = nullptr;
-        uint16_t *pos = nullptr;
-        uint64_t *hit_off = nullptr, *term_first = nullptr, *blk_off = nullptr, *term_off = nullptr, *payloads = nullptr, *scan_sums = nullptr;
-        uint64_t scan_cap = 0;
-        uint8_t *out = nullptr, *plens = nullptr;
-        ~EncBufs() {
-                for (void *p : {(void *)docs, (void *)freqs, (void *)blk_first, (void *)blk_term, (void *)sizes, (void *)tails, (void *)pos, (void *)hit_off,
-                                (void *)term_first, (void *)blk_off, (void *)term_off, (void *)out, (void *)payloads, (void *)plens, (void *)scan_sums})
-                        hipFree(p);
-        }
-};
-// exclusive scan of n u32 into u64 over the whole device: chunk sums, chunk bases, chunks (k_encode.hpp)
-int enc_scan(tri_dev *dev, EncBufs &d, const uint32_t *in, uint64_t *outp, const uint64_t n) {
-        const uint64_t nchunks = (n + ENC_SCAN_CHUNK - 1) / ENC_SCAN_CHUNK;
-        if (nchunks <= 1) {
-                hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(1024), 0, dev->stream, in, outp, n);
-                return TRI_OK;
-        }
-        if (nchunks + 1 > d.scan_cap) {
-                hipFree(d.scan_sums);
-                d.scan_sums = nullptr;
-                d.scan_cap = nchunks + 1;
-                HIP_TRY(hipMalloc((void **)&d.scan_sums, d.scan_cap * 8));
-        }
-        hipLaunchKernelGGL(k_enc_scan_sums, dim3((uint32_t)nchunks), dim3(1024), 0, dev->stream, in, d.scan_sums, n);
-        hipLaunchKernelGGL(k_enc_scan_bases, dim3(1), dim3(1024), 0, dev->stream, d.scan_sums, nchunks);
-        hipLaunchKernelGGL(k_enc_scan_chunks, dim3((uint32_t)nchunks), dim3(1024), 0, dev->stream, in, (const uint64_t *)d.scan_sums, outp, n);
-        return TRI_OK;
-}
-int encode_google_device(tri_dev *dev, EncBufs &d, const uint64_t *term_first, const size_t nterms, const uint64_t np, const uint64_t nhits, uint8_t *index_out,
-                         const size_t cap, size_t *index_len, tri_term *terms_out) {
-        (void)np;
-        (void)nhits;
-        // ---- host: the block structure (which block belongs to which term)
-        std::vector<uint32_t> blk_first(nterms + 1, 0), blk_term;
-        for (size_t t = 0; t < nterms; ++t) {
-                const uint64_t nb = (term_first[t + 1] - term_first[t] + 31) / 32;
-                if ((uint64_t)blk_first[t] + nb > 0xfffffff0ull)
-                        return fail(TRI_ERR_UNSUPPORTED, "more than 2^32 blocks");
-                blk_first[t + 1] = blk_first[t] + (uint32_t)nb;
-                blk_term.insert(blk_term.end(), (size_t)nb, (uint32_t)t);
-        }
-        const uint32_t nblocks = blk_first[nterms];
-        std::vector<uint64_t> term_off(nterms + 1, 0);
-        std::vector<uint64_t> blk_off(nblocks + 1, 0);
-        if (nblocks) {
-                HIP_TRY(hipMalloc((void **)&d.hit_off, (np + 1) * 8));
-                HIP_TRY(hipMalloc((void **)&d.term_first, (nterms + 1) * 8));
-                HIP_TRY(hipMalloc((void **)&d.blk_first, (nterms + 1) * 4));
-                HIP_TRY(hipMalloc((void **)&d.blk_term, (size_t)nblocks * 4));
-                HIP_TRY(hipMalloc((void **)&d.sizes, (size_t)nblocks * 4));
-                HIP_TRY(hipMalloc((void **)&d.tails, (size_t)nblocks * 4));
-                HIP_TRY(hipMalloc((void **)&d.blk_off, ((size_t)nblocks + 1) * 8));
-                HIP_TRY(hipMemcpyAsync(d.term_first, term_first, (nterms + 1) * 8, hipMemcpyHostToDevice, dev->stream));
-                HIP_TRY(hipMemcpyAsync(d.blk_first, blk_first.data(), (nterms + 1) * 4, hipMemcpyHostToDevice, dev->stream));
-                HIP_TRY(hipMemcpyAsync(d.blk_term, blk_term.data(), (size_t)nblocks * 4, hipMemcpyHostToDevice, dev->stream));
-                // hits before every posting, then the blocks' sizes and their running sum
-                // (exclusive scans over the whole device: chunk sums, chunk bases, chunks — k_encode.hpp)
-                int rcs;
-                if ((rcs = enc_scan(dev, d, d.freqs, d.hit_off, np)))
-                        return rcs;
-                const EncArgs a{d.docs, d.freqs, d.pos, d.plens, d.payloads, d.hit_off, d.term_first, d.blk_first, d.blk_term, nblocks};
-                hipLaunchKernelGGL(k_enc_size, dim3((nblocks + 255) / 256), dim3(256), 0, dev->stream, a, d.sizes, d.tails);
-                if ((rcs = enc_scan(dev, d, d.sizes, d.blk_off, (uint64_t)nblocks)))
-                        return rcs;
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(blk_off.data(), d.blk_off, ((size_t)nblocks + 1) * 8, hipMemcpyDeviceToHost, dev->stream));
-                HIP_TRY(hipStreamSynchronize(dev->stream));
-        }
-        // ---- host: where every term's chunk starts (2 bytes + its blocks + its skiplist entries)
-        for (size_t t = 0; t < nterms; ++t) {
-                const uint32_t g0 = blk_first[t], g1 = blk_first[t + 1];
-                uint64_t entries = 0;
-                if (g1 > g0) {
-                        const uint32_t first_marked = (g0 + 8) / 8 * 8 - 1;
-                        if (g1 - 1 >= first_marked)
-                                entries = std::min<uint64_t>(65535, (g1 - 1 - first_marked) / 8 + 1);
-                }
-                const uint64_t size = 2 + (blk_off[g1] - blk_off[g0]) + 8 * entries;
-                if (term_off[t] + size > 0xffffffffull)
-                        return fail(TRI_ERR_UNSUPPORTED, "the index would exceed 4 GiB (term_index_ctx offsets are 32 bits)");
-                terms_out[t] = {(uint32_t)(term_first[t + 1] - term_first[t]), (uint32_t)term_off[t], (uint32_t)size};
-                term_off[t + 1] = term_off[t] + size;
-        }
-        *index_len = (size_t)term_off[nterms];
-        if (!index_out)
-                return TRI_OK; // (sizing call)
-        if (cap < *index_len)
-                return fail(TRI_ERR_INVALID, "tri_encode_google: the index needs %zu bytes, %zu given", *index_len, cap);
-        if (!*index_len)
-                return TRI_OK;
-        HIP_TRY(hipMalloc((void **)&d.out, *index_len));
-        HIP_TRY(hipMemsetAsync(d.out, 0, *index_len, dev->stream)); // (a term without documents is two zero bytes)
-        if (nblocks) {
-                HIP_TRY(hipMalloc((void **)&d.term_off, (nterms + 1) * 8));
-                HIP_TRY(hipMemcpyAsync(d.term_off, term_off.data(), (nterms + 1) * 8, hipMemcpyHostToDevice, dev->stream));
-                const EncArgs a{d.docs, d.freqs, d.pos, d.plens, d.payloads, d.hit_off, d.term_first, d.blk_first, d.blk_term, nblocks};
-                hipLaunchKernelGGL(k_enc_write, dim3((nblocks + 255) / 256), dim3(256), 0, dev->stream, a, d.blk_off, d.tails, d.term_off, d.out);
-                HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipMemcpyAsync(index_out, d.out, *index_len, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipStreamSynchronize(dev->stream));
-        return TRI_OK;
-}
-
-} // namespace
-
-extern "C" int tri_encode_google_payloads(tri_dev *dev, const uint32_t *docs, const uint32_t *freqs, const uint16_t *positions, const uint8_t *payload_lens,
-                                          const uint64_t *payloads, size_t npositions, const uint64_t *term_first, size_t nterms, uint8_t *index_out, size_t cap,
-                                          size_t *index_len, tri_term *terms_out) {
-        if (!dev || !term_first || !index_len || (nterms && !terms_out) || (payload_lens && !payloads))
-                return fail(TRI_ERR_INVALID, "tri_encode_google: null argument");
-        HIP_TRY(hipSetDevice(dev->device));
-        const uint64_t np = nterms ? term_first[nterms] : 0;
-        if (np && (!docs || !freqs))
-                return fail(TRI_ERR_INVALID, "tri_encode_google: null postings");
-        if (npositions && !positions)
-                return fail(TRI_ERR_INVALID, "tri_encode_google: null positions");
-        // ---- host: input validation (what the reference's encoder would refuse)
-        uint64_t nhits = 0;
-        for (size_t t = 0; t < nterms; ++t) {
-                if (term_first[t + 1] < term_first[t])
-                        return fail(TRI_ERR_INVALID, "tri_encode_google: term_first must ascend");
-                const uint64_t n = term_first[t + 1] - term_first[t];
-                if (n > 0xffffffffull)
-                        return fail(TRI_ERR_UNSUPPORTED, "term %zu: more than 2^32 documents", t);
-                uint32_t prev = 0;
-                for (uint64_t p = term_first[t]; p < term_first[t + 1]; ++p) {
-                        if (!docs[p] || docs[p] <= prev)
-                                return fail(TRI_ERR_INVALID, "term %zu: document IDs must be > 0 and strictly ascending (codecs.h:188-190)", t);
-                        prev = docs[p];
-                        // the posting's hits: positions[nhits .. nhits + freqs[p]) — counted hits only (new_hit drops a payload-less hit at
-                        // position 0, google_codec.cpp:42-45), non-descending within the document (:49: the encoder writes pos - lastPos)
-                        if ((uint64_t)freqs[p] > npositions - std::min<uint64_t>(npositions, nhits))
-                                return fail(TRI_ERR_INVALID, "term %zu, document %u: freqs[] asks for more positions than the %zu given", t, docs[p], npositions);
-                        uint32_t last_pos = 0;
-                        for (uint64_t h = nhits; h < nhits + freqs[p]; ++h) {
-                                const uint32_t plen = payload_lens ? payload_lens[h] : 0u;
-                                if (plen > 8)
-                                        return fail(TRI_ERR_INVALID, "term %zu, document %u: a payload of %u bytes (at most 8: google_codec.cpp:46)", t, docs[p], plen);
-                                if ((!positions[h] && !plen) || positions[h] < last_pos) // (a position-0 hit WITH a payload is a counted hit: :42-45)
-                                        return fail(TRI_ERR_INVALID, "term %zu, document %u: positions must be non-descending within a document, and > 0 for a hit without payload (google_codec.cpp:42-49)", t, docs[p]);
-                                last_pos = positions[h];
-                        }
-                        nhits += freqs[p];
-                }
-        }
-        EncBufs d;
-        if (np) {
-                HIP_TRY(hipMalloc((void **)&d.docs, np * 4));
-                HIP_TRY(hipMalloc((void **)&d.freqs, np * 4));
-                HIP_TRY(hipMalloc((void **)&d.pos, (nhits + 1) * 2));
-                HIP_TRY(hipMemcpyAsync(d.docs, docs, np * 4, hipMemcpyHostToDevice, dev->stream));
-                HIP_TRY(hipMemcpyAsync(d.freqs, freqs, np * 4, hipMemcpyHostToDevice, dev->stream));
-                if (nhits)
-                        HIP_TRY(hipMemcpyAsync(d.pos, positions, nhits * 2, hipMemcpyHostToDevice, dev->stream));
-                if (nhits && payload_lens) {
-                        HIP_TRY(hipMalloc((void **)&d.plens, nhits));
-                        HIP_TRY(hipMalloc((void **)&d.payloads, nhits * 8));
-                        HIP_TRY(hipMemcpyAsync(d.plens, payload_lens, nhits, hipMemcpyHostToDevice, dev->stream));
-                        HIP_TRY(hipMemcpyAsync(d.payloads, payloads, nhits * 8, hipMemcpyHostToDevice, dev->stream));
-                }
-        }
-        return encode_google_device(dev, d, term_first, nterms, np, nhits, index_out, cap, index_len, terms_out);
-}
-
-// ---- Codecs::Lucene::Encoder (lucene_codec.cpp:163-388) on the device, PFOR128 payload (k_lencode.hpp, lucene_enc_units.hpp)
-// temporaries of the write-side calls: from the device handle's buffer pool, back to it when the call returns (the stream has been synchronised by then)
-namespace {
-struct PoolTmp {
-        tri_dev *dev;
-        std::vector<void *> p;
-        ~PoolTmp() {
-                if (!p.empty())
-                        hipStreamSynchronize(dev->stream); // (an early error return: nothing may still be running on what goes back to the pool)
-                for (void *q : p)
-                        pool_free(dev, q);
-        }
-        hipError_t get(void **out, size_t bytes) {
-                const hipError_t e = pool_alloc(dev, out, bytes ? bytes : 8);
-                if (e == hipSuccess)
-                        p.push_back(*out);
-                return e;
-        }
-};
-} // namespace
-
-// the device side of the Lucene-shaped encoder: d_docs / d_freqs / d_pos hold np postings and nhits hits, term after term as term_first (host) says
-static int encode_lucene_device(tri_dev *dev, const uint32_t *d_docs, const uint32_t *d_freqs, const uint16_t *d_pos, const uint64_t np, const uint64_t nhits, const uint64_t *term_first,
-                                const size_t nterms, uint8_t *index_out, const size_t index_cap, size_t *index_len, uint8_t *hits_out, const size_t hits_cap, size_t *hits_len,
-                                tri_term *terms_out) {
-        PoolTmp tmp{dev}; // (the large temporaries come from the device handle's pool: a sizing call and the call that follows it use the same ones)
-        EncBufs scratch; // (enc_scan's chunk sums)
-        uint32_t *d_hdelta, *d_dcnt, *d_hcnt, *d_dsize, *d_hsize, *d_tail_d, *d_tail_h, *d_isize, *d_hsz;
-        uint64_t *d_hit_off, *d_term_first, *d_dblk_first, *d_hblk_first, *d_doff, *d_hoff, *d_term_off, *d_hterm_off;
-        HIP_TRY(tmp.get((void **)&d_hdelta, (nhits + 1) * 4));
-        HIP_TRY(tmp.get((void **)&d_hit_off, (np + 2) * 8));
-        HIP_TRY(tmp.get((void **)&d_term_first, (nterms + 1) * 8));
-        HIP_TRY(tmp.get((void **)&d_dcnt, (nterms + 1) * 4));
-        HIP_TRY(tmp.get((void **)&d_hcnt, (nterms + 1) * 4));
-        HIP_TRY(tmp.get((void **)&d_dblk_first, (nterms + 2) * 8));
-        HIP_TRY(tmp.get((void **)&d_hblk_first, (nterms + 2) * 8));
-        HIP_TRY(tmp.get((void **)&d_tail_d, (nterms + 1) * 4));
-        HIP_TRY(tmp.get((void **)&d_tail_h, (nterms + 1) * 4));
-        HIP_TRY(tmp.get((void **)&d_isize, (nterms + 1) * 4));
-        HIP_TRY(tmp.get((void **)&d_hsz, (nterms + 1) * 4));
-        HIP_TRY(tmp.get((void **)&d_term_off, (nterms + 2) * 8));
-        HIP_TRY(tmp.get((void **)&d_hterm_off, (nterms + 2) * 8));
-        HIP_TRY(hipMemcpyAsync(d_term_first, term_first, (nterms + 1) * 8, hipMemcpyHostToDevice, dev->stream));
-        int rcs;
-        if ((rcs = enc_scan(dev, scratch, d_freqs, d_hit_off, np)))
-                return rcs;
-        const dim3 block(256);
-        auto grid = [](uint64_t n) { return dim3((uint32_t)std::max<uint64_t>(1, (n + 255) / 256)); };
-        LencArgs a{d_docs, d_freqs, d_pos, d_hit_off, d_term_first, d_hdelta, d_dblk_first, d_hblk_first, (uint64_t)nterms};
-        hipLaunchKernelGGL(k_lenc_hdelta, grid(np), block, 0, dev->stream, a, d_hdelta, np);
-        hipLaunchKernelGGL(k_lenc_term_counts, grid(nterms), block, 0, dev->stream, (const uint64_t *)d_term_first, (const uint64_t *)d_hit_off, (uint64_t)nterms, d_dcnt, d_hcnt);
-        if ((rcs = enc_scan(dev, scratch, d_dcnt, d_dblk_first, nterms)) || (rcs = enc_scan(dev, scratch, d_hcnt, d_hblk_first, nterms)))
-                return rcs;
-        uint64_t nd = 0, nh = 0;
-        HIP_TRY(hipMemcpyAsync(&nd, d_dblk_first + nterms, 8, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipMemcpyAsync(&nh, d_hblk_first + nterms, 8, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipStreamSynchronize(dev->stream));
-        HIP_TRY(tmp.get((void **)&d_dsize, (nd + 1) * 4));
-        HIP_TRY(tmp.get((void **)&d_hsize, (nh + 1) * 4));
-        HIP_TRY(tmp.get((void **)&d_doff, (nd + 2) * 8));
-        HIP_TRY(tmp.get((void **)&d_hoff, (nh + 2) * 8));
-        hipLaunchKernelGGL(k_lenc_dblk_size, grid(nd), block, 0, dev->stream, a, nd, d_dsize);
-        hipLaunchKernelGGL(k_lenc_hblk_size, grid(nh), block, 0, dev->stream, a, nh, d_hsize);
-        hipLaunchKernelGGL(k_lenc_tail_size, grid(nterms), block, 0, dev->stream, a, d_tail_d, d_tail_h);
-        if ((rcs = enc_scan(dev, scratch, d_dsize, d_doff, nd)) || (rcs = enc_scan(dev, scratch, d_hsize, d_hoff, nh)))
-                return rcs;
-        LencPlace pl{d_doff, d_hoff, d_term_off, d_hterm_off, d_tail_d, d_tail_h};
-        hipLaunchKernelGGL(k_lenc_term_sizes, grid(nterms), block, 0, dev->stream, a, pl, d_isize, d_hsz);
-        if ((rcs = enc_scan(dev, scratch, d_isize, d_term_off, nterms)) || (rcs = enc_scan(dev, scratch, d_hsz, d_hterm_off, nterms)))
-                return rcs;
-        HIP_TRY(hipGetLastError());
-        std::vector<uint64_t> term_off(nterms + 1), hterm_off(nterms + 1);
-        HIP_TRY(hipMemcpyAsync(term_off.data(), d_term_off, (nterms + 1) * 8, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipMemcpyAsync(hterm_off.data(), d_hterm_off, (nterms + 1) * 8, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipStreamSynchronize(dev->stream));
-        if (term_off[nterms] > 0xffffffffull || hterm_off[nterms] > 0xffffffffull)
-                return fail(TRI_ERR_UNSUPPORTED, "the index or hits.data would exceed 4 GiB (term_index_ctx offsets and the term header's hits offset are 32 bits)");
-        for (size_t t = 0; t < nterms; ++t)
-                terms_out[t] = {(uint32_t)(term_first[t + 1] - term_first[t]), (uint32_t)term_off[t], (uint32_t)(term_off[t + 1] - term_off[t])};
-        *index_len = (size_t)term_off[nterms];
-        *hits_len = (size_t)hterm_off[nterms];
-        if (!index_out)
-                return TRI_OK; // (sizing call)
-        if (index_cap < *index_len || hits_cap < *hits_len || (*hits_len && !hits_out))
-                return fail(TRI_ERR_INVALID, "tri_encode_lucene: the index needs %zu bytes (%zu given), hits.data %zu (%zu given)", *index_len, index_cap, *hits_len, hits_cap);
-        uint8_t *d_index, *d_hits;
-        HIP_TRY(tmp.get((void **)&d_index, *index_len + 8));
-        HIP_TRY(tmp.get((void **)&d_hits, *hits_len + 8));
-        hipLaunchKernelGGL(k_lenc_dblk_write, grid(nd), block, 0, dev->stream, a, pl, nd, d_index);
-        hipLaunchKernelGGL(k_lenc_hblk_write, grid(nh), block, 0, dev->stream, a, pl, nh, d_hits);
-        hipLaunchKernelGGL(k_lenc_term_write, grid(nterms), block, 0, dev->stream, a, pl, d_index, d_hits);
-        HIP_TRY(hipGetLastError());
-        if (*index_len)
-                HIP_TRY(hipMemcpyAsync(index_out, d_index, *index_len, hipMemcpyDeviceToHost, dev->stream));
-        if (*hits_len)
-                HIP_TRY(hipMemcpyAsync(hits_out, d_hits, *hits_len, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipStreamSynchronize(dev->stream));
-        return TRI_OK;
-}
-
-extern "C" int tri_encode_lucene(tri_dev *dev, const uint32_t *docs, const uint32_t *freqs, const uint16_t *positions, size_t npositions, const uint64_t *term_first, size_t nterms,
-                                 uint8_t *index_out, size_t index_cap, size_t *index_len, uint8_t *hits_out, size_t hits_cap, size_t *hits_len, tri_term *terms_out) {
-        if (!dev || !term_first || !index_len || !hits_len || (nterms && !terms_out))
-                return fail(TRI_ERR_INVALID, "tri_encode_lucene: null argument");
-        HIP_TRY(hipSetDevice(dev->device));
-        const uint64_t np = nterms ? term_first[nterms] : 0;
-        if (np && (!docs || !freqs))
-                return fail(TRI_ERR_INVALID, "tri_encode_lucene: null postings");
-        if (npositions && !positions)
-                return fail(TRI_ERR_INVALID, "tri_encode_lucene: null positions");
-        // ---- host: what the encoder would refuse (lucene_encoder.hpp: documents > 0 and ascending within a term; a hit at position 0 is not a hit — refused
-        //      here, as by tri_encode_google, rather than dropped silently; positions non-descending within a document)
-        uint64_t nhits = 0;
-        for (size_t t = 0; t < nterms; ++t) {
-                if (term_first[t + 1] < term_first[t])
-                        return fail(TRI_ERR_INVALID, "tri_encode_lucene: term_first must ascend");
-                uint32_t prev = 0;
-                for (uint64_t p = term_first[t]; p < term_first[t + 1]; ++p) {
-                        if (!docs[p] || docs[p] <= prev)
-                                return fail(TRI_ERR_INVALID, "term %zu: document IDs must be > 0 and strictly ascending (codecs.h:188-190)", t);
-                        prev = docs[p];
-                        if ((uint64_t)freqs[p] > npositions - std::min<uint64_t>(npositions, nhits))
-                                return fail(TRI_ERR_INVALID, "term %zu, document %u: freqs[] asks for more positions than the %zu given", t, docs[p], npositions);
-                        uint32_t last_pos = 0;
-                        for (uint64_t h = nhits; h < nhits + freqs[p]; ++h) {
-                                if (!positions[h] || positions[h] < last_pos)
-                                        return fail(TRI_ERR_INVALID, "term %zu, document %u: positions must be > 0 and non-descending within a document", t, docs[p]);
-                                last_pos = positions[h];
-                        }
-                        nhits += freqs[p];
-                }
-        }
-        struct Up {
-                uint32_t *docs = nullptr, *freqs = nullptr;
-                uint16_t *pos = nullptr;
-                ~Up() {
-                        hipFree(docs), hipFree(freqs), hipFree(pos);
-                }
-        } u;
-        HIP_TRY(hipMalloc((void **)&u.docs, (np + 1) * 4));
-        HIP_TRY(hipMalloc((void **)&u.freqs, (np + 1) * 4));
-        HIP_TRY(hipMalloc((void **)&u.pos, (nhits + 1) * 2));
-        if (np) {
-                HIP_TRY(hipMemcpyAsync(u.docs, docs, np * 4, hipMemcpyHostToDevice, dev->stream));
-                HIP_TRY(hipMemcpyAsync(u.freqs, freqs, np * 4, hipMemcpyHostToDevice, dev->stream));
-        }
-        if (nhits)
-                HIP_TRY(hipMemcpyAsync(u.pos, positions, nhits * 2, hipMemcpyHostToDevice, dev->stream));
-        return encode_lucene_device(dev, u.docs, u.freqs, u.pos, np, nhits, term_first, nterms, index_out, index_cap, index_len, hits_out, hits_cap, hits_len, terms_out);
-}
-
-// ---- SegmentIndexSession::commit (indexer.cpp:311-478) on the device: sort, gather, encode (k_commit.hpp, commit_sort.hip, k_encode.hpp)
-extern "C" int tri_sort_pairs_u64_u32(const unsigned long long *keys_in, unsigned long long *keys_out, const unsigned *vals_in, unsigned *vals_out, size_t n, void *tmp,
-                                      size_t *tmp_bytes, hipStream_t stream); // (commit_sort.hip)
-
-// (codec: TRI_CODEC_GOOGLE — index_out only —, or TRI_CODEC_LUCENE — index_out + hits_out, payload-less hits)
-static int commit_device(tri_dev *dev, const int codec, const uint32_t *term_ids, const uint32_t *doc_ids, const uint32_t *freqs, const uint16_t *positions, const uint8_t *payload_lens,
-                         const uint64_t *payloads, size_t npostings, size_t npositions, uint8_t *index_out, size_t cap, size_t *index_len, uint8_t *hits_out, size_t hits_cap,
-                         size_t *hits_len, uint32_t *term_ids_out, tri_term *terms_out, size_t terms_cap, size_t *nterms, tri_commit_stats *stats) {
-        if (!dev || !index_len || !nterms || (npostings && (!term_ids || !doc_ids || !freqs)) || (payload_lens && !payloads) || (npositions && !positions))
-                return fail(TRI_ERR_INVALID, "tri_commit_google: null argument");
-        if (npostings > 0xfffffff0ull)
-                return fail(TRI_ERR_UNSUPPORTED, "tri_commit_google: more than 2^32 postings in one session: commit in parts");
-        HIP_TRY(hipSetDevice(dev->device));
-        const uint64_t np = npostings;
-        uint64_t nhits = 0, docs_cnt = 0;
-        for (uint64_t i = 0; i < np; ++i) { // (the session's own bookkeeping: hits in all, documents = runs of one documentID in insertion order)
-                nhits += freqs[i];
-                docs_cnt += i == 0 || doc_ids[i] != doc_ids[i - 1];
-        }
-        if (nhits > npositions)
-                return fail(TRI_ERR_INVALID, "tri_commit_google: freqs[] asks for %llu positions, %zu given", (unsigned long long)nhits, npositions);
-        *nterms = 0;
-        *index_len = 0;
-        if (stats)
-                *stats = tri_commit_stats{docs_cnt, np, nhits, 0};
-        if (!np)
-                return TRI_OK;
-        PoolTmp tmp{dev}; // (the large temporaries come from the device handle's pool: a sizing call and the call that follows it use the same ones)
-        uint32_t *d_terms, *d_docs_in, *d_freqs_in, *d_vals, *d_perm, *d_marks, *d_term_ids;
-        unsigned long long *d_keys, *d_keys_sorted, *d_err;
-        uint16_t *d_pos_in = nullptr;
-        uint8_t *d_plens_in = nullptr;
-        uint64_t *d_payloads_in = nullptr, *d_hit_off_in, *d_hit_off_out, *d_mark_rank, *d_term_first;
-        HIP_TRY(tmp.get((void **)&d_terms, np * 4));
-        HIP_TRY(tmp.get((void **)&d_docs_in, np * 4));
-        HIP_TRY(tmp.get((void **)&d_freqs_in, np * 4));
-        HIP_TRY(tmp.get((void **)&d_keys, np * 8));
-        HIP_TRY(tmp.get((void **)&d_keys_sorted, np * 8));
-        HIP_TRY(tmp.get((void **)&d_vals, np * 4));
-        HIP_TRY(tmp.get((void **)&d_perm, np * 4));
-        HIP_TRY(tmp.get((void **)&d_marks, np * 4));
-        HIP_TRY(tmp.get((void **)&d_hit_off_in, (np + 1) * 8));
-        HIP_TRY(tmp.get((void **)&d_hit_off_out, (np + 1) * 8));
-        HIP_TRY(tmp.get((void **)&d_mark_rank, (np + 1) * 8));
-        HIP_TRY(tmp.get((void **)&d_err, 8));
-        HIP_TRY(hipMemcpyAsync(d_terms, term_ids, np * 4, hipMemcpyHostToDevice, dev->stream));
-        HIP_TRY(hipMemcpyAsync(d_docs_in, doc_ids, np * 4, hipMemcpyHostToDevice, dev->stream));
-        HIP_TRY(hipMemcpyAsync(d_freqs_in, freqs, np * 4, hipMemcpyHostToDevice, dev->stream));
-        if (nhits) {
-                HIP_TRY(tmp.get((void **)&d_pos_in, nhits * 2));
-                HIP_TRY(hipMemcpyAsync(d_pos_in, positions, nhits * 2, hipMemcpyHostToDevice, dev->stream));
-                if (payload_lens) {
-                        HIP_TRY(tmp.get((void **)&d_plens_in, nhits));
-                        HIP_TRY(tmp.get((void **)&d_payloads_in, nhits * 8));
-                        HIP_TRY(hipMemcpyAsync(d_plens_in, payload_lens, nhits, hipMemcpyHostToDevice, dev->stream));
-                        HIP_TRY(hipMemcpyAsync(d_payloads_in, payloads, nhits * 8, hipMemcpyHostToDevice, dev->stream));
-                }
-        }
-        EncBufs d; // (the sorted postings: what the encoder reads)
-        HIP_TRY(hipMalloc((void **)&d.docs, np * 4));
-        HIP_TRY(hipMalloc((void **)&d.freqs, np * 4));
-        HIP_TRY(hipMalloc((void **)&d.pos, (nhits + 1) * 2));
-        if (nhits && payload_lens) {
-                HIP_TRY(hipMalloc((void **)&d.plens, nhits));
-                HIP_TRY(hipMalloc((void **)&d.payloads, nhits * 8));
-        }
-        const dim3 grid((uint32_t)((np + 255) / 256)), block(256);
-        // ---- keys in the order the reference's commit walks (bucket = termID & 31, then termID, then documentID), sorted with the postings' indices
-        hipLaunchKernelGGL(k_commit_keys, grid, block, 0, dev->stream, (const uint32_t *)d_terms, (const uint32_t *)d_docs_in, d_keys, d_vals, np);
-        size_t sort_bytes = 0;
-        HIP_TRY((hipError_t)tri_sort_pairs_u64_u32(d_keys, d_keys_sorted, d_vals, d_perm, np, nullptr, &sort_bytes, dev->stream));
-        void *d_sort_tmp = nullptr;
-        HIP_TRY(tmp.get(&d_sort_tmp, sort_bytes));
-        HIP_TRY((hipError_t)tri_sort_pairs_u64_u32(d_keys, d_keys_sorted, d_vals, d_perm, np, d_sort_tmp, &sort_bytes, dev->stream));
-        // ---- documents and frequencies in sorted order; the hits follow their postings
-        hipLaunchKernelGGL(k_commit_gather, grid, block, 0, dev->stream, (const unsigned long long *)d_keys_sorted, (const uint32_t *)d_perm, (const uint32_t *)d_freqs_in, d.docs,
-                           d.freqs, d_marks, np);
-        int rcs;
-        EncBufs scan_scratch; // (enc_scan's chunk sums)
-        if ((rcs = enc_scan(dev, scan_scratch, d_freqs_in, d_hit_off_in, np)) || (rcs = enc_scan(dev, scan_scratch, d.freqs, d_hit_off_out, np)) ||
-            (rcs = enc_scan(dev, scan_scratch, d_marks, d_mark_rank, np)))
-                return rcs;
-        hipLaunchKernelGGL(k_commit_hits, grid, block, 0, dev->stream, (const uint32_t *)d_perm, (const uint64_t *)d_hit_off_in, (const uint64_t *)d_hit_off_out,
-                           (const uint32_t *)d.freqs, (const uint16_t *)d_pos_in, d.pos, (const uint8_t *)d_plens_in, d.plens, (const uint64_t *)d_payloads_in, d.payloads, np);
-        HIP_TRY(hipMemsetAsync(d_err, 0xff, 8, dev->stream));
-        hipLaunchKernelGGL(k_commit_validate, grid, block, 0, dev->stream, (const unsigned long long *)d_keys_sorted, (const uint32_t *)d.freqs, (const uint64_t *)d_hit_off_out,
-                           (const uint16_t *)d.pos, (const uint8_t *)d.plens, np, d_err);
-        HIP_TRY(hipGetLastError());
-        unsigned long long err = 0;
-        uint64_t nt = 0;
-        HIP_TRY(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipMemcpyAsync(&nt, d_mark_rank + np, 8, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipStreamSynchronize(dev->stream));
-        if (err != ~0ull) {
-                static const char *const why[] = {"", "document 0", "the same (term, document) twice (indexer.cpp:446: documentID > prevDID)",
-                                                  "positions must be non-descending within a document, and > 0 for a hit without payload (google_codec.cpp:42-49)",
-                                                  "a payload of more than 8 bytes (google_codec.cpp:46)"};
-                return fail(TRI_ERR_INVALID, "tri_commit_google: sorted posting %llu: %s", (unsigned long long)(err >> 8) - 1, why[std::min<unsigned long long>(err & 0xff, 4)]);
-        }
-        *nterms = (size_t)nt;
-        if (stats)
-                stats->total_terms = nt;
-        // ---- the distinct terms: first postings and termIDs, commit order
-        HIP_TRY(tmp.get((void **)&d_term_first, (nt + 1) * 8));
-        HIP_TRY(tmp.get((void **)&d_term_ids, nt * 4));
-        hipLaunchKernelGGL(k_commit_terms, grid, block, 0, dev->stream, (const unsigned long long *)d_keys_sorted, (const uint32_t *)d_marks, (const uint64_t *)d_mark_rank, d_term_first,
-                           d_term_ids, np);
-        HIP_TRY(hipGetLastError());
-        std::vector<uint64_t> term_first(nt + 1);
-        std::vector<uint32_t> tids(nt);
-        HIP_TRY(hipMemcpyAsync(term_first.data(), d_term_first, nt * 8, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipMemcpyAsync(tids.data(), d_term_ids, nt * 4, hipMemcpyDeviceToHost, dev->stream));
-        HIP_TRY(hipStreamSynchronize(dev->stream));
-        term_first[nt] = np;
-        std::vector<tri_term> tt(nt);
-        uint8_t *const io = index_out && terms_cap >= nt ? index_out : nullptr;
-        if (codec == TRI_CODEC_LUCENE) {
-                if (int rc = encode_lucene_device(dev, d.docs, d.freqs, d.pos, np, nhits, term_first.data(), nt, io, cap, index_len, hits_out, hits_cap, hits_len, tt.data()))
-                        return rc;
-        } else if (int rc = encode_google_device(dev, d, term_first.data(), nt, np, nhits, io, cap, index_len, tt.data()))
-                return rc;
-        if (!index_out)
-                return TRI_OK; // (sizing call: *index_len and *nterms)
-        if (terms_cap < nt || !terms_out || !term_ids_out)
-                return fail(TRI_ERR_INVALID, "tri_commit_google: the session holds %llu distinct terms, room for %zu given", (unsigned long long)nt, terms_cap);
-        memcpy(terms_out, tt.data(), nt * sizeof(tri_term));
-        memcpy(term_ids_out, tids.data(), nt * 4);
-        return TRI_OK;
-}
-
-extern "C" int tri_commit_google(tri_dev *dev, const uint32_t *term_ids, const uint32_t *doc_ids, const uint32_t *freqs, const uint16_t *positions, const uint8_t *payload_lens,
-                                 const uint64_t *payloads, size_t npostings, size_t npositions, uint8_t *index_out, size_t cap, size_t *index_len, uint32_t *term_ids_out,
-                                 tri_term *terms_out, size_t terms_cap, size_t *nterms, tri_commit_stats *stats) {
-        return commit_device(dev, TRI_CODEC_GOOGLE, term_ids, doc_ids, freqs, positions, payload_lens, payloads, npostings, npositions, index_out, cap, index_len, nullptr, 0, nullptr,
-                             term_ids_out, terms_out, terms_cap, nterms, stats);
-}
-extern "C" int tri_commit_lucene(tri_dev *dev, const uint32_t *term_ids, const uint32_t *doc_ids, const uint32_t *freqs, const uint16_t *positions, size_t npostings, size_t npositions,
-                                 uint8_t *index_out, size_t cap, size_t *index_len, uint8_t *hits_out, size_t hits_cap, size_t *hits_len, uint32_t *term_ids_out, tri_term *terms_out,
-                                 size_t terms_cap, size_t *nterms, tri_commit_stats *stats) {
-        if (!hits_len)
-                return fail(TRI_ERR_INVALID, "tri_commit_lucene: null argument");
-        *hits_len = 0;
-        return commit_device(dev, TRI_CODEC_LUCENE, term_ids, doc_ids, freqs, positions, nullptr, nullptr, npostings, npositions, index_out, cap, index_len, hits_out, hits_cap, hits_len,
-                             term_ids_out, terms_out, terms_cap, nterms, stats);
-}
-
-// ---- Codecs::Google::IndexSession::merge (google_codec.cpp:186-438) for a whole dictionary, on the device (k_commit.hpp)
-// The codecs' merge for a whole dictionary (Codecs::Google::IndexSession::merge, google_codec.cpp:186-438; Codecs::Lucene::IndexSession::merge, lucene_codec.cpp:963-1396 — the
-// same k-way walk over the participants' postings, most recent first, the winner kept unless its participant masks it; the codecs differ in how postings and hits are stored,
-// i.e. in the decode and the encode at the two ends of the sort below)
-static int merge_device(tri_dev *dev, const int codec, tri_index *const *parts, size_t nparts, const uint32_t *part_terms, size_t nterms, uint8_t *index_out, size_t cap, size_t *index_len,
-                        uint8_t *hits_out, size_t hits_cap, size_t *hits_len, tri_term *terms_out, tri_commit_stats *stats) {
-        if (!dev || !parts || !nparts || (nterms && (!part_terms || !terms_out)) || !index_len)
-                return fail(TRI_ERR_INVALID, "tri_merge_%s: null argument", codec == TRI_CODEC_GOOGLE ? "google" : "lucene");
-        if (nparts > 65535)
-                return fail(TRI_ERR_INVALID, "tri_merge_%s: at most 65535 participants (google_codec.cpp:186 / lucene_codec.cpp:963: uint16_t participantsCnt)", codec == TRI_CODEC_GOOGLE ? "google" : "lucene");
-        HIP_TRY(hipSetDevice(dev->device));
-        for (size_t p = 0; p < nparts; ++p) {
-                if (!parts[p] || parts[p]->dev != dev || parts[p]->codec != codec)
-                        return fail(TRI_ERR_INVALID, "tri_merge_%s: participant %zu is not a %s index of this device", codec == TRI_CODEC_GOOGLE ? "google" : "lucene", p, codec == TRI_CODEC_GOOGLE ? "google_codec" : "lucene_codec");
-                if (codec == TRI_CODEC_LUCENE && !parts[p]->d_hits && parts[p]->info.postings)
-                        return fail(TRI_ERR_INVALID, "tri_merge_lucene: participant %zu was uploaded without its hits.data (the merged segment needs every hit)", p);
-        }
-        // ---- the jobs: every (participant, output term) that holds postings, participant-major — the most recent participant's postings first, so that
-        //      a stable sort leaves them first among equal (term, document) keys
-        std::vector<std::vector<MergeJob>> jobs(nparts);
-        std::vector<uint64_t> part_first(nparts + 1, 0);
-        uint64_t np = 0;
-        for (size_t p = 0; p < nparts; ++p) {
-                part_first[p] = np;
-                for (size_t t = 0; t < nterms; ++t) {
-                        const uint32_t idx = part_terms[t * nparts + p];
-                        if (idx == 0xffffffffu)
-                                continue;
-                        if (idx >= parts[p]->terms.size())
-                                return fail(TRI_ERR_INVALID, "tri_merge_google: output term %zu: term %u out of range in participant %zu", t, idx, p);
-                        const DevTerm &dt = parts[p]->terms[idx];
-                        if (!dt.documents)
-                                continue; // (merge.cpp:263-270: a participant without documents for the term takes no part)
-                        if (!(dt.flags & TERM_FULL_BLOCKS))
-                                return fail(TRI_ERR_UNSUPPORTED, "tri_merge_google: term %u of participant %zu has short blocks inside its list (not written by the reference's encoder)", idx, p);
-                        jobs[p].push_back({idx, (uint32_t)t, np});
-                        np += dt.documents;
-                }
-        }
-        part_first[nparts] = np;
-        if (np > 0xfffffff0ull)
-                return fail(TRI_ERR_UNSUPPORTED, "tri_merge_google: more than 2^32 postings: merge in parts");
-        *index_len = 0;
-        if (stats)
-                *stats = tri_commit_stats{0, 0, 0, 0};
-        PoolTmp tmp{dev}; // (the large temporaries come from the device handle's pool: a sizing call and the call that follows it use the same ones)
-        EncBufs d;       // the merged postings: what the encoder reads
-        EncBufs scratch; // (enc_scan's chunk sums)
-        std::vector<uint64_t> term_first(nterms + 1, 0);
-        uint64_t kept = 0, nh_out = 0;
-        if (np) {
-                unsigned long long *d_keys, *d_keys_sorted;
-                uint32_t *d_vals, *d_perm, *d_freqs_all, *d_keep, *d_src_of, *d_term_cnt;
-                uint64_t *d_hit_off_all, *d_rank, *d_part_first, *d_hit_off_out, *d_term_first;
-                const uint32_t **d_masked;
-                HIP_TRY(tmp.get((void **)&d_keys, np * 8));
-                HIP_TRY(tmp.get((void **)&d_keys_sorted, np * 8));
-                HIP_TRY(tmp.get((void **)&d_vals, np * 4));
-                HIP_TRY(tmp.get((void **)&d_perm, np * 4));
-                HIP_TRY(tmp.get((void **)&d_freqs_all, np * 4));
-                HIP_TRY(tmp.get((void **)&d_keep, np * 4));
-                HIP_TRY(tmp.get((void **)&d_hit_off_all, (np + 1) * 8));
-                HIP_TRY(tmp.get((void **)&d_rank, (np + 1) * 8));
-                HIP_TRY(tmp.get((void **)&d_part_first, (nparts + 1) * 8));
-                HIP_TRY(tmp.get((void **)&d_masked, nparts * sizeof(void *)));
-                HIP_TRY(tmp.get((void **)&d_term_cnt, (nterms + 1) * 4));
-                HIP_TRY(tmp.get((void **)&d_term_first, (nterms + 2) * 8));
-                std::vector<const uint32_t *> masked(nparts);
-                for (size_t p = 0; p < nparts; ++p)
-                        masked[p] = parts[p]->d_masked;
-                HIP_TRY(hipMemcpyAsync(d_part_first, part_first.data(), (nparts + 1) * 8, hipMemcpyHostToDevice, dev->stream));
-                HIP_TRY(hipMemcpyAsync(d_masked, masked.data(), nparts * sizeof(void *), hipMemcpyHostToDevice, dev->stream));
-                std::vector<MergeJob *> d_jobs(nparts, nullptr);
-                for (size_t p = 0; p < nparts; ++p) {
-                        if (jobs[p].empty())
-                                continue;
-                        HIP_TRY(tmp.get((void **)&d_jobs[p], jobs[p].size() * sizeof(MergeJob)));
-                        HIP_TRY(hipMemcpyAsync(d_jobs[p], jobs[p].data(), jobs[p].size() * sizeof(MergeJob), hipMemcpyHostToDevice, dev->stream));
-                        const tri_index *ix = parts[p];
-                        TRI_LAUNCH(k_merge_decode, codec, dim3((uint32_t)std::min<size_t>(jobs[p].size(), (size_t)dev->cus * 16)), dim3(256), dev->stream, ix->d_index,
-                                   ix->d_blk_last, ix->d_blk_off, ix->d_terms, (const MergeJob *)d_jobs[p], (uint32_t)jobs[p].size(), d_freqs_all, d_keys, d_vals);
-                }
-                HIP_TRY(hipGetLastError());
-                int rcs;
-                if ((rcs = enc_scan(dev, scratch, d_freqs_all, d_hit_off_all, np)))
-                        return rcs;
-                uint64_t nh_all = 0;
-                HIP_TRY(hipMemcpyAsync(&nh_all, d_hit_off_all + np, 8, hipMemcpyDeviceToHost, dev->stream));
-                HIP_TRY(hipStreamSynchronize(dev->stream));
-                uint16_t *d_pos_all;
-                uint8_t *d_plens_all;
-                uint64_t *d_payloads_all;
-                HIP_TRY(tmp.get((void **)&d_pos_all, (nh_all + 1) * 2));
-                HIP_TRY(tmp.get((void **)&d_plens_all, nh_all + 1));
-                HIP_TRY(tmp.get((void **)&d_payloads_all, (nh_all + 1) * 8));
-                for (size_t p = 0; p < nparts; ++p) {
-                        if (jobs[p].empty())
-                                continue;
-                        const tri_index *ix = parts[p];
-                        if (codec == TRI_CODEC_LUCENE)
-                                hipLaunchKernelGGL(k_merge_hits_lucene, dim3((uint32_t)std::min<size_t>(jobs[p].size(), (size_t)dev->cus * 16)), dim3(256), 0, dev->stream, ix->d_hits,
-                                                   ix->d_blk_hits, ix->d_hdir, ix->d_terms, (const MergeJob *)d_jobs[p], (uint32_t)jobs[p].size(), (const uint32_t *)d_freqs_all,
-                                                   (const uint64_t *)d_hit_off_all, d_pos_all, d_plens_all, d_payloads_all);
-                        else
-                                hipLaunchKernelGGL(k_merge_hits, dim3((uint32_t)std::min<size_t>(jobs[p].size(), (size_t)dev->cus * 16)), dim3(256), 0, dev->stream, ix->d_index, ix->d_blk_off,
-                                                   ix->d_blk_hits, ix->d_terms, (const MergeJob *)d_jobs[p], (uint32_t)jobs[p].size(), (const uint32_t *)d_freqs_all, (const uint64_t *)d_hit_off_all,
-                                                   d_pos_all, d_plens_all, d_payloads_all);
-                }
-                HIP_TRY(hipGetLastError());
-                // ---- sort by (output term, document); the first of equal keys is the most recent participant's
-                size_t sort_bytes = 0;
-                HIP_TRY((hipError_t)tri_sort_pairs_u64_u32(d_keys, d_keys_sorted, d_vals, d_perm, np, nullptr, &sort_bytes, dev->stream));
-                void *d_sort_tmp = nullptr;
-                HIP_TRY(tmp.get(&d_sort_tmp, sort_bytes));
-                HIP_TRY((hipError_t)tri_sort_pairs_u64_u32(d_keys, d_keys_sorted, d_vals, d_perm, np, d_sort_tmp, &sort_bytes, dev->stream));
-                const dim3 grid((uint32_t)((np + 255) / 256)), block(256);
-                hipLaunchKernelGGL(k_merge_select, grid, block, 0, dev->stream, (const unsigned long long *)d_keys_sorted, (const uint32_t *)d_perm, (const uint64_t *)d_part_first,
-                                   (uint32_t)nparts, (const uint32_t *const *)d_masked, d_keep, np);
-                if ((rcs = enc_scan(dev, scratch, d_keep, d_rank, np)))
-                        return rcs;
-                HIP_TRY(hipMemcpyAsync(&kept, d_rank + np, 8, hipMemcpyDeviceToHost, dev->stream));
-                HIP_TRY(hipStreamSynchronize(dev->stream));
-                HIP_TRY(hipMalloc((void **)&d.docs, (kept + 1) * 4));
-                HIP_TRY(hipMalloc((void **)&d.freqs, (kept + 1) * 4));
-                HIP_TRY(tmp.get((void **)&d_src_of, (kept + 1) * 4));
-                HIP_TRY(tmp.get((void **)&d_hit_off_out, (kept + 2) * 8));
-                HIP_TRY(hipMemsetAsync(d_term_cnt, 0, (nterms + 1) * 4, dev->stream));
-                hipLaunchKernelGGL(k_merge_compact, grid, block, 0, dev->stream, (const unsigned long long *)d_keys_sorted, (const uint32_t *)d_perm, (const uint32_t *)d_keep,
-                                   (const uint64_t *)d_rank, (const uint32_t *)d_freqs_all, d.docs, d.freqs, d_src_of, d_term_cnt, np);
-                if ((rcs = enc_scan(dev, scratch, d.freqs, d_hit_off_out, kept)) || (rcs = enc_scan(dev, scratch, d_term_cnt, d_term_first, nterms)))
-                        return rcs;
-                HIP_TRY(hipMemcpyAsync(&nh_out, d_hit_off_out + kept, 8, hipMemcpyDeviceToHost, dev->stream));
-                HIP_TRY(hipMemcpyAsync(term_first.data(), d_term_first, (nterms + 1) * 8, hipMemcpyDeviceToHost, dev->stream));
-                HIP_TRY(hipStreamSynchronize(dev->stream));
-                HIP_TRY(hipMalloc((void **)&d.pos, (nh_out + 1) * 2));
-                HIP_TRY(hipMalloc((void **)&d.plens, nh_out + 1));
-                HIP_TRY(hipMalloc((void **)&d.payloads, (nh_out + 1) * 8));
-                if (kept)
-                        hipLaunchKernelGGL(k_commit_hits, dim3((uint32_t)((kept + 255) / 256)), block, 0, dev->stream, (const uint32_t *)d_src_of, (const uint64_t *)d_hit_off_all,
-                                           (const uint64_t *)d_hit_off_out, (const uint32_t *)d.freqs, (const uint16_t *)d_pos_all, d.pos, (const uint8_t *)d_plens_all, d.plens,
-                                           (const uint64_t *)d_payloads_all, d.payloads, kept);
-                HIP_TRY(hipGetLastError());
-        }
-        if (codec == TRI_CODEC_LUCENE) {
-                if (int rc = encode_lucene_device(dev, d.docs, d.freqs, d.pos, kept, nh_out, term_first.data(), nterms, index_out, cap, index_len, hits_out, hits_cap, hits_len, terms_out))
-                        return rc;
-        } else if (int rc = encode_google_device(dev, d, term_first.data(), nterms, kept, nh_out, index_out, cap, index_len, terms_out))
-                return rc;
-        if (stats) {
-                stats->sum_terms_docs = kept;
-                stats->sum_term_hits = nh_out;
-                for (size_t t = 0; t < nterms; ++t)
-                        stats->total_terms += term_first[t + 1] > term_first[t]; // (merge.cpp:241: a term that keeps no document is dropped from the dictionary)
-        }
-        return TRI_OK;
-}
-extern "C" int tri_merge_google(tri_dev *dev, tri_index *const *parts, size_t nparts, const uint32_t *part_terms, size_t nterms, uint8_t *index_out, size_t cap, size_t *index_len,
-                                tri_term *terms_out, tri_commit_stats *stats) {
-        return merge_device(dev, TRI_CODEC_GOOGLE, parts, nparts, part_terms, nterms, index_out, cap, index_len, nullptr, 0, nullptr, terms_out, stats);
-}
-extern "C" int tri_merge_lucene(tri_dev *dev, tri_index *const *parts, size_t nparts, const uint32_t *part_terms, size_t nterms, uint8_t *index_out, size_t cap, size_t *index_len,
-                                uint8_t *hits_out, size_t hits_cap, size_t *hits_len, tri_term *terms_out, tri_commit_stats *stats) {
-        if (!hits_len)
-                return fail(TRI_ERR_INVALID, "tri_merge_lucene: null argument");
-        *hits_len = 0;
-        return merge_device(dev, TRI_CODEC_LUCENE, parts, nparts, part_terms, nterms, index_out, cap, index_len, hits_out, hits_cap, hits_len, terms_out, stats);
-}
+// the encoders, commit and merge on the device: tri_encode_*, tri_commit_*, tri_merge_* and the scratch they allocate from
+#include "write_side.hpp"
 
 #ifdef TRI_PROF
 // perf-probe builds: read back and reset the per-phase cycle totals (dev_stream.hpp)

@@ -173,6 +173,7 @@ def hip_lib():
     L.tri_commit_lucene.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, C.c_size_t,
                                     C.POINTER(C.c_size_t), vp]
     L.tri_merge_google.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp]
+    L.tri_merge_lucene.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp]
     L.tri_commit_google.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
     L.tri_comm_unique_id.argtypes = [vp]
     L.tri_comm_create.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]
@@ -214,6 +215,27 @@ def host_lib():
 def _check(rc):
     if rc != 0:
         raise TrinityError(f"rc={rc}: {hip_lib().tri_last_error().decode()}")
+
+
+def _size_then_fill(call, lens, nterms=None):
+    """The write side's size-then-fill protocol.  call(out, cap, ...) takes a (byte buffer, capacity) pair per length of `lens` (c_size_t: the index, then
+    hits.data where the codec has one) and, when `nterms` (c_size_t) is given, (termIDs, term table, their capacity) after them.  Called with null outputs it
+    leaves the lengths; the outputs are allocated from those, the call is repeated, and the outputs come back cut to their lengths."""
+    _check(call(*[None, 0] * len(lens), *([None, None, 0] if nterms is not None else [])))
+    bufs = [np.zeros(max(1, n.value), dtype=np.uint8) for n in lens]
+    args = [x for b in bufs for x in (b.ctypes.data, b.size)]
+    outs = [b[: n.value] for b, n in zip(bufs, lens)]
+    if nterms is not None:
+        tids, terms = np.zeros(max(1, nterms.value), dtype=np.uint32), np.zeros((max(1, nterms.value), 3), dtype=np.uint32)
+        args += [tids.ctypes.data, terms.ctypes.data, nterms.value]
+        outs += [tids[: nterms.value], terms[: nterms.value]]
+    _check(call(*args))
+    return outs
+
+
+def _commit_stats(arr):
+    """tri_commit_stats as a dict"""
+    return dict(zip(("docs_cnt", "sum_terms_docs", "sum_term_hits", "total_terms"), (int(x) for x in arr)))
 
 
 def gen_queries(V, seed, nq, nterms):
@@ -318,10 +340,8 @@ class Device:
             assert pl.size == p.size == pv.size
             call = lambda out, cap: L.tri_encode_google_payloads(self.h, d.ctypes.data, f.ctypes.data, p.ctypes.data, pl.ctypes.data, pv.ctypes.data, p.size, tf.ctypes.data, n, out,
                                                                   cap, C.byref(ln), terms.ctypes.data)  # fmt: skip
-        _check(call(None, 0))
-        out = np.zeros(max(1, ln.value), dtype=np.uint8)
-        _check(call(out.ctypes.data, out.size))
-        return out[: ln.value], terms[:n]
+        (out,) = _size_then_fill(call, [ln])
+        return out, terms[:n]
 
     def commit_google(self, term_ids, doc_ids, freqs, positions, payload_lens=None, payloads=None):
         """SegmentIndexSession::commit on the device (tri_commit_google): a session's postings in insertion order -> (index bytes u8[], the committed
@@ -341,12 +361,8 @@ class Device:
             return L.tri_commit_google(self.h, t.ctypes.data, d.ctypes.data, f.ctypes.data, p.ctypes.data, None if pl is None else pl.ctypes.data,
                                        None if pv is None else pv.ctypes.data, t.size, p.size, out, cap, C.byref(ln), tids, terms, tcap, C.byref(nt), stats.ctypes.data)  # fmt: skip
 
-        _check(call(None, 0, None, None, 0))
-        out = np.zeros(max(1, ln.value), dtype=np.uint8)
-        tids = np.zeros(max(1, nt.value), dtype=np.uint32)
-        terms = np.zeros((max(1, nt.value), 3), dtype=np.uint32)
-        _check(call(out.ctypes.data, out.size, tids.ctypes.data, terms.ctypes.data, nt.value))
-        return out[: ln.value], tids[: nt.value], terms[: nt.value], dict(zip(("docs_cnt", "sum_terms_docs", "sum_term_hits", "total_terms"), (int(x) for x in stats)))
+        out, tids, terms = _size_then_fill(call, [ln], nt)
+        return out, tids, terms, _commit_stats(stats)
 
     def commit_lucene(self, term_ids, doc_ids, freqs, positions):
         """tri_commit_lucene: a session's postings in insertion order -> (index bytes, hits.data bytes, committed termIDs, term table, stats)."""
@@ -362,11 +378,8 @@ class Device:
             return L.tri_commit_lucene(self.h, t.ctypes.data, d.ctypes.data, f.ctypes.data, p.ctypes.data, t.size, p.size, io, ic, C.byref(il), ho, hc, C.byref(hl), tids, terms, tcap,
                                        C.byref(nt), stats.ctypes.data)  # fmt: skip
 
-        _check(call(None, 0, None, 0, None, None, 0))
-        io, ho = np.zeros(max(1, il.value), dtype=np.uint8), np.zeros(max(1, hl.value), dtype=np.uint8)
-        tids, terms = np.zeros(max(1, nt.value), dtype=np.uint32), np.zeros((max(1, nt.value), 3), dtype=np.uint32)
-        _check(call(io.ctypes.data, io.size, ho.ctypes.data, ho.size, tids.ctypes.data, terms.ctypes.data, nt.value))
-        return io[: il.value], ho[: hl.value], tids[: nt.value], terms[: nt.value], dict(zip(("docs_cnt", "sum_terms_docs", "sum_term_hits", "total_terms"), (int(x) for x in stats)))
+        io, ho, tids, terms = _size_then_fill(call, [il, hl], nt)
+        return io, ho, tids, terms, _commit_stats(stats)
 
     def encode_lucene(self, docs, freqs, positions, term_first):
         """The Lucene-shaped codec's encoder on the device (tri_encode_lucene, PFOR128 payload): -> (index bytes, hits.data bytes, term table u32[n, 3])."""
@@ -379,10 +392,8 @@ class Device:
         il, hl = C.c_size_t(), C.c_size_t()
         L = hip_lib()
         call = lambda io, ic, ho, hc: L.tri_encode_lucene(self.h, d.ctypes.data, f.ctypes.data, p.ctypes.data, p.size, tf.ctypes.data, n, io, ic, C.byref(il), ho, hc, C.byref(hl), terms.ctypes.data)
-        _check(call(None, 0, None, 0))
-        io, ho = np.zeros(max(1, il.value), dtype=np.uint8), np.zeros(max(1, hl.value), dtype=np.uint8)
-        _check(call(io.ctypes.data, io.size, ho.ctypes.data, ho.size))
-        return io[: il.value], ho[: hl.value], terms[:n]
+        io, ho = _size_then_fill(call, [il, hl])
+        return io, ho, terms[:n]
 
     def merge_google(self, parts, part_terms):
         """Codecs::Google::IndexSession::merge for a whole dictionary (tri_merge_google): parts = uploaded google_codec Index objects, most recent first
@@ -395,10 +406,8 @@ class Device:
         stats = np.zeros(4, dtype=np.uint64)
         L = hip_lib()
         call = lambda out, cap: L.tri_merge_google(self.h, hs, len(parts), pt.ctypes.data, pt.shape[0], out, cap, C.byref(ln), terms.ctypes.data, stats.ctypes.data)
-        _check(call(None, 0))
-        out = np.zeros(max(1, ln.value), dtype=np.uint8)
-        _check(call(out.ctypes.data, out.size))
-        return out[: ln.value], terms[: pt.shape[0]], dict(zip(("docs_cnt", "sum_terms_docs", "sum_term_hits", "total_terms"), (int(x) for x in stats)))
+        (out,) = _size_then_fill(call, [ln])
+        return out, terms[: pt.shape[0]], _commit_stats(stats)
 
     def merge_lucene(self, parts, part_terms):
         """Codecs::Lucene::IndexSession::merge for a whole dictionary (tri_merge_lucene): parts = lucene_codec Index objects uploaded with their hits.data, most recent
@@ -409,13 +418,9 @@ class Device:
         ln, hl = C.c_size_t(), C.c_size_t()
         stats = np.zeros(4, dtype=np.uint64)
         L = hip_lib()
-        L.tri_merge_lucene.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
-                                       C.c_void_p, C.c_void_p]  # fmt: skip
         call = lambda out, cap, hout, hcap: L.tri_merge_lucene(self.h, hs, len(parts), pt.ctypes.data, pt.shape[0], out, cap, C.byref(ln), hout, hcap, C.byref(hl), terms.ctypes.data, stats.ctypes.data)
-        _check(call(None, 0, None, 0))
-        out, hout = np.zeros(max(1, ln.value), dtype=np.uint8), np.zeros(max(1, hl.value), dtype=np.uint8)
-        _check(call(out.ctypes.data, out.size, hout.ctypes.data, hout.size))
-        return out[: ln.value], hout[: hl.value], terms[: pt.shape[0]], dict(zip(("docs_cnt", "sum_terms_docs", "sum_term_hits", "total_terms"), (int(x) for x in stats)))
+        out, hout = _size_then_fill(call, [ln, hl])
+        return out, hout, terms[: pt.shape[0]], _commit_stats(stats)
 
     def close(self):
         if self.h:
