@@ -193,7 +193,7 @@ void *tri_dev_stream(tri_dev *);
  *   "cand_xcd"            1 (default): the candidate-tile kernel's tasks are queued per XCD by the plane row they probe — a row's probes land in ONE 4 MB L2
  *                         (csrc/planner.hpp, "k_and's queues"); 0: the heaviest-first order dealt round the queues.  Results do not depend on it
  *   "probe_max_blocks"    > 0: a conjunction of ONE lead list of at most this many blocks with lists that all have planes runs in k_probe (a wave per
- *                         task, csrc/k_probe.hpp) instead of candidate tiles (default 0: off — measured slower at cfg2, planner.hpp)
+ *                         task, csrc/k_probe.hpp) instead of candidate tiles (default 0: off — measured slower at cfg2, planner_types.hpp)
  *   "overlap"             1: the candidate-tile kernel runs on a second stream beside the window kernels (default 0; measured: no gain, the persistent
  *                         grids do not interleave)
  *   "plan_threads"        host threads tri_batch_create plans large batches with (default 0: up to 16, by the host's cores; 1: the calling thread

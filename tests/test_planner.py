@@ -1,4 +1,4 @@
-"""The host planner behind tri_batch_create (csrc/planner.hpp) on a CPU-only machine, through libtrinity_host.so (csrc/host/plan_host.cpp):
+"""The host planner behind tri_batch_create (csrc/planner.hpp and its planner_*.hpp) on a CPU-only machine, through libtrinity_host.so (csrc/host/plan_host.cpp):
 what every kernel relies on without checking — a query's tasks are consecutive and cover its windows / tiles exactly once, output regions
 never overlap and stay inside the batch's capacity, the schedule is a permutation grouped by kernel with the heavier tasks first, every
 term position that names a plane row names the right term — and that the plan does not depend on how many host threads made it."""
@@ -8,6 +8,8 @@ import pytest
 import trinity_amd as T
 from trinity_amd import hostplan as HP
 from trinity_amd import workloads as W
+
+from random_programs import random_program
 
 
 @pytest.fixture(scope="module")
@@ -23,8 +25,23 @@ OPTION_SETS = ({}, {"dense_min_postings": 0}, {"planes": 0}, {"plane_div": 1 << 
                {"plane_div": 1 << 30, "plane_max_bytes": 300_000})  # fmt: skip
 
 
+def check_sections(s):
+    """The block's sections as the summary reports them (the order planner_types.hpp declares them in; splane, between plane_terms and sterms, is not
+    reported): offsets ascend, each is 64-byte aligned, a section ends at least 64 bytes before the next begins, the last one inside the block."""
+    sections = [("off_plan", s["n_plan"] * s["sizeof_query"]), ("off_qterms", s["n_qterms"] * 4), ("off_tasks", s["n_tasks"] * s["sizeof_task"]), ("off_sched", s["n_tasks"] * 4),
+                ("off_fused", s["n_fused_maps"] * s["sizeof_fused"]), ("off_qplane", s["n_qplane"] * 4), ("off_plane_terms", s["n_plane_terms"] * 4), ("off_sterms", s["n_sterms"] * 4),
+                ("off_sweights", s["n_sweights"] * 8), ("off_phrases", s["n_phrases"] * s["sizeof_phrase"]), ("off_pterms", s["n_pterms"] * 4), ("off_ptasks", s["n_ptasks"] * 4),
+                ("off_units", s["n_units"] * s["sizeof_unit"]), ("off_unit_sched", s["n_units"] * 4), ("off_cand_q", 9 * 4), ("off_tree", s["n_tree_words"] * 4),
+                ("off_tree_terms", s["n_tree_terms"] * 4), ("off_tree_hidden", s["n_tree_hidden"] * 4)]  # fmt: skip
+    assert s["off_plan"] == 0
+    for (name, size), (nxt, _) in zip(sections, sections[1:] + [("block_bytes", 0)]):
+        assert s[name] % 64 == 0, name
+        assert s[name] + size + (64 if nxt != "block_bytes" else 0) <= s[nxt], (name, nxt)
+
+
 def check_plan(p, nq):
     s = p.s
+    check_sections(s)
     plan, tasks, sched = p.plan, p.tasks, p.sched
     # queries: plan order = query order; every lowered query knows its slot
     # (a hidden phrase query — a phrase leaf of a TASK_TREE query — has a slot and tasks, and no caller query: qid = 0xffffffff)
@@ -248,7 +265,7 @@ def test_plane_set_tasks_name_a_row_for_every_term(world):
 
 
 def test_recycled_fragments_plan_the_same(world):
-    """tri_dev keeps the planner's per-fragment arrays from plan to plan (planner.hpp: Frag::recycle, FragCache).  A plan made on buffers that earlier plans
+    """tri_dev keeps the planner's per-fragment arrays from plan to plan (planner_types.hpp: Frag::recycle, FragCache).  A plan made on buffers that earlier plans
     of OTHER shapes left behind — another workload, the other codec, another thread count — is byte for byte the plan made on fresh ones, with the same
     counters."""
     D, V, segs, hix = world
@@ -274,31 +291,11 @@ def test_random_token_streams_are_planned_or_refused(world):
     D, V, segs, hix = world
     rng = np.random.default_rng(99)
 
-    def random_program(wellformed):
-        if wellformed:  # a random postfix tree over a few terms
-            st, out = 0, []
-            for _ in range(int(rng.integers(1, 14))):
-                if st >= 2 and rng.random() < 0.45:
-                    op = int(rng.choice([T.OP_AND, T.OP_OR, T.OP_NOT, T.OP_OPT, T.OP_SOME]))
-                    n = 2 if op in (T.OP_NOT, T.OP_OPT) else int(rng.integers(2, st + 1))
-                    out.append(T.tok(op, n | ((int(rng.integers(1, n + 1)) << 16) if op == T.OP_SOME else 0)))
-                    st -= n - 1
-                else:
-                    out.append(T.tok(T.OP_TERM, int(rng.integers(0, 40))))
-                    st += 1
-            if st > 1:
-                out.append(T.tok(T.OP_AND, st))
-            return np.array(out, dtype=np.uint32)
-        n = int(rng.integers(1, 12))
-        ops = rng.integers(0, 8, size=n)  # (7: not an operator at all)
-        args = np.where(rng.random(n) < 0.7, rng.integers(0, 6, size=n), rng.integers(0, 1 << 28, size=n))
-        return ((ops.astype(np.uint32) << 28) | args.astype(np.uint32)).astype(np.uint32)
-
     planned = refused = 0
     for flags, topk in ((T.FLAG_DOCUMENTS_ONLY, 0), (T.FLAG_ACCUMULATED_SCORE, 10), (T.FLAG_MATCHED_TERMS, 0)):
         for round_ in range(60):
             wellformed = round_ % 3 == 0
-            progs = [random_program(wellformed) for _ in range(int(rng.integers(1, 40)))]
+            progs = [random_program(rng, wellformed) for _ in range(int(rng.integers(1, 40)))]
             try:
                 p = HP.HostPlan(hix[1 + (round_ & 1)], progs, flags, topk, threads=1 + 3 * (round_ & 1))
             except T.TrinityError as e:

@@ -1,4 +1,4 @@
-// plan_host.cpp — the host planner (csrc/planner.hpp) and the upload-time walk (csrc/index_host.hpp) behind plain C entry points
+// plan_host.cpp — the host planner (csrc/planner.hpp and its planner_*.hpp) and the upload-time walk (csrc/index_host.hpp) behind plain C entry points
 // of libtrinity_host.so, WITHOUT a device: what tests/test_planner.py checks on a CPU-only machine (plan invariants, the same plan
 // whatever the thread count) and tools/plan_probe.py times.  The product library (libtrinity_hip.so) includes the same two headers;
 // nothing here is part of the C-ABI of include/trinity_hip.h.  New code, no reference source.
@@ -105,14 +105,14 @@ void tri_host_plan_free(void *p) { delete static_cast<HostPlan *>(p); }
 void tri_host_plan_summary(void *p, uint64_t *out /* [65] */, double *ms /* [4] */) {
         const BatchPlan &P = static_cast<HostPlan *>(p)->P;
         const uint64_t v[] = {P.block_bytes,       P.plan.size(),    P.qterms.size(),      P.tasks.size(),  P.fused.size(),       P.qplane.size(),    P.plane_terms.size(), P.sterms.size(),
-                              P.sweights.size(),   P.phrases.size(), P.pterms.size(),      P.ptasks.size(), P.off_plan,           P.off_qterms,       P.off_tasks,          P.off_sched,
-                              P.off_fused,         P.off_qplane,     P.off_plane_terms,    P.off_sterms,    P.off_sweights,       P.off_phrases,      P.off_pterms,         P.off_ptasks,
+                              P.sweights.size(),   P.phrases.size(), P.pterms.size(),      P.ptasks.size(), P.plan.off,           P.qterms.off,       P.tasks.off,          P.sched.off,
+                              P.fused.off,         P.qplane.off,     P.plane_terms.off,    P.sterms.off,    P.sweights.off,       P.phrases.off,      P.pterms.off,         P.ptasks.off,
                               P.n_dense,           P.n_cand,         P.n_fused,            P.n_fused16,     P.n_fusedgen,         P.n_planes,         P.n_planes8,          P.plw,
                               P.sparse_cap,        P.out_capacity,   P.term_bytes,         P.term_bytes_dense, P.dense_queries,   P.cand_queries,     P.fused_queries,      P.planes_queries,
                               P.unsupported_queries, P.rich_R,       sizeof(DevQuery),     sizeof(DevTask), sizeof(DevFused),     sizeof(DevPhrase),  P.cand_needed_term_bytes, P.plane_decoded_bytes,
-                              P.n_pset,            P.pset_queries,   P.n_probe,            P.probe_queries, P.units.size(),       P.off_units,        P.off_pset_sched,     sizeof(DevPsetUnit),
-                              P.n_tree,            P.tree_queries,   P.tree.size(),        P.off_tree,      P.tree_terms.size(),  P.off_tree_terms,   P.tree_hidden.size(), P.off_tree_hidden,
-                              P.off_cand_q};
+                              P.n_pset,            P.pset_queries,   P.n_probe,            P.probe_queries, P.units.size(),       P.units.off,        P.pset_sched.off,     sizeof(DevPsetUnit),
+                              P.n_tree,            P.tree_queries,   P.tree.size(),        P.tree.off,      P.tree_terms.size(),  P.tree_terms.off,   P.tree_hidden.size(), P.tree_hidden.off,
+                              P.cand_q.off};
         static_assert(sizeof v / sizeof v[0] == 65, "summary layout");
         memcpy(out, v, sizeof v);
         if (ms)

@@ -373,13 +373,18 @@ struct tri_batch : BatchPlan {
         size_t nq;
         size_t block_cap = 0;       // size of the pinned host block (BatchPlan::block) as the pool knows it
         uint8_t *d_arena = nullptr; // [copy of block][counts][ticket][qthr][part_counts][task_hits][task_pos_base] [zeroed at creation: qcounts, top_counts, top_docs, top_scores]
-        DevQuery *d_plan = nullptr;
-        DevTask *d_tasks = nullptr;
-        uint32_t *d_sched = nullptr; // task indices, heaviest first: [0, n_dense) TASK_DENSE, then the TASK_CAND ones, then the one-pass kinds
-        uint32_t *d_plane_terms = nullptr, *d_qplane = nullptr, *d_build = nullptr; // d_build: (term, row) pairs of the plane rows a run has to build first // d_qplane: parallel to d_qterms, the term's row or PL_NONE (nullptr: the batch has no planes)
+        // a section of the plan (a Span of BatchPlan: planner_types.hpp, for_each_section) on the device — the block's copy opens the arena
+        template <class T>
+        T *dev_at(const Span<T> &s) const {
+                return reinterpret_cast<T *>(d_arena + s.off);
+        }
+        template <class T>
+        T *dev_opt(const Span<T> &s) const { // ... one that a batch may lack (qplane, splane): nullptr tells the kernels so
+                return s.empty() ? nullptr : dev_at(s);
+        }
+        uint32_t *d_build = nullptr; // (term, row) pairs of the plane rows a run has to build first
         unsigned long long *d_qthr = nullptr; // k_planes: per query, the best k-th score any of its tasks has seen (cleared at every run)
         uint32_t *d_sparse = nullptr;      // k_planes: per resident workgroup, the lists of a task's decoded (non-plane) slots
-        DevFused *d_fused = nullptr;
         hipEvent_t ev[EV_COUNT] = {}; // (owned by the batch: two batches in flight on one device keep their own timings)
         // TASK_TREE (k_tree.hpp): one scratch block — [tree rows: a PL_PLANES-plane row per distinct term leaf][phrase rows: a plane per hidden phrase query]
         // [a match bitmap per tree query][per query and chunk: matches][(term, row) pairs for k_term_planes]
@@ -391,7 +396,6 @@ struct tri_batch : BatchPlan {
         uint32_t scat_cap = 0;
         bool ran = false;
         bool planes_hi = false; // the batch reads the HIGH parts of its plane rows (k_planes, k_score's level words): its run builds them where they are missing
-        uint32_t *d_qterms = nullptr;
         uint32_t *d_out = nullptr;
         uint32_t *d_counts = nullptr; // per task, indexed first_task + i in query order
         uint32_t *d_ticket = nullptr;
@@ -399,8 +403,6 @@ struct tri_batch : BatchPlan {
         uint64_t *d_hashes = nullptr;
         uint64_t *d_qcounts = nullptr; // per caller query: matches of the last run (device copy for the result gather)
         // AccumulatedScoreScheme
-        uint32_t *d_sterms = nullptr;
-        double *d_sweights = nullptr;
         uint32_t *d_part_docs = nullptr, *d_part_counts = nullptr, *d_top_docs = nullptr, *d_top_counts = nullptr;
         double *d_part_scores = nullptr;
         float *d_top_scores = nullptr;
@@ -414,8 +416,6 @@ struct tri_batch : BatchPlan {
         std::vector<uint64_t> h_task_pos_base; // per task; [ntasks] = the pool's size
         size_t rich_pool_cap = 0;
         // phrases
-        DevPhrase *d_phrases = nullptr;
-        uint32_t *d_pterms = nullptr, *d_ptasks = nullptr;
         double *d_pscore = nullptr; // per out[] slot: sum of the phrase scores of the match (scored mode)
         std::vector<uint32_t> h_counts;       // per task
         std::vector<uint64_t> h_query_counts; // per plan slot
@@ -1024,18 +1024,6 @@ extern "C" int tri_batch_create(tri_index *ix, const uint32_t *prog, size_t prog
         const size_t a_top_scores = scored ? carve((nq * topk + 1) * 4) : 0; // the blocks travel whole to the host and to the other ranks)
         HIP_TRY(pool_alloc(dev, (void **)&b->d_arena, a + 256));
         uint8_t *const A = b->d_arena;
-        b->d_plan = (DevQuery *)(A + b->off_plan);
-        b->d_qterms = (uint32_t *)(A + b->off_qterms);
-        b->d_tasks = (DevTask *)(A + b->off_tasks);
-        b->d_sched = (uint32_t *)(A + b->off_sched);
-        b->d_fused = (DevFused *)(A + b->off_fused);
-        b->d_qplane = b->qplane.empty() ? nullptr : (uint32_t *)(A + b->off_qplane);
-        b->d_plane_terms = (uint32_t *)(A + b->off_plane_terms);
-        b->d_sterms = (uint32_t *)(A + b->off_sterms);
-        b->d_sweights = (double *)(A + b->off_sweights);
-        b->d_phrases = (DevPhrase *)(A + b->off_phrases);
-        b->d_pterms = (uint32_t *)(A + b->off_pterms);
-        b->d_ptasks = (uint32_t *)(A + b->off_ptasks);
         b->d_counts = (uint32_t *)(A + a_counts);
         b->d_ticket = (uint32_t *)(A + a_ticket);
         b->d_build = (uint32_t *)(A + a_build);
@@ -1202,8 +1190,8 @@ static int run_matching(tri_batch *b) {
                 HIP_TRY(hipStreamWaitEvent(dev->stream2, dev->ev_fork, 0));
                 cand_stream = dev->stream2;
         }
-        const DevPsetUnit *units = (const DevPsetUnit *)(b->d_arena + b->off_units);
-        const uint32_t *pset_sched = (const uint32_t *)(b->d_arena + b->off_pset_sched);
+        const DevPsetUnit *units = b->dev_at(b->units);
+        const uint32_t *pset_sched = b->dev_at(b->pset_sched);
         // unions with terms that have no plane (PSET_UNIT_SCATTER): those terms' documents listed task by task, a workgroup per query (units[] holds the TASK_PROBE units
         // too) — on the second stream, beside k_and_dense, where that stream is not k_and's (option overlap)
         const bool prep = b->n_pset && b->pscatter_queries, prep_forked = prep && !overlap && b->n_dense;
@@ -1217,7 +1205,7 @@ static int run_matching(tri_batch *b) {
                 hipLaunchKernelGGL(k_psets_prep_list, dim3((nunits + 255) / 256), dim3(256), 0, prep_stream, units, nunits, b->d_ticket + TICKET_SCAT_WORD + 1, b->d_scat_list, nscat);
                 HIP_TRY(hipGetLastError());
                 TRI_LAUNCH(k_psets_prep, ix->codec, dim3(nscat), dim3(PSCAT_WG), prep_stream, units, (const uint32_t *)b->d_scat_list, (const uint32_t *)(b->d_ticket + TICKET_SCAT_WORD + 1),
-                           b->d_plan, b->d_tasks, (const uint32_t *)b->d_qterms, (const uint32_t *)b->d_qplane, ix->d_masked, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
+                           b->dev_at(b->plan), b->dev_at(b->tasks), (const uint32_t *)b->dev_at(b->qterms), (const uint32_t *)b->dev_opt(b->qplane), ix->d_masked, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
                            ix->d_blk_doff, ix->d_terms, b->d_ticket + TICKET_SCAT_WORD, b->d_scat_off, b->d_scat_cnt, b->d_scat_docs, b->scat_cap);
                 HIP_TRY(hipGetLastError());
                 if (prep_forked)
@@ -1225,8 +1213,8 @@ static int run_matching(tri_batch *b) {
         }
         if (b->n_dense) {
                 TRI_LAUNCH(k_and_dense, ix->codec, dim3(std::min<uint32_t>(b->n_dense, (uint32_t)dev->cus * dense_wgs)), dim3(DENSE_WG), dev->stream, match_bytes, ix->d_blk_last,
-                           match_off, ix->d_win, ix->d_terms, b->d_plan, b->d_tasks, b->d_sched + trip::sched_first(*b, TASK_DENSE), b->d_qterms, b->n_dense,
-                           b->d_ticket + TICKET_DENSE_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->d_qplane, (const uint32_t *)ix->d_pcache, b->plw);
+                           match_off, ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->sched) + trip::sched_first(*b, TASK_DENSE), b->dev_at(b->qterms), b->n_dense,
+                           b->d_ticket + TICKET_DENSE_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->dev_opt(b->qplane), (const uint32_t *)ix->d_pcache, b->plw);
                 HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(b->ev[EV_DENSE], dev->stream));
@@ -1236,7 +1224,7 @@ static int run_matching(tri_batch *b) {
                 // the queries all of whose terms have planes: word-wise algebra over the planes + expansion (k_psets.hpp)
                 const uint32_t pset_wgs = TRI_PSET_WAVES * 256 / PSET_WG;
                 TRI_LAUNCH(k_psets, ix->codec, dim3(std::min<uint32_t>(b->n_pset, (uint32_t)dev->cus * (overlap && dev->opt.overlap_dense_wgs ? std::min<uint32_t>(dense_wgs, pset_wgs) : pset_wgs))),
-                           dim3(PSET_WG), dev->stream, units, pset_sched, b->n_pset, b->d_ticket + TICKET_PSET_WORD, (const uint32_t *)b->d_qterms, (const uint32_t *)b->d_qplane, b->d_out,
+                           dim3(PSET_WG), dev->stream, units, pset_sched, b->n_pset, b->d_ticket + TICKET_PSET_WORD, (const uint32_t *)b->dev_at(b->qterms), (const uint32_t *)b->dev_opt(b->qplane), b->d_out,
                            b->d_counts, ix->d_masked, (const uint32_t *)ix->d_pcache, b->plw, (const uint32_t *)b->d_scat_off, (const uint32_t *)b->d_scat_cnt,
                            (const uint32_t *)b->d_scat_docs);
                 HIP_TRY(hipGetLastError());
@@ -1247,14 +1235,14 @@ static int run_matching(tri_batch *b) {
                 // its units run behind k_psets' in pset_sched[]
                 TRI_LAUNCH(k_probe, ix->codec, dim3(std::min<uint32_t>((b->n_probe + PROBE_WG / 64 - 1) / (PROBE_WG / 64), (uint32_t)dev->cus * (TRI_PROBE_WAVES * 256 / PROBE_WG))),
                            dim3(PROBE_WG), dev->stream, match_bytes, ix->d_blk_last, match_off, ix->d_terms, units, pset_sched + b->n_pset, b->n_probe, b->d_ticket + TICKET_PROBE_WORD,
-                           (const uint32_t *)b->d_qterms, (const uint32_t *)b->d_qplane, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)ix->d_pcache, b->plw);
+                           (const uint32_t *)b->dev_at(b->qterms), (const uint32_t *)b->dev_opt(b->qplane), b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)ix->d_pcache, b->plw);
                 HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(b->ev[EV_PROBE], dev->stream));
         if (b->n_cand)
                 TRI_LAUNCH(k_and, ix->codec, dim3(std::min<uint32_t>(b->n_cand, (uint32_t)dev->cus * cand_wgs)), dim3(AND_WG), cand_stream, match_bytes, ix->d_blk_last, match_off,
-                           ix->d_win, ix->d_terms, b->d_plan, b->d_tasks, b->d_sched + trip::sched_first(*b, TASK_CAND), b->d_qterms, (const uint32_t *)(b->d_arena + b->off_cand_q),
-                           b->d_ticket + TICKET_CAND_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->d_qplane, (const uint32_t *)ix->d_pcache, b->plw);
+                           ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->sched) + trip::sched_first(*b, TASK_CAND), b->dev_at(b->qterms), b->dev_at(b->cand_q),
+                           b->d_ticket + TICKET_CAND_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->dev_opt(b->qplane), (const uint32_t *)ix->d_pcache, b->plw);
         HIP_TRY(hipGetLastError());
         if (overlap) {
                 HIP_TRY(hipEventRecord(dev->ev_join, dev->stream2));
@@ -1275,8 +1263,8 @@ static int run_fused(tri_batch *b) {
                         continue;
                 tri_launch(ix->codec, [&](auto c) { return std::array{k_fused<c.value, 0, 0>, k_fused<c.value, 1, 0>, k_fused<c.value, 0, 1>}[variant]; },
                            dim3(std::min<uint32_t>(nf, (uint32_t)dev->cus * FUS_WGS_PER_CU)), dim3(FUS_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
-                           ix->d_blk_doff, ix->d_win, ix->d_terms, b->d_plan, b->d_fused, b->d_tasks, (const uint32_t *)b->d_sched + trip::sched_first(*b, kind), b->d_sterms,
-                           b->d_sweights, nf, b->d_ticket + TICKET_FUSED_WORD + 2 * variant, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, ix->d_masked,
+                           ix->d_blk_doff, ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->fused), b->dev_at(b->tasks), (const uint32_t *)b->dev_at(b->sched) + trip::sched_first(*b, kind), b->dev_at(b->sterms),
+                           b->dev_at(b->sweights), nf, b->d_ticket + TICKET_FUSED_WORD + 2 * variant, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, ix->d_masked,
                            b->similarity, b->d_out, b->d_all_scores, b->d_rich_allow);
                 HIP_TRY(hipGetLastError());
         }
@@ -1298,8 +1286,8 @@ static int run_planes(tri_batch *b) {
                         continue;
                 tri_launch(ix->codec, [&](auto c) { return wide ? k_planes<c.value, FUS_MAX_SLOTS> : k_planes<c.value, PLK_NS_SMALL>; },
                            dim3(std::min<uint32_t>(np, (uint32_t)dev->cus * PLK_WGS_PER_CU)), dim3(PLK_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
-                           ix->d_blk_doff, ix->d_win, ix->d_terms, b->d_plan, b->d_fused, b->d_tasks, (const uint32_t *)b->d_sched + trip::sched_first(*b, kind), b->d_sterms,
-                           b->d_sweights, np, b->d_ticket + TICKET_PLANES_WORD + 2 * wide, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, ix->d_masked,
+                           ix->d_blk_doff, ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->fused), b->dev_at(b->tasks), (const uint32_t *)b->dev_at(b->sched) + trip::sched_first(*b, kind), b->dev_at(b->sterms),
+                           b->dev_at(b->sweights), np, b->d_ticket + TICKET_PLANES_WORD + 2 * wide, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, ix->d_masked,
                            b->similarity, (const uint32_t *)ix->d_pcache, (const uint32_t *)ix->d_pcache_hi, b->plw, ix->pc_cap, b->d_sparse, b->sparse_cap, b->d_qthr);
                 HIP_TRY(hipGetLastError());
         }
@@ -1355,7 +1343,7 @@ static int run_phrases(tri_batch *b) {
         if (!b->ptasks.empty()) {
                 const uint32_t np = (uint32_t)b->ptasks.size();
                 TRI_LAUNCH(k_phrase, ix->codec, dim3(std::min<uint32_t>(np, (uint32_t)dev->cus * PHRASE_WGS_PER_CU)), dim3(AND_WG), dev->stream, ix->d_index, ix->d_hits,
-                           ix->d_blk_hits, ix->d_hdir, ix->d_blk_last, ix->d_blk_off, ix->d_win, ix->d_terms, b->d_plan, b->d_tasks, b->d_ptasks, np, b->d_phrases, b->d_pterms,
+                           ix->d_blk_hits, ix->d_hdir, ix->d_blk_last, ix->d_blk_off, ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->ptasks), np, b->dev_at(b->phrases), b->dev_at(b->pterms),
                            b->d_ticket + TICKET_PHRASE_WORD, b->d_out, b->d_counts, b->d_pscore,
                            (b->flags & TRI_FLAG_ACCUMULATED_SCORE) ? 65535u : 1u, // exec.cpp:296 trackCnt
                            b->similarity, (const uint32_t *)ix->d_pcache, ix->pc_plw, (const uint32_t *)ix->d_prank, (const unsigned long long *)ix->d_phs,
@@ -1374,8 +1362,8 @@ static int run_trees(tri_batch *b) {
         if (b->n_tree) {
                 const uint32_t plw = b->plw, nterms = (uint32_t)b->tree_terms.size(), nhid = (uint32_t)b->tree_hidden.size();
                 const uint32_t nchunks = (plw + TREE_CHUNK_WORDS - 1) / TREE_CHUNK_WORDS;
-                const uint32_t *tsched = b->d_sched + trip::sched_first(*b, TASK_TREE);
-                const uint32_t *d_tree = (const uint32_t *)(b->d_arena + b->off_tree);
+                const uint32_t *tsched = b->dev_at(b->sched) + trip::sched_first(*b, TASK_TREE);
+                const uint32_t *d_tree = b->dev_at(b->tree);
                 for (uint32_t y0 = 0; y0 < nterms; y0 += 65535u) { // (gridDim.y <= 65535)
                         const dim3 grid(plw / PL_WORDS, std::min(65535u, nterms - y0));
                         TRI_LAUNCH(k_term_planes, ix->codec, grid, dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec, ix->d_blk_doff, ix->d_win,
@@ -1385,7 +1373,7 @@ static int run_trees(tri_batch *b) {
                 }
                 if (nhid) {
                         HIP_TRY(hipMemsetAsync(b->d_tree_prows, 0, (size_t)nhid * plw * 4, dev->stream));
-                        hipLaunchKernelGGL(k_tree_gather, dim3(nhid), dim3(TREE_WG), 0, dev->stream, b->d_plan, b->d_tasks, (const uint32_t *)(b->d_arena + b->off_tree_hidden), b->d_out,
+                        hipLaunchKernelGGL(k_tree_gather, dim3(nhid), dim3(TREE_WG), 0, dev->stream, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->tree_hidden), b->d_out,
                                            b->d_counts, b->d_pscore, b->d_tree_prows, plw);
                         HIP_TRY(hipGetLastError());
                 }
@@ -1394,19 +1382,19 @@ static int run_trees(tri_batch *b) {
                 for (uint32_t y0 = 0; y0 < b->n_tree; y0 += 65535u) {
                         const dim3 grid(nchunks, std::min(65535u, b->n_tree - y0));
                         uint32_t *qbits = b->d_tree_qbits + (size_t)y0 * plw, *cc = b->d_tree_cc + (size_t)y0 * nchunks;
-                        hipLaunchKernelGGL(k_tree_eval, grid, dim3(TREE_WG), 0, dev->stream, b->d_plan, b->d_tasks, tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows,
+                        hipLaunchKernelGGL(k_tree_eval, grid, dim3(TREE_WG), 0, dev->stream, b->dev_at(b->plan), b->dev_at(b->tasks), tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows,
                                            (const uint32_t *)b->d_tree_prows, (const uint32_t *)ix->d_masked, qbits, cc, plw);
-                        hipLaunchKernelGGL(k_tree_expand, grid, dim3(TREE_WG), 0, dev->stream, b->d_plan, b->d_tasks, tsched + y0, (const uint32_t *)qbits, (const uint32_t *)cc,
+                        hipLaunchKernelGGL(k_tree_expand, grid, dim3(TREE_WG), 0, dev->stream, b->dev_at(b->plan), b->dev_at(b->tasks), tsched + y0, (const uint32_t *)qbits, (const uint32_t *)cc,
                                            b->d_out, b->d_counts, plw);
                         if (scored_run || rich_run)
-                                TRI_LAUNCH(k_tree_leaves, ix->codec, grid, dim3(TREE_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->d_plan, b->d_tasks,
+                                TRI_LAUNCH(k_tree_leaves, ix->codec, grid, dim3(TREE_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks),
                                            tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows, (const uint32_t *)b->d_tree_prows, (const uint32_t *)cc, (const uint32_t *)b->d_out,
-                                           (const uint32_t *)b->d_counts, (const double *)b->d_sweights, (const double *)b->d_pscore, tscores, rich_run ? b->d_rich_allow : nullptr,
+                                           (const uint32_t *)b->d_counts, (const double *)b->dev_at(b->sweights), (const double *)b->d_pscore, tscores, rich_run ? b->d_rich_allow : nullptr,
                                            plw, b->similarity);
                         HIP_TRY(hipGetLastError());
                 }
                 if (scored_run && b->topk) {
-                        hipLaunchKernelGGL(k_tree_topk, dim3(b->n_tree), dim3(AND_WG), 0, dev->stream, tsched, b->d_tasks, (const uint32_t *)b->d_out, (const uint32_t *)b->d_counts,
+                        hipLaunchKernelGGL(k_tree_topk, dim3(b->n_tree), dim3(AND_WG), 0, dev->stream, tsched, b->dev_at(b->tasks), (const uint32_t *)b->d_out, (const uint32_t *)b->d_counts,
                                            (const double *)tscores, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts);
                         HIP_TRY(hipGetLastError());
                 }
@@ -1423,7 +1411,7 @@ static int launch_rich(tri_batch *b) {
         tri_index *ix = b->ix;
         const uint32_t n = (uint32_t)b->tasks.size();
         tri_launch(ix->codec, [](auto c) { return k_rich<c.value, WRITE>; }, dim3(std::min<uint32_t>(n, (uint32_t)dev->cus * 3)), dim3(AND_WG), dev->stream, ix->d_index,
-                   ix->d_hits, ix->d_blk_hits, ix->d_hdir, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->d_plan, b->d_tasks, b->d_sched, b->d_sterms, n,
+                   ix->d_hits, ix->d_blk_hits, ix->d_hdir, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->sched), b->dev_at(b->sterms), n,
                    b->d_ticket + (WRITE ? TICKET_RICH_WRITE_WORD : TICKET_RICH_COUNT_WORD), b->d_out, b->d_counts, b->rich_R, b->d_rich_present, b->d_rich_freq, b->d_task_hits,
                    WRITE ? (const uint64_t *)b->d_task_pos_base : nullptr, WRITE ? b->d_rich_pool : nullptr, (const uint32_t *)b->d_rich_allow, WRITE ? b->d_rich_plen : nullptr,
                    WRITE ? b->d_rich_payload : nullptr);
@@ -1450,18 +1438,18 @@ static int run_scores(tri_batch *b) {
         tri_index *ix = b->ix;
         const uint32_t nlegacy = trip::sched_first(*b, TASK_FUSED);
         if (nlegacy) {
-                hipLaunchKernelGGL(k_score_order, dim3(1), dim3(SORD_WG), 0, dev->stream, (const uint32_t *)b->d_sched, (const uint32_t *)b->d_counts, nlegacy, b->d_score_order);
+                hipLaunchKernelGGL(k_score_order, dim3(1), dim3(SORD_WG), 0, dev->stream, (const uint32_t *)b->dev_at(b->sched), (const uint32_t *)b->d_counts, nlegacy, b->d_score_order);
                 HIP_TRY(hipGetLastError());
                 TRI_LAUNCH(k_score, ix->codec, dim3(std::min<uint32_t>(nlegacy, (uint32_t)dev->cus * SCORE_WGS_PER_CU)), dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last,
-                           ix->d_blk_off, ix->d_terms, b->d_plan, b->d_tasks, (const uint32_t *)b->d_score_order, b->d_sterms, b->d_sweights, nlegacy,
+                           ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), (const uint32_t *)b->d_score_order, b->dev_at(b->sterms), b->dev_at(b->sweights), nlegacy,
                            b->d_ticket + TICKET_SCORE_WORD, b->d_out, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, b->d_all_scores, b->d_pscore,
-                           b->similarity, ix->d_win, b->splane.empty() ? (const uint32_t *)nullptr : (const uint32_t *)(b->d_arena + b->off_splane),
+                           b->similarity, ix->d_win, b->dev_opt(b->splane),
                            (const uint32_t *)ix->d_pcache_hi, b->plw); // (the scorers read the level words: the rows' high parts)
         }
         HIP_TRY(hipGetLastError());
         const uint32_t nqs = (uint32_t)b->plan.size();
         if (b->topk)
-                hipLaunchKernelGGL(k_topk_merge, dim3(std::min<uint32_t>(nqs, (uint32_t)dev->cus * 8)), dim3(AND_WG), 0, dev->stream, b->d_plan, nqs, b->topk, b->d_part_docs,
+                hipLaunchKernelGGL(k_topk_merge, dim3(std::min<uint32_t>(nqs, (uint32_t)dev->cus * 8)), dim3(AND_WG), 0, dev->stream, b->dev_at(b->plan), nqs, b->topk, b->d_part_docs,
                                    b->d_part_scores, b->d_part_counts, b->d_top_docs, b->d_top_scores, b->d_top_counts);
         HIP_TRY(hipGetLastError());
         return TRI_OK;
@@ -1471,7 +1459,7 @@ static int run_scores(tri_batch *b) {
 static int run_query_counts(tri_batch *b) {
         if (!b->plan.empty()) {
                 const uint32_t nqs = (uint32_t)b->plan.size();
-                hipLaunchKernelGGL(k_query_counts, dim3((nqs + 255) / 256), dim3(256), 0, b->dev->stream, b->d_plan, b->d_counts, nqs, b->d_qcounts);
+                hipLaunchKernelGGL(k_query_counts, dim3((nqs + 255) / 256), dim3(256), 0, b->dev->stream, b->dev_at(b->plan), b->d_counts, nqs, b->d_qcounts);
                 HIP_TRY(hipGetLastError());
         }
         return TRI_OK;
@@ -2055,7 +2043,7 @@ extern "C" int tri_batch_docset_hashes(tri_batch *b, uint64_t *hashes) {
                 if (!b->d_hashes)
                         HIP_TRY(hipMalloc((void **)&b->d_hashes, (size_t)n * 8));
                 DevLock g(dev->mu);
-                hipLaunchKernelGGL(k_hash_docsets, dim3((n + 63) / 64), dim3(64), 0, dev->stream_rb, b->d_plan, b->d_tasks, b->d_counts, n, b->d_out,
+                hipLaunchKernelGGL(k_hash_docsets, dim3((n + 63) / 64), dim3(64), 0, dev->stream_rb, b->dev_at(b->plan), b->dev_at(b->tasks), b->d_counts, n, b->d_out,
                                    b->d_hashes);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipStreamSynchronize(dev->stream_rb));
@@ -2153,7 +2141,7 @@ static int docsets_deliver(tri_batch *b, uint32_t *out, size_t cap, uint64_t *of
                 if (e == hipSuccess)
                         e = hipMemcpyAsync(d_slot_off, slot_off.data(), (nslots + 1) * 8, hipMemcpyHostToDevice, dev->stream_rb); // (pageable source: staged before the call returns)
                 if (e == hipSuccess) {
-                        hipLaunchKernelGGL(k_deliver_docsets, dim3((uint32_t)b->tasks.size()), dim3(256), 0, dev->stream_rb, (const DevQuery *)b->d_plan, (const DevTask *)b->d_tasks,
+                        hipLaunchKernelGGL(k_deliver_docsets, dim3((uint32_t)b->tasks.size()), dim3(256), 0, dev->stream_rb, (const DevQuery *)b->dev_at(b->plan), (const DevTask *)b->dev_at(b->tasks),
                                            (const uint32_t *)b->d_counts, (const uint32_t *)b->d_out, (const uint64_t *)d_slot_off, d_flat, forms ? 1u : 0u);
                         e = hipGetLastError();
                 }
@@ -2249,7 +2237,7 @@ extern "C" int tri_cbatch_create(tri_batch *const *parts, size_t n, tri_cbatch *
                 if ((rc = dev_upload(&d, parts[i]->slot_of_query)))
                         return rc;
                 c->d_slots.push_back(d);
-                src[i] = {parts[i]->d_plan, d, parts[i]->d_part_docs, parts[i]->d_part_scores, parts[i]->d_part_counts, parts[i]->d_qcounts};
+                src[i] = {parts[i]->dev_at(parts[i]->plan), d, parts[i]->d_part_docs, parts[i]->d_part_scores, parts[i]->d_part_counts, parts[i]->d_qcounts};
         }
         int rc;
         if ((rc = dev_upload(&c->d_src, src)))

@@ -1,6 +1,6 @@
 """The host planner without a device (csrc/host/plan_host.cpp in libtrinity_host.so): plans a batch exactly as tri_batch_create does
 and hands back the plan's host block — for the CPU tests of the planner (tests/test_planner.py) and tools/plan_probe.py.  Test and
-probe infrastructure: the product path is tri_batch_create in libtrinity_hip.so, which includes the same planner.hpp."""
+probe infrastructure: the product path is tri_batch_create in libtrinity_hip.so, which includes the same planner.hpp (and its planner_*.hpp)."""
 import ctypes as C
 
 import numpy as np
