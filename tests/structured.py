@@ -476,6 +476,88 @@ def phrase_queries(c):
     return [(c.q(t), 1) for t in out]
 
 
+# ---- a stream of batches over one index (tests/test_gpu_stream.py) ---------------------------------------------------------------------------
+D_STREAM = 2 * SPAN_BITS + 37
+STREAM_STEPS = [2, 3, 5, 7, 11, 17, 29, 47, 79, 113, 157, 199]  # h_i: every STREAM_STEPS[i]-th document and the boundary documents — D / 2 .. D / 199, pairwise distinct
+STREAM_EDGES = [SPAN_BITS - 1, SPAN_BITS, SPAN_BITS + 1, 2 * SPAN_BITS, D_STREAM]
+STREAM_HEADS = [f"h{i}" for i in range(len(STREAM_STEPS))]
+STREAM_PHRASE_HEADS = STREAM_HEADS[:6]  # the terms with written positions: df ranks 0 .. 5
+STREAM_RARE = {"r0": 5, "r1": 37, "r2": 200}  # fewer than D / 1024 documents: no plane under the default plane_div either, df ranks 12 .. 14
+STREAM_PHRASE_STRIDE = 7
+STREAM_PHRASE_SHIFTS = [0, 0, 0, 0, 0, 1, 2, 6]  # (a document's shift for a term: 0 five times in eight)
+
+
+def stream_corpus():
+    """D = 2 SPAN_BITS + 37 (three windows).  Head terms h0 .. h11 of pairwise distinct document frequencies D / 2 .. D / 199 — a plane row is the term's df rank, so
+    h_i's row is i —, each with documents in every window and on SPAN_BITS - 1, SPAN_BITS, SPAN_BITS + 1, 2 SPAN_BITS and D; frequencies FREQ_CYCLE by rank in the list (a row's
+    nested planes and level words differ from its plane 0).  h0 .. h5 carry written positions: hit k of h_i in a document sits at 1 + i + shift + 7 k, shift one of 0 (five
+    times in eight), 1, 2, 6 by a hash of (document, term) — "h_i h_i+1" starts exactly where both shifts agree, and misses by the same position (shift 1 against 0: the later
+    term of the phrase owns it), reversed order (2 against 0) or a gap of 2 (6 against 0); frequencies 0, 5, 6, 7, 13 lie around k_phrase's INLINE_MAX.  Rare terms r0 .. r2 (5,
+    37 and 200 documents) never get a plane."""
+    D = D_STREAM
+    ar = np.arange(1, D + 1, dtype=np.int64)
+    lists, positions = {}, {}
+    for i, (n, step) in enumerate(zip(STREAM_HEADS, STREAM_STEPS)):
+        d = _u32(np.concatenate([ar[ar % step == i % step], STREAM_EDGES]))
+        f = np.array(FREQ_CYCLE, dtype=np.int64)[(np.arange(d.size) + 3 * i) % len(FREQ_CYCLE)]
+        lists[n] = (d, f)
+        if n in STREAM_PHRASE_HEADS:
+            h = ((d.astype(np.uint64) * np.uint64(2654435761) + np.uint64(40503 * (i + 1))) >> np.uint64(13)) & np.uint64(7)
+            first = 1 + i + np.array(STREAM_PHRASE_SHIFTS, dtype=np.int64)[h.astype(np.int64)]
+            ends = np.cumsum(f)
+            k = np.arange(int(ends[-1]), dtype=np.int64) - np.repeat(ends - f, f)
+            positions[n] = (np.repeat(first, f) + STREAM_PHRASE_STRIDE * k).astype(np.uint16)
+    for j, (n, df) in enumerate(STREAM_RARE.items()):
+        d = _u32(STREAM_EDGES) if df == len(STREAM_EDGES) else _u32(np.concatenate([spread(df - len(STREAM_EDGES), D - 3) + 1, STREAM_EDGES]))
+        lists[n] = (d, 1 + (np.arange(d.size) * 5 + j) % 9)
+    c = build(lists, positions=positions)
+    df = c.df()
+    assert c.D == D and np.all(np.diff(df[: len(STREAM_HEADS)]) < 0) and int(df[len(STREAM_HEADS) - 1]) > 1024 > D // 1024 > int(df[len(STREAM_HEADS) :].max()), df
+    return c
+
+
+def _stream_shapes(names):
+    """ANDs, unions and CNFs over the head terms `names` (in df order) and the rare terms: ONE list, from which the docs-only, scored and phrase tables are all derived."""
+    n = len(names)
+    out = []
+    for i in range(n):
+        a, b, c = (f"{{{names[(i + k) % n]}}}" for k in range(3))
+        out += [f"{a} {b}", f"{a} OR {b}", f"{a} ({b} OR {c})"]
+    a, b = f"{{{names[0]}}}", f"{{{names[-1]}}}"
+    out += [f"{a} {{r2}}", f"{b} OR {{r1}}", f"({a} OR {{r0}}) {b}", " OR ".join(f"{{{x}}}" for x in names[:5])]
+    return out
+
+
+def stream_docs_queries(c, names=STREAM_HEADS):
+    """DocumentsOnly: every head term of `names` in an AND, a union and a CNF with its neighbours in df order; head terms with rare ones."""
+    return [(c.q(t), 1) for t in _stream_shapes(list(names))]
+
+
+def stream_scored_queries(c, names=STREAM_HEADS):
+    """The same shapes, scored (run at K = 10 and 256)."""
+    return stream_docs_queries(c, names)
+
+
+def stream_phrase_queries(c, names=STREAM_PHRASE_HEADS):
+    """Phrases over the heads with written positions among `names`: "h_i h_j" of neighbours in df order, "h_i h_j h_k", a phrase and a term, a phrase or a phrase."""
+    ph = [x for x in names if x in STREAM_PHRASE_HEADS]
+    out = []
+    for i in range(len(ph) - 1):
+        out += [f'"{{{ph[i]}}} {{{ph[i + 1]}}}"'] + ([f'"{{{ph[i + 1]}}} {{{ph[i]}}}"'] if i % 2 else [])  # (the reversed order for every other pair: numpy's phrase check is slow)
+    for i in range(len(ph) - 2):
+        out += [f'"{{{ph[i]}}} {{{ph[i + 1]}}} {{{ph[i + 2]}}}"']
+    out += [f'"{{{ph[-2]}}} {{{ph[-1]}}}" {{r2}}']
+    if len(ph) >= 3:
+        out += [f'"{{{ph[1]}}} {{{ph[2]}}}" {{{ph[0]}}}']
+    if len(ph) >= 4:
+        out += [f'"{{{ph[-4]}}} {{{ph[-3]}}}" OR "{{{ph[-2]}}} {{{ph[-1]}}}"']
+    return [(c.q(t), 1) for t in out]
+
+
+def stream_queries(c):
+    return stream_docs_queries(c) + stream_phrase_queries(c)
+
+
 # ---- the scored cases (shared by the CPU file's score-gap condition and the GPU file) --------------------------------------------------------
 MAIN_SCORED_LISTS = ["all", "edges", "lastwin", "holes", "dense_many_slow", "sparse_runs", "df4065", "last1"]
 
@@ -497,9 +579,10 @@ def tall_scored_queries(c):
     return [(c.q(t), 1) for t in [TALL_SCORED, "{beyond} {tall_33}", "{dense_tail3} {tall_odd}", "{gap4_a} OR {gap4_b}", "{tall_edges} OR {gap4_c}", "{beyond}"]]
 
 
-SCORED_CASES = {"freq": (freq_queries, K_VALUES), "main": (main_scored_queries, (10, 256)), "tall": (tall_scored_queries, (10,)), "phrase": (phrase_queries, (10, 256))}
-CORPORA = {"main": main_corpus, "freq": freq_corpus, "tall": tall_corpus, "phrase": phrase_corpus}
-QUERIES = {"main": main_queries, "freq": freq_queries, "tall": tall_queries, "phrase": phrase_queries}
+SCORED_CASES = {"freq": (freq_queries, K_VALUES), "main": (main_scored_queries, (10, 256)), "tall": (tall_scored_queries, (10,)), "phrase": (phrase_queries, (10, 256)),
+                "stream": (stream_queries, (10, 256))}
+CORPORA = {"main": main_corpus, "freq": freq_corpus, "tall": tall_corpus, "phrase": phrase_corpus, "stream": stream_corpus}
+QUERIES = {"main": main_queries, "freq": freq_queries, "tall": tall_queries, "phrase": phrase_queries, "stream": stream_queries}
 
 ALL_PLANES = 1 << 30
 # DocumentsOnly option sets (planner options, tri_dev_set_option) and the task kinds each is meant to put queries of the main corpus on

@@ -2,7 +2,7 @@
 equals the oracle over the encoded bytes, and the oracle decodes the bytes back to the postings), the catalogue reaches the task kinds and the two dense_pass
 branches it claims to, the mirrored geometry constants have not drifted, and the top-K comparison rarely needs its tie-group form.
 
-The score-gap condition, measured on the oracle (test_score_gap_condition prints both): 34 of 804 scored (query, K, similarity) cases, 4.2 %, fall under the
+The score-gap condition, measured on the oracle (test_score_gap_condition prints both): 46 of 912 scored (query, K, similarity) cases, 5.0 %, fall under the
 set-wise rule (bound: 10 %); the smallest relative gap between distinct oracle scores within ranks 1 .. K + 1 is 3.1e-11 (tolerance: 1e-5) — the same addends
 summed in another order."""
 import numpy as np
@@ -156,6 +156,37 @@ def test_routing(corpora, codec):
     hi.close()
     hi = f.host_index(codec)
     plan(f, hi, S.rich_freq_queries(f), T.FLAG_MATCHED_TERMS, 0, {})
+    hi.close()
+    # the stream corpus (tests/test_gpu_stream.py): plane_max_bytes = N rows makes exactly the head terms of df rank < N eligible, and every batch of the docs-only and
+    # scored tables CHOOSES every eligible head term it names — the GPU file's model of the plane cache relies on both; the rare terms never get a plane
+    st = corpora["stream"]
+    hi = st.host_index(codec)
+    heads = S.STREAM_HEADS
+    assert [st.names[t] for t in np.argsort(-st.df(), kind="stable")[: len(heads)]] == heads  # (a term's plane row is its df rank: h_i's is i)
+    plw = ((S.D_STREAM >> 17) + 2) * (S.SPAN_BITS // 32)
+    row_bytes = S.header_constants("dev_structs.hpp")["PL_PLANES"] * plw * 4
+
+    def chosen(queries, flags, topk, opts):
+        p = HP.HostPlan(hi, S.programs(queries), flags, topk, threads=2, options=opts)
+        assert p.s["unsupported_queries"] == 0 and p.s["plw"] == plw, opts
+        for k in KINDS:
+            reached[k] += p.s[k]
+        out = sorted(st.names[t] for t in p.plane_terms.tolist())
+        nptasks = p.s["n_ptasks"]
+        p.close()
+        return out, nptasks
+
+    for n, names in ((2, heads[:2]), (2, heads[:5]), (3, heads[:3]), (4, heads[:4]), (5, heads[:5]), (6, heads[4:6]), (len(heads), heads), (0, heads)):
+        cap = {"plane_div": S.ALL_PLANES, "plane_max_bytes": n * row_bytes} if n else {}
+        want = sorted(x for x in names if heads.index(x) < (n or len(heads)))
+        assert chosen(S.stream_docs_queries(st, names), T.FLAG_DOCUMENTS_ONLY, 0, cap)[0] == want, (n, names)
+        for opts in ({}, {"dense_min_postings": 0}, {"fused": 0, "planes": 3}):
+            for k in (10, 256):
+                assert chosen(S.stream_scored_queries(st, names), T.FLAG_ACCUMULATED_SCORE, k, dict(cap, **opts))[0] == want, (n, names, opts, k)
+    for n, names in ((2, heads[:2]), (len(heads), heads[:6])):
+        for flags in (T.FLAG_DOCUMENTS_ONLY, T.FLAG_ACCUMULATED_SCORE):
+            got, nptasks = chosen(S.stream_phrase_queries(st, names), flags, 10 if flags == T.FLAG_ACCUMULATED_SCORE else 0, {"plane_div": S.ALL_PLANES, "plane_max_bytes": n * row_bytes})
+            assert nptasks > 0 and got and set(got) <= set(names), (n, got)
     hi.close()
     assert all(reached[k] > 0 for k in KINDS), reached
 
