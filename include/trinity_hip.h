@@ -27,7 +27,8 @@ extern "C" {
                              6: tri_batch_info.create_ms / create_plan_ms / *_bound_bytes, options plane_max_bytes / plan_threads, tri_cbatch_query_status;
                              7: TASK_TREE (any query tree), tri_batch_info.tree_ms / tree_queries / tree_scratch_bytes, tri_commit_* / tri_merge_google;
                              8: tri_batch_docsets (every query's docID set in one call), tri_merge_lucene, option planes_rebuild;
-                             9: tri_dev_memory (HBM in use), tri_batch_docsets_mixed (dense sets delivered as bitmap words), two planner contexts per handle (two threads may compile at once), plane rows built by need */
+                             9: tri_dev_memory (HBM in use), tri_batch_docsets_mixed (dense sets delivered as bitmap words), two planner contexts per handle (two threads may compile at once), plane rows built by need;
+                                within 9: tri_filter_create / tri_filter_from_docset / tri_filter_destroy / tri_batch_set_filters (per-query document filters on the device) */
 
 /* status codes */
 #define TRI_OK 0
@@ -233,6 +234,30 @@ int tri_index_term_docbytes(const tri_index *, const uint32_t *terms, size_t n, 
  * matching kernels, so match counts, docsets, scores and top-K of batches run afterwards never contain a masked document.
  * Batches created before the call keep working; the set they see is the one in place when they RUN. */
 int tri_index_set_masked(tri_index *, const uint32_t *docids, size_t n);
+
+/* ---- per-query document filters --------------------------------------------------------------------
+ * exec_query's IndexDocumentsFilter (matches.h:190-201): the application rules documents out BEFORE they are considered — an ACL, a tenant, a category,
+ * a date range expressed as a docID set —, tested in addition to the masked documents (exec.cpp:1133-1150: the match handler hands a document to
+ * consider(), and counts it, only when documentsFilter->filter(id) is false).  On the device a filter is a bitmap over the segment's docIDs, and every query of a
+ * batch may name one: the matching kernels drop, for query q, the documents of the index's masked set as it stands when the batch RUNS and those of q's
+ * filter, at the one place they test the mask today — DocumentsOnly sets, match counts, hashes, scores, top-K lists and the default mode's matched terms
+ * never see a dropped document, so the K slots of a top-K go to documents the application would have kept.
+ *
+ * tri_filter_create: docids in any order, duplicates allowed, n == 0 legal, IDs above the segment's largest document ignored.  mode TRI_FILTER_DROP: docids =
+ * the documents IndexDocumentsFilter::filter() returns true for; TRI_FILTER_KEEP: the only documents a query may match (an allow-list; complemented when the
+ * bitmap is built).  tri_filter_from_docset: the filter is the docID set of query q of a synced DocumentsOnly batch, taken on the device in the form the
+ * engine holds it (docIDs or bitmap); it belongs to the batch's index and outlives the batch.  Both return once the bitmap stands.  A filter is destroyed
+ * before its index, and kept alive while a batch that names it may run — the rule batches follow towards their index.
+ * tri_batch_set_filters: after tri_batch_create, before a run, again between runs; filters[] are stored by reference; filter_of_query[q] < nf names query
+ * q's filter, 0xffffffff none; nf == 0 clears.  A filter of another index or an index >= nf is TRI_ERR_INVALID and changes nothing.  Runs already queued
+ * keep the assignment they were launched with.  The parts of a tri_cbatch each carry their own filters. */
+typedef struct tri_filter tri_filter;
+#define TRI_FILTER_DROP 0 /* docids = the documents IndexDocumentsFilter::filter() returns true for */
+#define TRI_FILTER_KEEP 1 /* docids = the only documents a query may match (allow-list)             */
+int tri_filter_create(tri_index *, const uint32_t *docids, size_t n, int mode, tri_filter **out);
+int tri_filter_from_docset(tri_batch *, size_t q, int mode, tri_filter **out);
+void tri_filter_destroy(tri_filter *);
+int tri_batch_set_filters(tri_batch *, tri_filter *const *filters, size_t nf, const uint32_t *filter_of_query /* [nq], 0xffffffff: none */);
 
 /* ---- postings decode (codec seam) -----------------------------------------------------------------
  * Replaces Codecs::PostingsListIterator::next() driven to exhaustion (google_codec.cpp:777-819,

@@ -2,7 +2,8 @@
 """Every s_barrier of the engine's kernels must be preceded, on EVERY path, by `s_waitcnt lgkmcnt(0)` after the wave's last LDS store / atomic —
 otherwise another wave may read LDS behind the barrier before the store has landed (hazard 1: the compiler left that wait out
 at a barrier reached over a loop's back edge).  Walks the control-flow graph of `hipcc -S --cuda-device-only` output backwards from each barrier.
-    usage: tools/isa_barrier_check.py [file.s]     (without a file: compiles trinity_amd/csrc/trinity_hip.hip to build/isa_check.s first)"""
+    usage: tools/isa_barrier_check.py [file.s]     (without a file: compiles trinity_amd/csrc/trinity_hip.hip and filtered_kernels.hip — the matching kernels
+    of batches with document filters — to build/isa_check.s first)"""
 import os
 import re
 import subprocess
@@ -14,8 +15,14 @@ if len(sys.argv) > 1:
 else:
     os.makedirs(os.path.join(root, "build"), exist_ok=True)
     path = os.path.join(root, "build", "isa_check.s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Wno-unused-value", "-o", path,
-                    os.path.join(root, "trinity_amd", "csrc", "trinity_hip.hip")] + [a for a in os.environ.get("ISA_CHECK_FLAGS", "").split() if a], check=True)  # fmt: skip
+    parts = []
+    for src in ("trinity_hip.hip", "filtered_kernels.hip"):
+        parts.append(path + "." + src)
+        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-Wno-unused-value", "-o", parts[-1],
+                        os.path.join(root, "trinity_amd", "csrc", src)] + [a for a in os.environ.get("ISA_CHECK_FLAGS", "").split() if a], check=True)  # fmt: skip
+    with open(path, "w") as out:  # (labels are looked up per function: one file after the other reads like one)
+        for p in parts:
+            out.write(open(p).read())
 LDS_WRITE = re.compile(r"^ds_(write|or|and|xor|add|sub|min|max|inc|dec|cmpst|wrxchg|append|consume)")
 kernels, cur = {}, None
 for line in open(path):

@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
 """Registers, spills, scratch, LDS and the occupancy the compiler states for every kernel of the engine (no GPU): `hipcc -Rpass-analysis=kernel-resource-usage`
-on trinity_hip.hip, one row per kernel.    usage: tools/kernel_resources.py > profiles/rNN_kernel_resources.txt"""
+on trinity_hip.hip and filtered_kernels.hip (the matching kernels of batches with document filters: namespace filtered), one row per kernel.    usage: tools/kernel_resources.py > profiles/rNN_kernel_resources.txt"""
 import os
 import re
 import subprocess
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.makedirs(os.path.join(root, "build"), exist_ok=True)
-r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-fPIC", "-Wno-unused-value", "-Rpass-analysis=kernel-resource-usage",
-                    os.path.join(root, "trinity_amd", "csrc", "trinity_hip.hip"), "-o", os.path.join(root, "build", "resources.o")], capture_output=True, text=True)  # fmt: skip
+stderr = ""
+for src in ("trinity_hip.hip", "filtered_kernels.hip"):
+    stderr += subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-fPIC", "-Wno-unused-value", "-Rpass-analysis=kernel-resource-usage",
+                              os.path.join(root, "trinity_amd", "csrc", src), "-o", os.path.join(root, "build", "resources.o")], capture_output=True, text=True).stderr  # fmt: skip
 rows, cur = [], None
-for line in r.stderr.splitlines():
+for line in stderr.splitlines():
     m = re.search(r"remark: Function Name: (\S+)", line)
     if m:
         cur = {"name": m.group(1)}

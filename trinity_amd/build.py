@@ -8,7 +8,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB_HIP = os.path.join(PKG, "libtrinity_hip.so")
 LIB_HOST = os.path.join(PKG, "libtrinity_host.so")
-HIP_SRCS = [os.path.join(PKG, "csrc", "trinity_hip.hip"), os.path.join(PKG, "csrc", "commit_sort.hip")]
+HIP_SRCS = [os.path.join(PKG, "csrc", n) for n in ("trinity_hip.hip", "commit_sort.hip", "filtered_kernels.hip")]  # (filtered_kernels.hip: csrc/k_filter.hpp)
 HOST_SRCS = [os.path.join(PKG, "csrc", "host", "synth.cpp"), os.path.join(PKG, "csrc", "host", "plan_host.cpp")]
 
 
@@ -76,8 +76,23 @@ def build_mirror_write_test(force=False):
     return MIRROR_WRITE_BIN
 
 
+MIRROR_FILTER_SRC = os.path.join(ROOT, "tests", "cpp", "host_mirror_filter_test.cpp")
+MIRROR_FILTER_BIN = os.path.join(ROOT, "tests", "cpp", "host_mirror_filter_test")
+
+
+def build_mirror_filter_test(force=False):
+    """exec_query / exec_queries with a DeviceDocumentsFilter (csrc/host/trinity_gpu.hpp) next to the equivalent host filter, compiled into its driver; in-tree,
+    like the other two."""
+    deps = [MIRROR_FILTER_SRC, os.path.join(PKG, "csrc", "host", "trinity_gpu.hpp"), os.path.join(PKG, "csrc", "host", "google_encoder.hpp"), os.path.join(ROOT, "include", "trinity_hip.h")]
+    if force or _newer(MIRROR_FILTER_BIN, deps):
+        build_hip()
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", MIRROR_FILTER_BIN, MIRROR_FILTER_SRC, "-L" + PKG, "-ltrinity_hip", "-Wl,-rpath,$ORIGIN/../../trinity_amd"]
+        subprocess.run(cmd, check=True)
+    return MIRROR_FILTER_BIN
+
+
 def build_all(force=False):
-    return build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force)
+    return build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force)
 
 
 def kernels_stamp():

@@ -393,6 +393,10 @@ namespace trinity_amd {
 
         struct IndexDocumentsFilter { // matches.h:198-201: return true to disregard the document
                 virtual bool filter(const docid_t) = 0;
+                // The filter as a device bitmap (tri_filter), if it has one: exec_query / exec_queries then install it with tri_batch_set_filters and the matching
+                // kernels drop its documents themselves — match counts and the engine's top-K never see them.  nullptr (every plain host filter): filter() is
+                // called per replayed document, as before.
+                virtual tri_filter *device_filter() { return nullptr; }
                 virtual ~IndexDocumentsFilter() = default;
         };
 
@@ -576,6 +580,40 @@ namespace trinity_amd {
                 };
         } // namespace Similarity
 
+        // An IndexDocumentsFilter the DEVICE applies (include/trinity_hip.h, per-query document filters): built once from a docID list — the documents to drop, or
+        // with keep = true the only documents a query may match — or from a predicate evaluated once over the source's documents 1 .. docsCnt
+        // (matches.h:199: true = disregard the document).  It belongs to its source and goes before it.  filter() answers from the same set, for a caller
+        // that still asks on the host.
+        class DeviceDocumentsFilter final : public IndexDocumentsFilter {
+                tri_filter *h{nullptr};
+                std::vector<docid_t> ids; // ascending, distinct
+                bool keep{false};
+
+                void upload(IndexSource *src) {
+                        std::sort(ids.begin(), ids.end());
+                        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+                        check(tri_filter_create(src->handle(), ids.data(), ids.size(), keep ? TRI_FILTER_KEEP : TRI_FILTER_DROP, &h));
+                }
+
+              public:
+                DeviceDocumentsFilter(IndexSource *src, std::vector<docid_t> docids, const bool keepOnly = false)
+                    : ids(std::move(docids)), keep{keepOnly} {
+                        upload(src);
+                }
+                template <class Pred, class = decltype(bool(std::declval<Pred &>()(docid_t{})))>
+                DeviceDocumentsFilter(IndexSource *src, Pred &&disregard) {
+                        const uint32_t n = src->default_field_stats().docsCnt;
+                        for (docid_t d = 1; d <= n; ++d)
+                                if (disregard(d))
+                                        ids.push_back(d);
+                        upload(src);
+                }
+                ~DeviceDocumentsFilter() override { tri_filter_destroy(h); }
+                DeviceDocumentsFilter(const DeviceDocumentsFilter &) = delete;
+                bool filter(const docid_t id) override { return std::binary_search(ids.begin(), ids.end(), id) != keep; }
+                tri_filter *device_filter() override { return h; }
+        };
+
         // ------------------------------------------------------------------ execution
         struct BatchDeleter {
                 void operator()(tri_batch *b) const { tri_batch_destroy(b); }
@@ -590,8 +628,9 @@ namespace trinity_amd {
 
         // Lower iterator trees (the mirror of build_iterator's output), attach one ScorerWeight per TERM token
         // (docset_iterators_scorers.cpp:16-22), create + run one batch.
+        // docFilters: per query its device filter (IndexDocumentsFilter::device_filter; nullptr: none), installed before the run; empty: no query has one.
         inline BatchPtr run_batch(IndexSource *src, const std::vector<DocsSetIterators::Iterator *> &roots, uint32_t flags, uint32_t topk,
-                                  Similarity::IndexSourceTermsScorer *scorer) {
+                                  Similarity::IndexSourceTermsScorer *scorer, const std::vector<tri_filter *> &docFilters = {}) {
                 validate_flags(flags);
                 const bool scored = flags & unsigned(ExecFlags::AccumulatedScoreScheme);
                 if (!(flags & (unsigned(ExecFlags::DocumentsOnly) | unsigned(ExecFlags::AccumulatedScoreScheme))))
@@ -617,6 +656,21 @@ namespace trinity_amd {
                 for (const int32_t x : st)
                         if (x != TRI_OK)
                                 check(x);
+                if (!docFilters.empty()) {
+                        if (docFilters.size() != qs.size())
+                                throw invalid_argument("one document filter per query");
+                        std::vector<tri_filter *> distinct;
+                        std::vector<uint32_t> of_query(qs.size(), 0xffffffffu);
+                        for (size_t q = 0; q < qs.size(); ++q)
+                                if (docFilters[q]) {
+                                        const auto it = std::find(distinct.begin(), distinct.end(), docFilters[q]);
+                                        of_query[q] = uint32_t(it - distinct.begin());
+                                        if (it == distinct.end())
+                                                distinct.push_back(docFilters[q]);
+                                }
+                        if (!distinct.empty())
+                                check(tri_batch_set_filters(b, distinct.data(), distinct.size(), of_query.data()));
+                }
                 check(tri_batch_run(b));
                 check(tri_batch_sync(b));
                 return bp;
@@ -639,6 +693,7 @@ namespace trinity_amd {
                 DocsSetIterators::Iterator *const root;
                 const uint32_t flags;
                 Similarity::IndexSourceTermsScorer *const scorer;
+                tri_filter *const docFilter; // the application's filter, applied by the device (nullptr: none, or one the caller applies while it replays)
                 std::vector<uint32_t> ids; // the query's matches, ascending (filled by the first process())
                 std::vector<double> sc;    // ... and their scores (AccumulatedScoreScheme)
                 bool ran{false};
@@ -648,7 +703,7 @@ namespace trinity_amd {
                         if (ran)
                                 return;
                         const bool scored = flags & unsigned(ExecFlags::AccumulatedScoreScheme);
-                        auto b = run_batch(root->isrc, {root}, flags, 0, scorer);
+                        auto b = run_batch(root->isrc, {root}, flags, 0, scorer, docFilter ? std::vector<tri_filter *>{docFilter} : std::vector<tri_filter *>{});
                         ++batches;
                         size_t n = 0;
                         check(tri_batch_docset(b.get(), 0, nullptr, 0, &n));
@@ -663,8 +718,8 @@ namespace trinity_amd {
                 }
 
               public:
-                GpuDocsSetSpan(DocsSetIterators::Iterator *r, uint32_t f, Similarity::IndexSourceTermsScorer *s)
-                    : root{r}, flags{f}, scorer{s} {}
+                GpuDocsSetSpan(DocsSetIterators::Iterator *r, uint32_t f, Similarity::IndexSourceTermsScorer *s, tri_filter *df = nullptr)
+                    : root{r}, flags{f}, scorer{s}, docFilter{df} {}
                 uint64_t cost() override { return root->cost(); }
                 unsigned batches_run() const { return batches; } // device batches this span has compiled and run (1 after any number of windows)
                 isrc_docid_t process(MatchesProxy *mp, const isrc_docid_t min, const isrc_docid_t max) override {
@@ -688,7 +743,10 @@ namespace trinity_amd {
         // The default mode: every match is delivered as a matched_document — the query terms that matched it and their hits
         // (prepare_match, queryexec_ctx.cpp:522-648) — rebuilt here from the engine's packed arrays.
         inline void exec_query_default_mode(DocsSetIterators::Iterator *root, IndexSource *src, MatchedIndexDocumentsFilter *mf, IndexDocumentsFilter *df) {
-                auto b = run_batch(src, {root}, 0, 0, nullptr);
+                tri_filter *const onDevice = df ? df->device_filter() : nullptr;
+                auto b = run_batch(src, {root}, 0, 0, nullptr, onDevice ? std::vector<tri_filter *>{onDevice} : std::vector<tri_filter *>{});
+                if (onDevice)
+                        df = nullptr; // (the batch has dropped its documents: nothing to ask per match)
                 size_t n = 0, npos = 0;
                 check(tri_batch_docset(b.get(), 0, nullptr, 0, &n));
                 std::vector<docid_t> ids(n);
@@ -801,10 +859,13 @@ namespace trinity_amd {
                                         mf->consider(id);
                         }
                 } handler;
+                // a filter the device holds (DeviceDocumentsFilter) is installed with the batch — tri_batch_set_filters — and asked nothing here; a plain host
+                // filter is asked per replayed document
+                tri_filter *const onDevice = f ? f->device_filter() : nullptr;
                 handler.mf = matchesFilter;
-                handler.df = f;
+                handler.df = onDevice ? nullptr : f;
                 handler.scored = flags & unsigned(ExecFlags::AccumulatedScoreScheme);
-                GpuDocsSetSpan span(root, flags, scorer);
+                GpuDocsSetSpan span(root, flags, scorer, onDevice);
                 try {
                         span.process(&handler, 1, DocIDsEND);
                 } catch (const aborted_search_exception &) {
@@ -814,12 +875,17 @@ namespace trinity_amd {
 
         // The batched sibling of exec_query_par (exec.h:87-177): all queries in ONE engine batch; DocumentsOnly results
         // arrive through consider(ids, cnt) (matches.h:161-165), scored ones through consider(id, score).
+        // docFilters: optionally one IndexDocumentsFilter per query (nullptr: none) — filters the device holds (DeviceDocumentsFilter), installed with the batch.
         inline void exec_queries(const std::vector<DocsSetIterators::Iterator *> &roots, IndexSource *src, const std::vector<MatchedIndexDocumentsFilter *> &filters,
-                                 const uint32_t flags, Similarity::IndexSourceTermsScorer *scorer = nullptr) {
-                if (roots.size() != filters.size())
+                                 const uint32_t flags, Similarity::IndexSourceTermsScorer *scorer = nullptr, const std::vector<IndexDocumentsFilter *> &docFilters = {}) {
+                if (roots.size() != filters.size() || (!docFilters.empty() && docFilters.size() != roots.size()))
                         throw invalid_argument("one filter per query");
+                std::vector<tri_filter *> onDevice(docFilters.size(), nullptr);
+                for (size_t q = 0; q < docFilters.size(); ++q)
+                        if (docFilters[q] && !(onDevice[q] = docFilters[q]->device_filter()))
+                                throw invalid_argument("exec_queries takes document filters the device holds (DeviceDocumentsFilter)");
                 const bool scored = flags & unsigned(ExecFlags::AccumulatedScoreScheme);
-                auto b = run_batch(src, roots, flags, 0, scorer);
+                auto b = run_batch(src, roots, flags, 0, scorer, onDevice);
                 std::vector<uint32_t> ids;
                 std::vector<double> sc;
                 if (!scored) {

@@ -672,7 +672,7 @@ __global__ __launch_bounds__(FUS_WG, (FUS_WGS_PER_CU * FUS_WG + 255) / 256) void
                                                      uint32_t *__restrict__ ticket, uint32_t *__restrict__ counts, const uint32_t k,
                                                      uint32_t *__restrict__ part_docs, double *__restrict__ part_scores,
                                                      uint32_t *__restrict__ part_counts, const uint32_t *__restrict__ masked, const int sim,
-                                                     uint32_t *__restrict__ out, double *__restrict__ all_scores, uint32_t *__restrict__ allow) {
+                                                     uint32_t *__restrict__ out, double *__restrict__ all_scores, uint32_t *__restrict__ allow TRI_FILTER_ARG) {
         __shared__ FusedShared sh;
         constexpr uint32_t W = FusGeom<HW>::W, CELLS = FusGeom<HW>::CELLS;
         const uint32_t tid = threadIdx.x;
@@ -694,6 +694,7 @@ __global__ __launch_bounds__(FUS_WG, (FUS_WGS_PER_CU * FUS_WG + 255) / 256) void
                 const uint32_t tix = sched[ticket_no];
                 const DevTask task = tasks[tix];
                 const DevQuery q = plan[task.slot];
+                TRI_FILTER_TASK(task.slot); // (a filtered query sweeps with the variant that tests the bitmap: below)
                 // ---- per task: the query's slot map, the slots' terms, the score tables, an empty candidate buffer
                 {
                         const uint32_t wi = min(tid, (uint32_t)(sizeof(DevFused) / 4 - 1)); // (every lane stores: no divergent branch around the barriers)

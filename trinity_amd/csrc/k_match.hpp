@@ -12,6 +12,7 @@ static_assert(TILE_BLOCKS == AND_WG, "the candidate kernel maps one 32-candidate
 // loop whose exit depends on one gets exec-masked structurisation, which is fatal around s_barrier (lanes
 // "leave" the loop at different times).  uni() pins such values into an SGPR so the branch is scalar.
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+#include "k_filter.hpp" // (per-query document filters: FilterSel / filter_pick, which every kernel that drops masked documents calls once per task)
 
 // LDS candidate layout: logical slot j lives at phys(j); rotating each 32-slot row by its row number keeps
 // the one-lane-per-row writes of the lead decode (lane t writes row t, column i) off a single bank.
@@ -1017,7 +1018,7 @@ __global__ __launch_bounds__(DENSE_WG, TRI_DENSE_WAVES) void k_and_dense(const u
                                                         const uint32_t *__restrict__ qterms, const uint32_t ntasks, uint32_t *__restrict__ ticket,
                                                         uint32_t *__restrict__ out, uint32_t *__restrict__ counts,
                                                         const uint32_t *__restrict__ masked, const uint32_t *__restrict__ qplane,
-                                                        const uint32_t *__restrict__ planes, const uint32_t plw) {
+                                                        const uint32_t *__restrict__ planes, const uint32_t plw TRI_FILTER_ARG) {
         __shared__ DenseShared sh;
         const uint32_t wave = uni(threadIdx.x >> 6);
         PROF_DECL;
@@ -1035,6 +1036,7 @@ __global__ __launch_bounds__(DENSE_WG, TRI_DENSE_WAVES) void k_and_dense(const u
                 const uint32_t tix = sched[ticket_no];
                 const DevTask task = tasks[tix];
                 const DevQuery q = plan[task.slot];
+                TRI_FILTER_TASK(task.slot);
                 PROF_LAP(0);
                 TASKTIME_DENSE(8 * ticket_no);
                 dense_task<DENSE_WG, CODEC>(sh, index, blk_last, blk_off, win, terms, qterms, q, task, out, counts + tix, masked, qplane, planes, plw PROF_PASS);
@@ -1061,7 +1063,7 @@ __global__ __launch_bounds__(AND_WG, TRI_AND_WAVES) void k_and(const uint8_t *__
                                                 const uint32_t *__restrict__ cand_q, uint32_t *__restrict__ ticket,
                                                 uint32_t *__restrict__ out, uint32_t *__restrict__ counts,
                                                 const uint32_t *__restrict__ masked, const uint32_t *__restrict__ qplane,
-                                                const uint32_t *__restrict__ planes, const uint32_t plw) {
+                                                const uint32_t *__restrict__ planes, const uint32_t plw TRI_FILTER_ARG) {
         __shared__ AndShared sh;
         const uint32_t tid = threadIdx.x;
         const uint32_t wave = uni(tid >> 6);
@@ -1109,6 +1111,7 @@ __global__ __launch_bounds__(AND_WG, TRI_AND_WAVES) void k_and(const uint8_t *__
                 const DevTask task = tasks[tix];
                 const uint32_t slot = task.slot;
                 const DevQuery q = plan[slot];
+                TRI_FILTER_TASK(slot);
                 const DevTerm lead = terms[qterms[q.term_base] & QT_TERM];
                 TRACE(1, slot, q.nterms);
                 uint32_t *qout = out + task.out_off;

@@ -1102,7 +1102,7 @@ __global__ __launch_bounds__(PLK_WG, (PLK_WGS_PER_CU * PLK_WG + 255) / 256) void
         const double *__restrict__ sweights, const uint32_t ntasks, uint32_t *__restrict__ ticket, uint32_t *__restrict__ counts, const uint32_t k,
         uint32_t *__restrict__ part_docs, double *__restrict__ part_scores, uint32_t *__restrict__ part_counts, const uint32_t *__restrict__ masked,
         const int sim, const uint32_t *__restrict__ planes0, const uint32_t *__restrict__ planes_hi, const uint32_t plw, const uint32_t zrow, uint32_t *__restrict__ scratch, const uint32_t sparse_cap,
-        unsigned long long *__restrict__ qthr) {
+        unsigned long long *__restrict__ qthr TRI_FILTER_ARG) {
         PlanesShared &sh = plk_shared();
         const uint32_t tid = threadIdx.x, lane = tid & 63u;
         const uint32_t wave = uni(tid >> 6);
@@ -1127,6 +1127,7 @@ __global__ __launch_bounds__(PLK_WG, (PLK_WGS_PER_CU * PLK_WG + 255) / 256) void
                 TASKTIME_PLANES(8 * ticket_no);
                 const DevTask task = tasks[tix];
                 const DevQuery q = plan[task.slot];
+                TRI_FILTER_TASK(task.slot);
                 unsigned long long *const gthr = qthr + task.slot; // the threshold the query's tasks share
                 {
                         const uint32_t wi = min(tid, (uint32_t)(sizeof(DevFused) / 4 - 1)); // (every lane stores: no divergent branch around the barriers)

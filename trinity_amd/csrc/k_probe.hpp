@@ -42,7 +42,7 @@ __global__ __launch_bounds__(PROBE_WG, TRI_PROBE_WAVES) void k_probe(const uint8
                                                                       const DevTerm *__restrict__ terms, const DevPsetUnit *__restrict__ units, const uint32_t *__restrict__ order,
                                                                       const uint32_t ntasks, uint32_t *__restrict__ ticket, const uint32_t *__restrict__ qterms,
                                                                       const uint32_t *__restrict__ qplane, uint32_t *__restrict__ out, uint32_t *__restrict__ counts,
-                                                                      const uint32_t *__restrict__ masked, const uint32_t *__restrict__ planes, const uint32_t plw) {
+                                                                      const uint32_t *__restrict__ masked, const uint32_t *__restrict__ planes, const uint32_t plw TRI_FILTER_ARG) {
         __shared__ ProbeShared sh;
         const uint32_t lane = threadIdx.x & 63u;
         uint32_t *const cand = sh.cand[uni(threadIdx.x >> 6)];
@@ -56,6 +56,7 @@ __global__ __launch_bounds__(PROBE_WG, TRI_PROBE_WAVES) void k_probe(const uint8
                 auto word = [&](const int i) { return (uint32_t)__builtin_amdgcn_readlane((int)rec, i); };
                 const uint32_t nterms = word(5), term_base = word(6), tix = word(4);
                 uint32_t *const qout = out + (((uint64_t)word(1) << 32) | word(0));
+                TRI_FILTER_TASK_OF(tix); // (the wave's task: uniform)
                 const DevTerm lead = terms[word(8) & QT_TERM];
                 const uint32_t tb_end = min(lead.nblocks, word(3) * (uint32_t)TILE_BLOCKS);
                 uint32_t produced = 0;

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(PSET_WG, TRI_PSET_WAVES) void k_psets(const DevPset
                                                                    uint32_t *__restrict__ ticket, const uint32_t *__restrict__ qterms, const uint32_t *__restrict__ qplane,
                                                                    uint32_t *__restrict__ out, uint32_t *__restrict__ counts, const uint32_t *__restrict__ masked,
                                                                    const uint32_t *__restrict__ planes, const uint32_t plw, const uint32_t *__restrict__ scat_off,
-                                                                   const uint32_t *__restrict__ scat_cnt, const uint32_t *__restrict__ scat_docs) {
+                                                                   const uint32_t *__restrict__ scat_cnt, const uint32_t *__restrict__ scat_docs TRI_FILTER_ARG) {
         __shared__ PsetShared sh;
         const uint32_t tid = threadIdx.x, lane = tid & 63u;
         const uint32_t wave = uni(tid >> 6);
@@ -259,6 +259,7 @@ __global__ __launch_bounds__(PSET_WG, TRI_PSET_WAVES) void k_psets(const DevPset
                 const DevPsetUnit &U = sh.unit[p];
                 const uint32_t nterms = uni(U.nterms), w_begin = uni(U.w_begin), w_end = uni(U.w_end), tix = uni(U.tix), term_base = uni(U.term_base);
                 const bool as_bitmap = uni(U.first) & PSET_UNIT_BITMAP; // RESULT_BITMAP (dev_structs.hpp): the survivors' words go out as they are
+                TRI_FILTER_TASK_OF(tix); // (the unit names no query on purpose: only a batch with filters goes tix -> tasks[].slot -> the query's row)
                 uint32_t *const qout = out + (((uint64_t)uni((uint32_t)(U.out_off >> 32)) << 32) | uni((uint32_t)U.out_off));
                 // (wave 0) the next task's record and the ticket after it: issued now, used when this task is done
                 uint32_t nwd = 0, nnt = 0xffffffffu;
@@ -437,11 +438,11 @@ __global__ __launch_bounds__(256) void k_psets_prep_list(const DevPsetUnit *__re
 }
 template <int CODEC>
 __global__ __launch_bounds__(PSCAT_WG) void k_psets_prep(const DevPsetUnit *__restrict__ units, const uint32_t *__restrict__ list, const uint32_t *__restrict__ listed, const DevQuery *__restrict__ plan, const DevTask *__restrict__ tasks,
-                                                         const uint32_t *__restrict__ qterms, const uint32_t *__restrict__ qplane, const uint32_t *__restrict__ masked,
+                                                         const uint32_t *__restrict__ qterms, const uint32_t *__restrict__ qplane, const uint32_t *__restrict__ masked_,
                                                          const uint8_t *__restrict__ index, const uint32_t *__restrict__ blk_last, const uint32_t *__restrict__ blk_off,
                                                          const uint4 *__restrict__ blk_rec, const uint32_t *__restrict__ blk_doff, const DevTerm *__restrict__ terms,
                                                          uint32_t *__restrict__ cursor, uint32_t *__restrict__ scat_off, uint32_t *__restrict__ scat_cnt,
-                                                         uint32_t *__restrict__ scat_docs, const uint32_t scat_cap) {
+                                                         uint32_t *__restrict__ scat_docs, const uint32_t scat_cap, const FilterSel fsel) {
         __shared__ PscatShared sh;
         const uint32_t tid = threadIdx.x;
         if (blockIdx.x >= uni(*listed)) // (grid: the planner's count of scatter queries == the units k_psets_prep_list found; belt and braces)
@@ -457,7 +458,9 @@ __global__ __launch_bounds__(PSCAT_WG) void k_psets_prep(const DevPsetUnit *__re
                 }
                 sh.nrows[tid] = n;
         }
-        const DevQuery &q = plan[uni(tasks[tix].slot)];
+        const uint32_t slot = uni(tasks[tix].slot);
+        const DevQuery &q = plan[slot];
+        const uint32_t *const masked = filter_pick_if(masked_, fsel, slot);
         const uint32_t ntasks = min(uni(q.ntasks), PSCAT_MAX_TASKS), nbits = uni(q.out_cap) * 32u, task_docs = (uni(U.w_end) - uni(U.w_begin)) * SPAN_BITS;
         for (uint32_t t = tid; t < ntasks; t += PSCAT_WG)
                 sh.cnt[t] = 0;

@@ -129,11 +129,14 @@ struct TreeEvalShared {
 };
 __global__ __launch_bounds__(TREE_WG) void k_tree_eval(const DevQuery *__restrict__ plan, const DevTask *__restrict__ tasks, const uint32_t *__restrict__ sched,
                                                        const uint32_t *__restrict__ tree, const uint32_t *__restrict__ trows, const uint32_t *__restrict__ prows,
-                                                       const uint32_t *__restrict__ masked, uint32_t *__restrict__ qbits, uint32_t *__restrict__ chunk_counts,
-                                                       const uint32_t plw) {
+                                                       const uint32_t *__restrict__ masked_, uint32_t *__restrict__ qbits, uint32_t *__restrict__ chunk_counts,
+                                                       const uint32_t plw, const FilterSel fsel) {
         __shared__ TreeEvalShared sh;
         const uint32_t tid = threadIdx.x, chunk = blockIdx.x, nchunks = gridDim.x, qi = blockIdx.y;
-        const DevQuery q = plan[tasks[sched[qi]].slot];
+        const uint32_t slot = tasks[sched[qi]].slot;
+        const DevQuery q = plan[slot];
+        // the root drops the index's masked documents and the query's own filter (its hidden phrase queries ran against the mask alone)
+        const uint32_t *const masked = filter_pick_if(masked_, fsel, uni(slot));
         const uint32_t nn = tree_load(sh.t, tree + q.fused_idx);
         uint32_t count = 0;
         for (uint32_t pass = 0; pass < TREE_PASSES; ++pass) {

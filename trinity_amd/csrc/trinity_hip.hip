@@ -359,6 +359,24 @@ struct tri_index : HostIndex {
         }
 };
 
+// A per-query document filter (IndexDocumentsFilter, matches.h:190-201) as the device keeps it: a bitmap over the index's docIDs in DROP polarity, of the
+// extent of d_masked (filter_words).  It belongs to its index — destroyed before it, like a batch — and is only read by the batches that name it
+// (tri_batch_set_filters): their runs OR it with the mask of the moment into a row of their own (k_filter.hpp)
+struct tri_filter {
+        tri_index *ix = nullptr;
+        tri_dev *dev = nullptr;
+        uint32_t *d_bits = nullptr;
+        size_t words = 0;
+        ~tri_filter() {
+                if (dev)
+                        hipSetDevice(dev->device);
+                pool_free(dev, d_bits);
+                dev_release(dev);
+        }
+};
+// whole docID windows (the bitmap kernels read a window's worth of words at a time), one spare window: the extent of d_masked and of every filter
+static size_t filter_words(const tri_index *ix) { return ((size_t)ix->max_doc / SPAN_BITS + 2) * SPAN_WORDS; }
+
 // a batch's HIP events, in the order they are recorded: EV_UP, the plan has arrived (upload stream); then on the engine stream the run's start,
 // the end of each of its stages (tri_batch_run), the run's end
 enum BatchEvent { EV_UP, EV_START, EV_PLANE_ROWS, EV_DENSE, EV_PSET, EV_PROBE, EV_CAND, EV_FUSED, EV_PLANES, EV_PHRASE, EV_TREE, EV_END, EV_COUNT };
@@ -420,6 +438,12 @@ struct tri_batch : BatchPlan {
         std::vector<uint32_t> h_counts;       // per task
         std::vector<uint64_t> h_query_counts; // per plan slot
         bool synced = false;
+        // per-query filters (tri_batch_set_filters; stored by reference): filter_rows[r - 1] = the filter behind row id r — the filters at least one query
+        // names —, d_filter_tab = [row id per plan slot][the rows' source pointers], d_filter_rows = the rows every run rebuilds (filter | mask)
+        std::vector<const tri_filter *> filter_rows;
+        uint8_t *d_filter_tab = nullptr;
+        uint32_t *d_filter_rows = nullptr;
+        size_t filter_rows_cap = 0; // rows d_filter_rows holds
         tri_batch_info info{};
         ~tri_batch() { // also runs when tri_batch_create fails half-way: nothing allocated so far is leaked
                 if (dev) {
@@ -452,6 +476,8 @@ struct tri_batch : BatchPlan {
                 pool_free(dev, d_tree_scratch);
                 pool_free(dev, d_tree_scores);
                 pool_free(dev, d_scat_docs);
+                pool_free(dev, d_filter_tab);
+                pool_free(dev, d_filter_rows);
                 dev_release(dev);
         }
 };
@@ -471,6 +497,7 @@ struct tri_batch : BatchPlan {
 #include "k_tree.hpp"
 #include "k_commit.hpp"
 #include "k_lencode.hpp"
+#include "filtered_kernels.hpp"
 
 // launch the instantiation of a codec-templated kernel that matches the uploaded segment: `pick` maps the codec (a std::integral_constant: the
 // kernel template's first argument) to the kernel, and chooses the template's other arguments, if it has any
@@ -1129,6 +1156,48 @@ extern "C" void tri_batch_destroy(tri_batch *b) {
 
 // ---- tri_batch_run's stages, in launch order: each ends with the event that closes its time (EV_PLANE_ROWS .. EV_TREE)
 
+// what the matching kernels are handed beside the index's mask (k_filter.hpp): nothing, for a batch without filters
+static FilterSel filter_sel(const tri_batch *b) {
+        if (b->filter_rows.empty())
+                return FilterSel{nullptr, nullptr, nullptr, 0u};
+        return FilterSel{b->d_filter_rows, (const uint32_t *)b->d_filter_tab, b->dev_at(b->tasks), (uint32_t)filter_words(b->ix)};
+}
+// A persistent matching kernel for batch b: the kernel of this file (tri_launch), or — the batch has filters — its twin of filtered_kernels.hip, which takes the
+// same arguments and a FilterSel behind them
+template <class F>
+struct FilteredKernel;
+template <class... A>
+struct FilteredKernel<void (*)(A...)> {
+        using type = void (*)(A..., FilterSel);
+};
+template <class Pick, class... Args>
+static void tri_launch_matching(const tri_batch *b, const int kernel, const int variant, Pick pick, const dim3 grid, const dim3 block, const hipStream_t stream, Args... args) {
+        const FilterSel fsel = filter_sel(b);
+        if (!fsel.rows)
+                return tri_launch(b->ix->codec, pick, grid, block, stream, args...);
+        using Plain = decltype(+pick(std::integral_constant<int, CODEC_GOOGLE>()));
+        const auto twin = reinterpret_cast<typename FilteredKernel<Plain>::type>(const_cast<void *>(filtered_kernel(kernel, b->ix->codec == TRI_CODEC_LUCENE ? CODEC_LUCENE : CODEC_GOOGLE, variant)));
+        hipLaunchKernelGGL(twin, grid, block, 0, stream, args..., fsel);
+}
+// where the rows' source pointers lie in d_filter_tab: behind the row ids of the plan's slots
+static size_t filter_tab_ptrs_off(const tri_batch *b) { return (b->plan.size() * 4 + 15) & ~(size_t)15; }
+
+// a batch with filters: the rows its queries select from — every named filter OR-ed with the index's masked documents AS THEY STAND NOW (the set a batch
+// sees is the one in place when it runs) — in one launch, before anything reads them (timed with the plane rows)
+static int run_filter_rows(tri_batch *b) {
+        if (b->filter_rows.empty())
+                return TRI_OK;
+        tri_dev *dev = b->dev;
+        const size_t n4 = filter_words(b->ix) / 4;
+        const uint32_t nrows = (uint32_t)b->filter_rows.size();
+        for (uint32_t y0 = 0; y0 < nrows; y0 += 65535u) { // (gridDim.y <= 65535)
+                hipLaunchKernelGGL(k_filter_rows, dim3((unsigned)std::min<size_t>((n4 + FILTER_WG - 1) / FILTER_WG, 1024), std::min(65535u, nrows - y0)), dim3(FILTER_WG), 0, dev->stream,
+                                   (const uint4 *const *)(b->d_filter_tab + filter_tab_ptrs_off(b)) + y0, (const uint4 *)b->ix->d_masked, (uint4 *)b->d_filter_rows + (size_t)y0 * n4, n4);
+                HIP_TRY(hipGetLastError());
+        }
+        return TRI_OK;
+}
+
 // the head terms the batch's queries share: the rows of the index's plane cache that no earlier run has built are decoded now — once for the
 // index, not once per batch (every word of a row is written: no memset)
 static int run_plane_rows(tri_batch *b) {
@@ -1192,6 +1261,7 @@ static int run_matching(tri_batch *b) {
         }
         const DevPsetUnit *units = b->dev_at(b->units);
         const uint32_t *pset_sched = b->dev_at(b->pset_sched);
+        const FilterSel fsel = filter_sel(b);
         // unions with terms that have no plane (PSET_UNIT_SCATTER): those terms' documents listed task by task, a workgroup per query (units[] holds the TASK_PROBE units
         // too) — on the second stream, beside k_and_dense, where that stream is not k_and's (option overlap)
         const bool prep = b->n_pset && b->pscatter_queries, prep_forked = prep && !overlap && b->n_dense;
@@ -1206,13 +1276,13 @@ static int run_matching(tri_batch *b) {
                 HIP_TRY(hipGetLastError());
                 TRI_LAUNCH(k_psets_prep, ix->codec, dim3(nscat), dim3(PSCAT_WG), prep_stream, units, (const uint32_t *)b->d_scat_list, (const uint32_t *)(b->d_ticket + TICKET_SCAT_WORD + 1),
                            b->dev_at(b->plan), b->dev_at(b->tasks), (const uint32_t *)b->dev_at(b->qterms), (const uint32_t *)b->dev_opt(b->qplane), ix->d_masked, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
-                           ix->d_blk_doff, ix->d_terms, b->d_ticket + TICKET_SCAT_WORD, b->d_scat_off, b->d_scat_cnt, b->d_scat_docs, b->scat_cap);
+                           ix->d_blk_doff, ix->d_terms, b->d_ticket + TICKET_SCAT_WORD, b->d_scat_off, b->d_scat_cnt, b->d_scat_docs, b->scat_cap, fsel);
                 HIP_TRY(hipGetLastError());
                 if (prep_forked)
                         HIP_TRY(hipEventRecord(dev->ev_join, dev->stream2));
         }
         if (b->n_dense) {
-                TRI_LAUNCH(k_and_dense, ix->codec, dim3(std::min<uint32_t>(b->n_dense, (uint32_t)dev->cus * dense_wgs)), dim3(DENSE_WG), dev->stream, match_bytes, ix->d_blk_last,
+                tri_launch_matching(b, FK_AND_DENSE, 0, [](auto c) { return k_and_dense<c.value>; }, dim3(std::min<uint32_t>(b->n_dense, (uint32_t)dev->cus * dense_wgs)), dim3(DENSE_WG), dev->stream, match_bytes, ix->d_blk_last,
                            match_off, ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->sched) + trip::sched_first(*b, TASK_DENSE), b->dev_at(b->qterms), b->n_dense,
                            b->d_ticket + TICKET_DENSE_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->dev_opt(b->qplane), (const uint32_t *)ix->d_pcache, b->plw);
                 HIP_TRY(hipGetLastError());
@@ -1223,7 +1293,7 @@ static int run_matching(tri_batch *b) {
         if (b->n_pset) {
                 // the queries all of whose terms have planes: word-wise algebra over the planes + expansion (k_psets.hpp)
                 const uint32_t pset_wgs = TRI_PSET_WAVES * 256 / PSET_WG;
-                TRI_LAUNCH(k_psets, ix->codec, dim3(std::min<uint32_t>(b->n_pset, (uint32_t)dev->cus * (overlap && dev->opt.overlap_dense_wgs ? std::min<uint32_t>(dense_wgs, pset_wgs) : pset_wgs))),
+                tri_launch_matching(b, FK_PSETS, 0, [](auto c) { return k_psets<c.value>; }, dim3(std::min<uint32_t>(b->n_pset, (uint32_t)dev->cus * (overlap && dev->opt.overlap_dense_wgs ? std::min<uint32_t>(dense_wgs, pset_wgs) : pset_wgs))),
                            dim3(PSET_WG), dev->stream, units, pset_sched, b->n_pset, b->d_ticket + TICKET_PSET_WORD, (const uint32_t *)b->dev_at(b->qterms), (const uint32_t *)b->dev_opt(b->qplane), b->d_out,
                            b->d_counts, ix->d_masked, (const uint32_t *)ix->d_pcache, b->plw, (const uint32_t *)b->d_scat_off, (const uint32_t *)b->d_scat_cnt,
                            (const uint32_t *)b->d_scat_docs);
@@ -1233,14 +1303,14 @@ static int run_matching(tri_batch *b) {
         if (b->n_probe) {
                 // one short lead list against lists that all have planes: a wave per task, the lead's documents probed from registers (k_probe.hpp);
                 // its units run behind k_psets' in pset_sched[]
-                TRI_LAUNCH(k_probe, ix->codec, dim3(std::min<uint32_t>((b->n_probe + PROBE_WG / 64 - 1) / (PROBE_WG / 64), (uint32_t)dev->cus * (TRI_PROBE_WAVES * 256 / PROBE_WG))),
+                tri_launch_matching(b, FK_PROBE, 0, [](auto c) { return k_probe<c.value>; }, dim3(std::min<uint32_t>((b->n_probe + PROBE_WG / 64 - 1) / (PROBE_WG / 64), (uint32_t)dev->cus * (TRI_PROBE_WAVES * 256 / PROBE_WG))),
                            dim3(PROBE_WG), dev->stream, match_bytes, ix->d_blk_last, match_off, ix->d_terms, units, pset_sched + b->n_pset, b->n_probe, b->d_ticket + TICKET_PROBE_WORD,
                            (const uint32_t *)b->dev_at(b->qterms), (const uint32_t *)b->dev_opt(b->qplane), b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)ix->d_pcache, b->plw);
                 HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(b->ev[EV_PROBE], dev->stream));
         if (b->n_cand)
-                TRI_LAUNCH(k_and, ix->codec, dim3(std::min<uint32_t>(b->n_cand, (uint32_t)dev->cus * cand_wgs)), dim3(AND_WG), cand_stream, match_bytes, ix->d_blk_last, match_off,
+                tri_launch_matching(b, FK_AND, 0, [](auto c) { return k_and<c.value>; }, dim3(std::min<uint32_t>(b->n_cand, (uint32_t)dev->cus * cand_wgs)), dim3(AND_WG), cand_stream, match_bytes, ix->d_blk_last, match_off,
                            ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->sched) + trip::sched_first(*b, TASK_CAND), b->dev_at(b->qterms), b->dev_at(b->cand_q),
                            b->d_ticket + TICKET_CAND_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->dev_opt(b->qplane), (const uint32_t *)ix->d_pcache, b->plw);
         HIP_TRY(hipGetLastError());
@@ -1261,7 +1331,7 @@ static int run_fused(tri_batch *b) {
                 const uint32_t nf = b->*trip::SCHED_COUNT[kind], variant = kind - TASK_FUSED;
                 if (!nf)
                         continue;
-                tri_launch(ix->codec, [&](auto c) { return std::array{k_fused<c.value, 0, 0>, k_fused<c.value, 1, 0>, k_fused<c.value, 0, 1>}[variant]; },
+                tri_launch_matching(b, FK_FUSED, (int)variant, [&](auto c) { return std::array{k_fused<c.value, 0, 0>, k_fused<c.value, 1, 0>, k_fused<c.value, 0, 1>}[variant]; },
                            dim3(std::min<uint32_t>(nf, (uint32_t)dev->cus * FUS_WGS_PER_CU)), dim3(FUS_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
                            ix->d_blk_doff, ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->fused), b->dev_at(b->tasks), (const uint32_t *)b->dev_at(b->sched) + trip::sched_first(*b, kind), b->dev_at(b->sterms),
                            b->dev_at(b->sweights), nf, b->d_ticket + TICKET_FUSED_WORD + 2 * variant, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, ix->d_masked,
@@ -1284,7 +1354,7 @@ static int run_planes(tri_batch *b) {
                 const uint32_t np = b->*trip::SCHED_COUNT[kind], wide = kind - TASK_PLANES;
                 if (!np)
                         continue;
-                tri_launch(ix->codec, [&](auto c) { return wide ? k_planes<c.value, FUS_MAX_SLOTS> : k_planes<c.value, PLK_NS_SMALL>; },
+                tri_launch_matching(b, FK_PLANES, (int)wide, [&](auto c) { return wide ? k_planes<c.value, FUS_MAX_SLOTS> : k_planes<c.value, PLK_NS_SMALL>; },
                            dim3(std::min<uint32_t>(np, (uint32_t)dev->cus * PLK_WGS_PER_CU)), dim3(PLK_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
                            ix->d_blk_doff, ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->fused), b->dev_at(b->tasks), (const uint32_t *)b->dev_at(b->sched) + trip::sched_first(*b, kind), b->dev_at(b->sterms),
                            b->dev_at(b->sweights), np, b->d_ticket + TICKET_PLANES_WORD + 2 * wide, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, ix->d_masked,
@@ -1383,7 +1453,7 @@ static int run_trees(tri_batch *b) {
                         const dim3 grid(nchunks, std::min(65535u, b->n_tree - y0));
                         uint32_t *qbits = b->d_tree_qbits + (size_t)y0 * plw, *cc = b->d_tree_cc + (size_t)y0 * nchunks;
                         hipLaunchKernelGGL(k_tree_eval, grid, dim3(TREE_WG), 0, dev->stream, b->dev_at(b->plan), b->dev_at(b->tasks), tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows,
-                                           (const uint32_t *)b->d_tree_prows, (const uint32_t *)ix->d_masked, qbits, cc, plw);
+                                           (const uint32_t *)b->d_tree_prows, (const uint32_t *)ix->d_masked, qbits, cc, plw, filter_sel(b));
                         hipLaunchKernelGGL(k_tree_expand, grid, dim3(TREE_WG), 0, dev->stream, b->dev_at(b->plan), b->dev_at(b->tasks), tsched + y0, (const uint32_t *)qbits, (const uint32_t *)cc,
                                            b->d_out, b->d_counts, plw);
                         if (scored_run || rich_run)
@@ -1505,7 +1575,7 @@ extern "C" int tri_batch_run(tri_batch *b) {
                         HIP_TRY(hipEventRecord(b->ev[e], dev->stream));
         } else {
                 HIP_TRY(hipMemsetAsync(b->d_ticket, 0, TICKET_BYTES, dev->stream)); // (timed with the plane rows)
-                for (int (*stage)(tri_batch *) : {run_plane_rows, run_matching, run_fused, run_planes, run_phrases, run_trees, run_rich_count, run_scores})
+                for (int (*stage)(tri_batch *) : {run_filter_rows, run_plane_rows, run_matching, run_fused, run_planes, run_phrases, run_trees, run_rich_count, run_scores})
                         if (const int rc = stage(b))
                                 return rc;
         }
@@ -2186,6 +2256,174 @@ extern "C" int tri_batch_topk_device(tri_batch *b, void **docids, void **scores,
         *docids = b->d_top_docs;
         *scores = b->d_top_scores;
         *counts = b->d_top_counts;
+        return TRI_OK;
+}
+
+// ------------------------------------------------------------------------------------------ per-query document filters
+// IndexDocumentsFilter (matches.h:190-201; exec.cpp:1133-1150: tested where the masked documents are, before consider()) as a device bitmap per filter and a
+// row id per query: k_filter.hpp.  A filter's bitmap is built on the engine stream — behind every run already queued, ahead of every later one — and the call
+// returns once it stands (the docID list's staging buffer is released then)
+namespace {
+        // the bitmap's buffer and handle; the caller fills it under the handle's lock
+        int filter_new(tri_index *ix, std::unique_ptr<tri_filter> &f) {
+                f = std::make_unique<tri_filter>();
+                f->ix = ix;
+                f->dev = ix->dev;
+                dev_retain(ix->dev);
+                f->words = filter_words(ix);
+                HIP_TRY(pool_alloc(ix->dev, (void **)&f->d_bits, f->words * 4));
+                return TRI_OK;
+        }
+        // KEEP: the allow-list's bitmap becomes the drop bitmap; then wait for the filter to stand
+        int filter_finish(tri_filter *f, const int mode, std::unique_lock<std::recursive_mutex> &lock) {
+                tri_dev *dev = f->dev;
+                if (mode == TRI_FILTER_KEEP) {
+                        const size_t n4 = f->words / 4;
+                        hipLaunchKernelGGL(k_filter_complement, dim3((unsigned)std::min<size_t>((n4 + FILTER_WG - 1) / FILTER_WG, 1024)), dim3(FILTER_WG), 0, dev->stream, (uint4 *)f->d_bits, n4);
+                        HIP_TRY(hipGetLastError());
+                }
+                hipEvent_t done = nullptr;
+                HIP_TRY(event_get(dev, &done));
+                const hipError_t e = hipEventRecord(done, dev->stream);
+                lock.unlock(); // (the wait stands outside the lock, like tri_batch_sync's)
+                const hipError_t e2 = e == hipSuccess ? hipEventSynchronize(done) : e;
+                event_put(dev, done);
+                HIP_TRY(e2);
+                return TRI_OK;
+        }
+} // namespace
+
+extern "C" int tri_filter_create(tri_index *ix, const uint32_t *docids, size_t n, int mode, tri_filter **out) {
+        if (!ix || !out || (!docids && n))
+                return fail(TRI_ERR_INVALID, "tri_filter_create: null argument");
+        if (mode != TRI_FILTER_DROP && mode != TRI_FILTER_KEEP)
+                return fail(TRI_ERR_INVALID, "tri_filter_create: mode %d is neither TRI_FILTER_DROP nor TRI_FILTER_KEEP", mode);
+        tri_dev *dev = ix->dev;
+        HIP_TRY(hipSetDevice(dev->device));
+        std::unique_ptr<tri_filter> f;
+        if (const int rc = filter_new(ix, f))
+                return rc;
+        uint32_t *d_ids = nullptr;
+        struct Staging { // (released on every way out)
+                tri_dev *dev;
+                uint32_t *&p;
+                ~Staging() { pool_free(dev, p); }
+        } staging{dev, d_ids};
+        std::unique_lock<std::recursive_mutex> lock(dev->mu);
+        HIP_TRY(hipMemsetAsync(f->d_bits, 0, f->words * 4, dev->stream));
+        if (n) {
+                HIP_TRY(pool_alloc(dev, (void **)&d_ids, n * 4));
+                HIP_TRY(hipMemcpyAsync(d_ids, docids, n * 4, hipMemcpyHostToDevice, dev->stream)); // (pageable source: staged before the call returns)
+                hipLaunchKernelGGL(k_filter_scatter, dim3((unsigned)std::min<size_t>((n + FILTER_WG - 1) / FILTER_WG, 4096)), dim3(FILTER_WG), 0, dev->stream, (const uint32_t *)d_ids, n,
+                                   ix->max_doc, f->d_bits);
+                HIP_TRY(hipGetLastError());
+        }
+        if (const int rc = filter_finish(f.get(), mode, lock))
+                return rc;
+        *out = f.release();
+        return TRI_OK;
+}
+
+extern "C" int tri_filter_from_docset(tri_batch *b, size_t q, int mode, tri_filter **out) {
+        if (!b || !out)
+                return fail(TRI_ERR_INVALID, "tri_filter_from_docset: null argument");
+        if (mode != TRI_FILTER_DROP && mode != TRI_FILTER_KEEP)
+                return fail(TRI_ERR_INVALID, "tri_filter_from_docset: mode %d is neither TRI_FILTER_DROP nor TRI_FILTER_KEEP", mode);
+        if (q >= b->nq)
+                return fail(TRI_ERR_INVALID, "tri_filter_from_docset: query %zu of %zu", q, b->nq);
+        if (!(b->flags & TRI_FLAG_DOCUMENTS_ONLY))
+                return fail(TRI_ERR_INVALID, "tri_filter_from_docset: a filter is made of a DocumentsOnly batch's docID set");
+        if (!b->synced)
+                return fail(TRI_ERR_INVALID, "tri_filter_from_docset: tri_batch_sync first");
+        tri_index *ix = b->ix;
+        tri_dev *dev = b->dev;
+        HIP_TRY(hipSetDevice(dev->device));
+        std::unique_ptr<tri_filter> f;
+        if (const int rc = filter_new(ix, f))
+                return rc;
+        std::unique_lock<std::recursive_mutex> lock(dev->mu);
+        HIP_TRY(hipMemsetAsync(f->d_bits, 0, f->words * 4, dev->stream));
+        const uint32_t slot = b->slot_of_query[q];
+        if (slot != UINT32_MAX && b->plan[slot].ntasks) { // (else: a query that can never match — the empty set)
+                const DevQuery &dq = b->plan[slot];
+                uint32_t most = 0; // the longest task segment: docIDs, or the words of its docID windows
+                for (uint32_t t = 0; t < dq.ntasks; ++t) {
+                        const DevTask &task = b->tasks[dq.first_task + t];
+                        most = std::max(most, dq.form == RESULT_BITMAP ? (task.tile_end - task.tile_begin) * SPAN_WORDS : b->h_counts[dq.first_task + t]);
+                }
+                if (dq.ntasks > 65535u) // (gridDim.y; a query is cut into a few hundred tasks at the most)
+                        return fail(TRI_ERR_UNSUPPORTED, "tri_filter_from_docset: query %zu has more than 65535 tasks", q);
+                if (most) {
+                        hipLaunchKernelGGL(k_filter_from_docset, dim3(std::min<uint32_t>((most + FILTER_WG - 1) / FILTER_WG, 256u), dq.ntasks), dim3(FILTER_WG), 0, dev->stream,
+                                           (const DevQuery *)b->dev_at(b->plan), (const DevTask *)b->dev_at(b->tasks), slot, (const uint32_t *)b->d_out, (const uint32_t *)b->d_counts,
+                                           ix->max_doc, f->d_bits, f->words);
+                        HIP_TRY(hipGetLastError());
+                }
+        }
+        if (const int rc = filter_finish(f.get(), mode, lock))
+                return rc;
+        *out = f.release();
+        return TRI_OK;
+}
+
+extern "C" void tri_filter_destroy(tri_filter *f) {
+        delete f; // ~tri_filter hands the bitmap back
+}
+
+extern "C" int tri_batch_set_filters(tri_batch *b, tri_filter *const *filters, size_t nf, const uint32_t *filter_of_query) {
+        if (!b || (nf && (!filters || !filter_of_query)))
+                return fail(TRI_ERR_INVALID, "tri_batch_set_filters: null argument");
+        tri_dev *dev = b->dev;
+        DevLock dev_lock(dev->mu);
+        if (!nf) {
+                b->filter_rows.clear(); // (the table and the rows stay with the batch until it goes)
+                return TRI_OK;
+        }
+        for (size_t i = 0; i < nf; ++i)
+                if (!filters[i] || filters[i]->ix != b->ix)
+                        return fail(TRI_ERR_INVALID, "tri_batch_set_filters: filter %zu %s", i, filters[i] ? "belongs to another index" : "is null");
+        for (size_t q = 0; q < b->nq; ++q)
+                if (filter_of_query[q] != 0xffffffffu && filter_of_query[q] >= nf)
+                        return fail(TRI_ERR_INVALID, "tri_batch_set_filters: query %zu names filter %u of %zu", q, filter_of_query[q], nf);
+        // row ids, in the order the plan's slots first name a filter (a hidden phrase query — no caller query — takes the index's mask: the tree's root applies the owner's filter)
+        const size_t nslots = b->plan.size(), ptrs_off = filter_tab_ptrs_off(b);
+        std::vector<uint32_t> row_of_filter(nf, 0), row_of_slot(nslots, 0);
+        std::vector<const tri_filter *> rows;
+        for (size_t s = 0; s < nslots; ++s) {
+                const uint32_t qid = b->plan[s].qid;
+                if (qid == 0xffffffffu || filter_of_query[qid] == 0xffffffffu)
+                        continue;
+                uint32_t &r = row_of_filter[filter_of_query[qid]];
+                if (!r) {
+                        rows.push_back(filters[filter_of_query[qid]]);
+                        r = (uint32_t)rows.size();
+                }
+                row_of_slot[s] = r;
+        }
+        if (rows.empty()) {
+                b->filter_rows.clear();
+                return TRI_OK;
+        }
+        HIP_TRY(hipSetDevice(dev->device));
+        const size_t stride = filter_words(b->ix);
+        if (rows.size() > b->filter_rows_cap || !b->d_filter_tab) {
+                if (b->ran && !b->synced) // (a run in flight reads the buffers that are about to go back to the pool)
+                        HIP_TRY(hipStreamSynchronize(dev->stream));
+                pool_free(dev, b->d_filter_tab);
+                pool_free(dev, b->d_filter_rows);
+                b->d_filter_tab = nullptr, b->d_filter_rows = nullptr, b->filter_rows_cap = 0;
+                b->filter_rows.clear();
+                HIP_TRY(pool_alloc(dev, (void **)&b->d_filter_tab, ptrs_off + std::max(rows.size(), b->nq) * sizeof(void *)));
+                HIP_TRY(pool_alloc(dev, (void **)&b->d_filter_rows, rows.size() * stride * 4));
+                b->filter_rows_cap = rows.size();
+        }
+        // one block — [row id per slot][source pointer per row] — on the engine stream: behind the runs already queued, which keep the assignment they were launched with
+        std::vector<uint8_t> tab(ptrs_off + rows.size() * sizeof(void *), 0);
+        memcpy(tab.data(), row_of_slot.data(), nslots * 4);
+        for (size_t r = 0; r < rows.size(); ++r)
+                memcpy(tab.data() + ptrs_off + r * sizeof(void *), &rows[r]->d_bits, sizeof(void *));
+        HIP_TRY(hipMemcpyAsync(b->d_filter_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, dev->stream)); // (pageable source: staged before the call returns)
+        b->filter_rows = std::move(rows);
         return TRI_OK;
 }
 

@@ -109,6 +109,7 @@ ABI_SYMBOLS = [
     "tri_batch_match_counts", "tri_batch_docset", "tri_batch_docset_bitmap", "tri_batch_docsets", "tri_batch_docsets_mixed", "tri_batch_scores", "tri_batch_query_terms", "tri_batch_matched_terms", "tri_batch_matched_payloads", "tri_batch_topk", "tri_batch_topk_device", "tri_batch_counts_device", "tri_batch_docset_hashes",
     "tri_cbatch_create", "tri_cbatch_destroy", "tri_cbatch_query_status", "tri_cbatch_run", "tri_cbatch_sync", "tri_cbatch_match_counts", "tri_cbatch_topk", "tri_cbatch_docset", "tri_encode_google", "tri_encode_google_payloads", "tri_commit_google", "tri_commit_lucene", "tri_merge_google", "tri_merge_lucene", "tri_encode_lucene",
     "tri_comm_unique_id", "tri_comm_create", "tri_comm_create_custom", "tri_comm_destroy", "tri_gather_results",
+    "tri_filter_create", "tri_filter_from_docset", "tri_filter_destroy", "tri_batch_set_filters",
 ]  # fmt: skip
 
 _hip = None
@@ -180,6 +181,11 @@ def hip_lib():
     L.tri_comm_create_custom.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.POINTER(vp)]
     L.tri_comm_destroy.argtypes = [vp]
     L.tri_gather_results.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.tri_filter_create.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(vp)]
+    L.tri_filter_from_docset.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(vp)]
+    L.tri_filter_destroy.argtypes = [vp]
+    L.tri_filter_destroy.restype = None
+    L.tri_batch_set_filters.argtypes = [vp, vp, C.c_size_t, vp]
     _hip = L
     return L
 
@@ -495,6 +501,35 @@ class Index:
             self.h = C.c_void_p()
 
 
+FILTER_DROP, FILTER_KEEP = 0, 1
+NO_FILTER = 0xFFFFFFFF
+
+
+class Filter:
+    """A per-query document filter on the device (IndexDocumentsFilter, matches.h:190-201): docids = the documents a query that names the
+    filter never matches — or, keep=True, the only ones it may match.  Closed before its index; alive while a batch that names it may run."""
+
+    def __init__(self, index, docids, keep=False):
+        self.index = index
+        d = np.ascontiguousarray(docids, dtype=np.uint32)
+        self.h = C.c_void_p()
+        _check(hip_lib().tri_filter_create(index.h, d.ctypes.data if d.size else None, d.size, FILTER_KEEP if keep else FILTER_DROP, C.byref(self.h)))
+
+    @classmethod
+    def from_docset(cls, batch, q, keep=True):
+        """The docID set of query q of a synced DocumentsOnly batch, taken on the device: by default an allow-list (queries restricted to it)."""
+        f = cls.__new__(cls)
+        f.index = batch.index
+        f.h = C.c_void_p()
+        _check(hip_lib().tri_filter_from_docset(batch.h, q, FILTER_KEEP if keep else FILTER_DROP, C.byref(f.h)))
+        return f
+
+    def close(self):
+        if self.h:
+            hip_lib().tri_filter_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Batch:
     """A compiled batch of postfix query programs."""
 
@@ -530,6 +565,17 @@ class Batch:
         out = np.zeros(self.nq, dtype=np.int32)
         _check(hip_lib().tri_batch_query_status(self.h, out.ctypes.data))
         return out
+
+    def set_filters(self, filters, filter_of_query=None):
+        """Per-query document filters for the runs that follow (tri_batch_set_filters): filter_of_query[q] = index into `filters` of query q's
+        filter, NO_FILTER for none; an empty `filters` clears.  The batch keeps the Filter objects referenced."""
+        filters = list(filters)
+        foq = np.ascontiguousarray(filter_of_query if filters else [], dtype=np.uint32)
+        if filters and foq.size != self.nq:
+            raise TrinityError(f"filter_of_query has {foq.size} entries for {self.nq} queries")
+        arr = (C.c_void_p * max(1, len(filters)))(*[f.h for f in filters])
+        _check(hip_lib().tri_batch_set_filters(self.h, arr if filters else None, len(filters), foq.ctypes.data if filters else None))
+        self._filters = filters
 
     def run(self):
         _check(hip_lib().tri_batch_run(self.h))
