@@ -28,7 +28,8 @@ extern "C" {
                              7: TASK_TREE (any query tree), tri_batch_info.tree_ms / tree_queries / tree_scratch_bytes, tri_commit_* / tri_merge_google;
                              8: tri_batch_docsets (every query's docID set in one call), tri_merge_lucene, option planes_rebuild;
                              9: tri_dev_memory (HBM in use), tri_batch_docsets_mixed (dense sets delivered as bitmap words), two planner contexts per handle (two threads may compile at once), plane rows built by need;
-                                within 9: tri_filter_create / tri_filter_from_docset / tri_filter_destroy / tri_batch_set_filters (per-query document filters on the device) */
+                                within 9: tri_filter_create / tri_filter_from_docset / tri_filter_destroy / tri_batch_set_filters (per-query document filters on the device);
+                                within 9: options tree_max_nodes / tree_wide_min_nodes (query trees of up to 1024 nodes; no new export, no struct grew) */
 
 /* status codes */
 #define TRI_OK 0
@@ -200,6 +201,13 @@ void *tri_dev_stream(tri_dev *);
  *   "plan_threads"        host threads tri_batch_create plans large batches with (default 0: up to 16, by the host's cores; 1: the calling thread
  *                         only).  The threads belong to the handle, are pinned to distinct CPUs next to the creating thread's, and keep polling for
  *                         about 3 ms after a batch before they sleep (csrc/host_pool.hpp says why); read when the first large batch is created
+ *   "tree_max_nodes"      a query tree of more than this many nodes is left out of the batch (TRI_ERR_UNSUPPORTED per query).  Default 64: what the narrow tree
+ *                         kernels hold (csrc/k_tree.hpp).  64 .. 1024: trees above 64 nodes — a flat OR of 70 terms, an AND of 22 three-term ORs, a matchsome
+ *                         over 100 alternatives — run in the wide tree kernels (csrc/k_tree_wide.hpp).  Any other value fails tri_batch_create with
+ *                         TRI_ERR_INVALID.  Still left out: a tree whose evaluation needs more than 64 stack words (a word per nested AND / OR / NOT /
+ *                         <optional> on the deepest path, ceil(log2(children + 1)) per nested matchsome), more than 16 reportable terms in the default mode
+ *   "tree_wide_min_nodes" a tree query of at least this many nodes runs in the wide kernels (default 65: only the trees the narrow ones cannot hold; 0: every
+ *                         tree query).  Results do not depend on it; it is there so that the wide kernels can be checked on trees with pinned answers
  * ("fused" also takes 2: only pure unions run in one pass.)  The options are read when a batch is CREATED, except the two overlap_* ones and planes_rebuild,
  * which tri_batch_run reads (they change how existing batches are launched).  Unknown names fail with TRI_ERR_INVALID. */
 int tri_dev_set_option(tri_dev *, const char *name, uint64_t value);
@@ -282,9 +290,9 @@ int tri_decode_terms(tri_index *, const uint32_t *terms, size_t n, uint32_t *doc
  * IndexSourcesCollectionBM25Scorer does for a single source (similarity.h:179-181, 202-226). */
 int tri_batch_create(tri_index *, const uint32_t *prog, size_t prog_len, const tri_query *queries, size_t nq,
                      const double *weights, uint32_t flags, uint32_t topk, int similarity, tri_batch **out);
-/* A query whose shape the planner does not lower (today: a multi-word phrase under an OR or inside a general tree, a general tree over
- * more than 8 distinct terms or 16 scored leaves, more than 16 term slots in a CNF, more than 16 reportable terms in the default mode)
- * does NOT fail tri_batch_create: the query is left out of the batch — it reports no matches — and its status says so, so that one such
+/* A query whose shape the planner does not lower (today: a tree of more nodes than option tree_max_nodes allows — 64 by default, up to 1024 —
+ * or one whose evaluation needs more than 64 stack words, more than 16 reportable terms in the default mode, a tree that matches documents
+ * holding none of its terms) does NOT fail tri_batch_create: the query is left out of the batch — it reports no matches — and its status says so, so that one such
  * query among thousands costs the caller one CPU span (exec.cpp:509-1517 for that query alone), not the batch.  status[q]: TRI_OK or
  * TRI_ERR_UNSUPPORTED; tri_batch_info.unsupported_queries counts them; tri_last_error() after tri_batch_create describes the last one.
  * (A malformed program is the caller's bug and still fails the call with TRI_ERR_INVALID.) */

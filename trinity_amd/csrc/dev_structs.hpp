@@ -144,6 +144,34 @@ struct DevTreeNode {
         uint64_t kids;  // inner node: bit k = node k is a child
 };
 static_assert(sizeof(DevTreeNode) == 32, "eight words per node");
+// ---- a WIDE record (k_tree_wide.hpp): a tree of more than TREE_MAX_NODES nodes (option tree_max_nodes lets them in), or any tree once option
+//      tree_wide_min_nodes says so.  Same place (tree[], DevQuery::fused_idx), same header length — { nnodes, TREE_KIND_WIDE, stack words
+//      k_tree_eval_wide needs, counter depth k_tree_leaves_wide needs, 0... } (header word 1 is 0 in every narrow record) —, then nnodes
+//      DevTreeNodeW in postfix order.  op / arg / row / score / rmask lie where DevTreeNode has them; what a 64-bit word cannot say about a
+//      1024-node tree is said per CHILD: its parent, its place among the parent's children, the parent's operator and counter planes
+constexpr uint32_t TREE_WIDE_MAX_NODES = 1024; // the largest tree_max_nodes (k_tree_leaves_wide: a bit per node per thread in LDS)
+constexpr uint32_t TREE_WIDE_STACK = 64;       // words of a thread's evaluation stack (k_tree_eval_wide): a tree that needs more is left out
+constexpr uint32_t TREE_KIND_WIDE = 1;         // header word 1
+constexpr uint32_t TREE_NO_PARENT = 0xffffu;
+struct DevTreeNodeW {
+        uint8_t op;      // as DevTreeNode::op
+        uint8_t cbits;   // SOME: counter planes, ceil(log2(nkids + 1)); else 0
+        uint16_t parent; // node index; the root: TREE_NO_PARENT
+        uint32_t arg, row, score, rmask; // as in DevTreeNode
+        uint16_t ord;    // position among the parent's children (NOT / OPT: 0 = the required / main side)
+        uint16_t nkids;  // inner node: its children
+        uint16_t thr;    // SOME: the threshold (TRI_OP_SOME carries 12 bits of it)
+        uint8_t pop;     // the parent's op (the root: 0) ...
+        uint8_t pcbits;  // ... and its counter planes: how the node's value is folded into the accumulator beneath it
+        uint32_t pad;
+};
+static_assert(sizeof(DevTreeNodeW) == sizeof(DevTreeNode), "a wide record's nodes are eight words each too");
+TRI_HD constexpr uint32_t tree_counter_planes(const uint32_t nkids) { // bits that hold 0 .. nkids
+        uint32_t b = 0;
+        while ((1u << b) <= nkids)
+                ++b;
+        return b;
+}
 // the one-pass kinds (decode -> match -> score -> top-K inside one kernel: k_fused / k_planes); the others materialise docID sets
 TRI_HD constexpr bool task_onepass(const uint32_t kind) { return kind >= TASK_FUSED && kind <= TASK_PLANES8; }
 

@@ -57,7 +57,7 @@ void *tri_host_plan(void *hindex, const uint32_t *prog, uint64_t prog_len, const
                 uint64_t *slot = n == "dense_min_postings" ? &o.dense_min_postings : n == "dense_task_cost" ? &o.dense_task_cost : n == "fused" ? &o.fused
                                  : n == "fused_task_cost" ? &o.fused_task_cost : n == "fused_freq_cap" ? &o.fused_freq_cap : n == "fused_halfwords" ? &o.fused_halfwords
                                  : n == "account_needed_bytes" ? &o.account_needed_bytes : n == "planes" ? &o.planes : n == "planes_split" ? &o.planes_split
-                                 : n == "plane_div" ? &o.plane_div : n == "plane_max_bytes" ? &o.plane_max_bytes : n == "probe_max_blocks" ? &o.probe_max_blocks : n == "tree_max_bytes" ? &o.tree_max_bytes : n == "result_bitmaps" ? &o.result_bitmaps : n == "cand_task_cost" ? &o.cand_task_cost : n == "dense_window_cost" ? &o.dense_window_cost
+                                 : n == "plane_div" ? &o.plane_div : n == "plane_max_bytes" ? &o.plane_max_bytes : n == "probe_max_blocks" ? &o.probe_max_blocks : n == "tree_max_bytes" ? &o.tree_max_bytes : n == "tree_max_nodes" ? &o.tree_max_nodes : n == "tree_wide_min_nodes" ? &o.tree_wide_min_nodes : n == "result_bitmaps" ? &o.result_bitmaps : n == "cand_task_cost" ? &o.cand_task_cost : n == "dense_window_cost" ? &o.dense_window_cost
                                  : n == "cand_xcd" ? &o.cand_xcd : n == "planes_order" ? &o.planes_order : n == "pset_order" ? &o.pset_order : n == "scatter_bitmap_slack" ? &o.scatter_bitmap_slack : n == "phrase_task_div" ? &o.phrase_task_div : n == "plane_amortize" ? &o.plane_amortize : nullptr;
                 if (!slot) {
                         put_err(err, errcap, "unknown option " + n);
@@ -118,6 +118,8 @@ void tri_host_plan_summary(void *p, uint64_t *out /* [65] */, double *ms /* [4] 
         if (ms)
                 memcpy(ms, P.plan_ms, sizeof P.plan_ms);
 }
+// why the last left-out query was left out (what tri_batch_last_unsupported reports on the device side); "" when none was
+void tri_host_plan_last_unsupported(void *p, char *out, uint64_t cap) { put_err(out, cap, static_cast<HostPlan *>(p)->P.last_unsupported); }
 const uint8_t *tri_host_plan_block(void *p) { return static_cast<HostPlan *>(p)->P.block; }
 void tri_host_plan_query_maps(void *p, uint32_t *slot_of_query, int32_t *qstatus) {
         const BatchPlan &P = static_cast<HostPlan *>(p)->P;

@@ -48,8 +48,9 @@ __device__ __forceinline__ uint32_t tree_load(TreeNodes &sh, const uint32_t *__r
 __device__ __forceinline__ const uint32_t *tree_row(const DevTreeNode &nd, const uint32_t *__restrict__ trows, const uint32_t *__restrict__ prows, const uint32_t plw) {
         return (nd.row & TREE_ROW_PHRASE) ? prows + (size_t)(nd.row & ~TREE_ROW_PHRASE) * plw : trows + (size_t)nd.row * PL_PLANES * plw;
 }
-// sum over the workgroup (every thread calls it, every thread gets it)
-__device__ __forceinline__ uint32_t tree_block_sum(TreeNodes &sh, uint32_t v) {
+// sum over the workgroup (every thread calls it, every thread gets it; Sh: TreeNodes, or k_tree_wide.hpp's TreeWideNodes — anything with red[])
+template <class Sh>
+__device__ __forceinline__ uint32_t tree_block_sum(Sh &sh, uint32_t v) {
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1)
                 v += __shfl_xor(v, d, 64);
@@ -200,7 +201,8 @@ __global__ __launch_bounds__(TREE_WG) void k_tree_eval(const DevQuery *__restric
 }
 
 // matches of the chunks before `chunk` (every thread calls it)
-__device__ __forceinline__ uint32_t tree_chunk_base(TreeNodes &sh, const uint32_t *__restrict__ cc, const uint32_t chunk) {
+template <class Sh>
+__device__ __forceinline__ uint32_t tree_chunk_base(Sh &sh, const uint32_t *__restrict__ cc, const uint32_t chunk) {
         uint32_t s = 0;
         for (uint32_t c = threadIdx.x; c < chunk; c += TREE_WG)
                 s += cc[c];

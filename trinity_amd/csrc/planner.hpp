@@ -507,6 +507,18 @@ namespace trip {
                 });
         }
 
+        // ---- the TASK_TREE section: the queries with narrow records first, the wide ones (k_tree_wide.hpp) last, each part in the order the schedule gave it — the
+        //      narrow kernels are never handed a wide record (tree_load would clamp it to its first 64 nodes).  A batch without wide records: nothing moves
+        inline void split_tree_section(BatchPlan &P) {
+                if (!P.n_tree)
+                        return;
+                uint32_t *const ts = P.sched.p + sched_first(P, TASK_TREE);
+                auto narrow = [&](const uint32_t ti) { return P.tree[P.plan[P.tasks[ti].slot].fused_idx + 1] != TREE_KIND_WIDE; };
+                P.n_tree_wide = P.n_tree - (uint32_t)std::count_if(ts, ts + P.n_tree, narrow);
+                if (P.n_tree_wide && P.n_tree_wide < P.n_tree)
+                        std::stable_partition(ts, ts + P.n_tree, narrow);
+        }
+
         // ---- k_and's queues.  A candidate tile probes the planes of the query's other terms: ONE bit per candidate, a 64-byte sector of a 1.25 MB row
         //      each — in cost order the tasks in flight probe a hundred rows at once and every sector comes from HBM (cfg2: 2.9 GB per step of them).
         //      The section is cut into one queue per XCD (workgroups draw from the queue of the XCD they run on, and from the next ones when theirs is
@@ -614,6 +626,8 @@ inline int plan_batch(const HostIndex &ix, const PlanEnv &env, const PlanInput &
         static const bool dbg_plan = getenv("TRINITY_DEBUG_PLAN") != nullptr;
         const uint32_t mode = in.flags & (TRI_FLAG_DOCUMENTS_ONLY | TRI_FLAG_ACCUMULATED_SCORE | TRI_FLAG_MATCHED_TERMS);
         PlanState S{ix, env, env.opt, pool, P, err, Ctx{ix, env, in, mode == TRI_FLAG_ACCUMULATED_SCORE, mode == TRI_FLAG_MATCHED_TERMS, mode}, LapTimer{dbg_plan}};
+        if (env.opt.tree_max_nodes < TREE_MAX_NODES || env.opt.tree_max_nodes > TREE_WIDE_MAX_NODES)
+                return herr(err, TRI_ERR_INVALID, "tri_batch_create: option tree_max_nodes = %llu (%u .. %u)", (unsigned long long)env.opt.tree_max_nodes, TREE_MAX_NODES, TREE_WIDE_MAX_NODES);
         P.slot_of_query.assign(in.nq, UINT32_MAX);
         P.qstatus.assign(in.nq, TRI_OK);
         eligible_planes(S);
@@ -646,6 +660,7 @@ inline int plan_batch(const HostIndex &ix, const PlanEnv &env, const PlanInput &
         P.plan_ms[2] = ms_since(t0);
         place_schedule(S);
         deal_cand_queues(S);
+        split_tree_section(P);
         order_phrase_tasks(P);
         P.sparse_cap = (P.sparse_cap + 63u) & ~63u;
         S.dbg.lap("sched+rest");

@@ -769,7 +769,11 @@ namespace trip {
                 struct PhraseLeaf {
                         uint32_t node, t0, n, tok;
                 };
-                std::vector<DevTreeNode> tn;
+                struct HNode { // a node before it is written as a DevTreeNode or a DevTreeNodeW
+                        uint32_t op = 0, thr = 0, arg = 0, row = 0, score = 0xffffffffu, rmask = 0, parent = UINT32_MAX, ord = 0, nkids = 0, kid0 = 0, kid1 = 0;
+                };
+                const uint32_t max_nodes = (uint32_t)C.env.opt.tree_max_nodes;
+                std::vector<HNode> tn;
                 std::vector<PhraseLeaf> phl;
                 std::vector<uint32_t> phterms, leaf_tok; // phrase leaves' terms; per node, the program token of a leaf
                 std::vector<uint8_t> positive;           // per node: a leaf an iterator of the tree can report (not under an excluded side)
@@ -778,9 +782,7 @@ namespace trip {
                 std::function<int(int, bool)> emit = [&](const int ni, const bool pos) -> int {
                         const PNode x = S.nodes[ni];
                         const int *kd = S.kids(x);
-                        DevTreeNode d{};
-                        d.parent = 0xff;
-                        d.score = 0xffffffffu;
+                        HNode d;
                         uint32_t tok = x.tok;
                         if (x.op == TRI_OP_TERM || (x.op == TRI_OP_PHRASE && x.kid_n == 1)) {
                                 const PNode &t = x.op == TRI_OP_TERM ? x : S.nodes[kd[0]];
@@ -795,22 +797,22 @@ namespace trip {
                                 for (uint32_t k = 0; k < x.kid_n; ++k)
                                         phterms.push_back(S.nodes[kd[k]].term);
                         } else {
-                                d.op = (uint8_t)x.op;
-                                d.thr = x.op == TRI_OP_SOME ? (uint8_t)std::min<uint32_t>(x.term, 255) : 0;
+                                d.op = x.op;
+                                d.thr = x.op == TRI_OP_SOME ? x.term : 0;
                                 std::vector<int> kids;
                                 for (uint32_t k = 0; k < x.kid_n && ok; ++k)
                                         kids.push_back(emit(kd[k], pos && !(x.op == TRI_OP_NOT && k == 1)));
-                                if (!ok || tn.size() + 1 > TREE_MAX_NODES)
+                                if (!ok || tn.size() + 1 > max_nodes)
                                         return ok = false, -1;
                                 for (size_t k = 0; k < kids.size(); ++k) {
-                                        d.kids |= 1ull << kids[k];
-                                        tn[kids[k]].parent = (uint8_t)tn.size();
-                                        tn[kids[k]].ord = (uint8_t)k;
+                                        tn[kids[k]].parent = (uint32_t)tn.size();
+                                        tn[kids[k]].ord = (uint32_t)k;
                                 }
+                                d.nkids = (uint32_t)kids.size();
                                 if (x.op == TRI_OP_NOT || x.op == TRI_OP_OPT)
-                                        d.kid0 = (uint8_t)kids[0], d.kid1 = (uint8_t)kids[1];
+                                        d.kid0 = (uint32_t)kids[0], d.kid1 = (uint32_t)kids[1];
                         }
-                        if (tn.size() + 1 > TREE_MAX_NODES)
+                        if (tn.size() + 1 > max_nodes)
                                 return ok = false, -1;
                         tn.push_back(d);
                         leaf_tok.push_back(tok);
@@ -818,23 +820,46 @@ namespace trip {
                         return (int)tn.size() - 1;
                 };
                 emit(root, true);
-                if (!ok)
-                        return leave_out("a tree of more than 64 nodes");
+                if (!ok) {
+                        char why[64];
+                        snprintf(why, sizeof why, "a tree of more than %u nodes", max_nodes);
+                        return leave_out(why);
+                }
                 const uint32_t nn = (uint32_t)tn.size();
+                // a WIDE record (k_tree_wide.hpp) for what the narrow kernels do not hold, or from tree_wide_min_nodes on.  What its kernels need per thread: the
+                // evaluation stack holds, while a leaf is read, the accumulator of every ancestor — a word, or a matchsome's counter planes —, the counter stack
+                // of k_tree_leaves_wide a count per ancestor: the deepest path decides
+                const bool wide = nn > TREE_MAX_NODES || nn >= C.env.opt.tree_wide_min_nodes;
+                uint32_t stack_need = 0, depth_need = 0;
+                if (wide) {
+                        std::vector<uint32_t> words(nn, 0), depth(nn, 0);
+                        for (uint32_t i = nn; i-- > 0;) {
+                                if (tn[i].parent != UINT32_MAX) {
+                                        const HNode &p = tn[tn[i].parent];
+                                        words[i] = words[tn[i].parent] + (p.op == TRI_OP_SOME ? tree_counter_planes(p.nkids) : 1u);
+                                        depth[i] = depth[tn[i].parent] + 1;
+                                }
+                                if (!tn[i].nkids)
+                                        stack_need = std::max(stack_need, words[i]), depth_need = std::max(depth_need, depth[i]);
+                        }
+                        if (stack_need > TREE_WIDE_STACK) {
+                                char why[96];
+                                snprintf(why, sizeof why, "a tree that needs more than %u words of evaluation stack (it needs %u)", TREE_WIDE_STACK, stack_need);
+                                return leave_out(why);
+                        }
+                }
                 if (C.scored && std::find(positive.begin(), positive.end(), 1) == positive.end())
                         return leave_out("a tree without a scoring leaf");
                 // the value of every node for a document that holds none of the leaves, and an upper bound of a node's matches
                 uint64_t ub_root = 0;
                 {
-                        uint64_t val = 0;
-                        std::vector<uint64_t> ub(nn, 0);
+                        std::vector<uint8_t> val(nn, 0);
+                        std::vector<uint32_t> ntrue(nn, 0);           // per inner node: its children that hold
+                        std::vector<uint64_t> ub(nn, 0), sum(nn, 0), mn(nn, UINT64_MAX); // ... the sum and the least of their bounds
                         for (uint32_t i = 0; i < nn; ++i) {
-                                const DevTreeNode &d = tn[i];
+                                const HNode &d = tn[i];
                                 bool v = false;
-                                uint64_t u = 0, sum = 0, mn = UINT64_MAX;
-                                for (uint32_t k = 0; k < i; ++k)
-                                        if ((d.kids >> k) & 1ull)
-                                                sum += ub[k], mn = std::min(mn, ub[k]);
+                                uint64_t u = 0;
                                 switch (d.op) {
                                         case TRI_OP_TERM:
                                                 u = ix.terms[d.arg].documents;
@@ -847,30 +872,32 @@ namespace trip {
                                                                         u = std::min<uint64_t>(u, ix.terms[phterms[p.t0 + k]].documents);
                                                 break;
                                         case TRI_OP_AND:
-                                                v = (val & d.kids) == d.kids;
-                                                u = mn;
+                                                v = ntrue[i] == d.nkids;
+                                                u = mn[i];
                                                 break;
                                         case TRI_OP_OR:
-                                                v = (val & d.kids) != 0;
-                                                u = sum;
+                                                v = ntrue[i] != 0;
+                                                u = sum[i];
                                                 break;
                                         case TRI_OP_SOME:
-                                                v = (uint32_t)__builtin_popcountll(val & d.kids) >= d.thr;
-                                                u = sum;
+                                                v = ntrue[i] >= d.thr;
+                                                u = sum[i];
                                                 break;
                                         case TRI_OP_NOT:
-                                                v = ((val >> d.kid0) & 1ull) && !((val >> d.kid1) & 1ull);
+                                                v = val[d.kid0] && !val[d.kid1];
                                                 u = ub[d.kid0];
                                                 break;
                                         case TRI_OP_OPT:
-                                                v = (val >> d.kid0) & 1ull;
+                                                v = val[d.kid0];
                                                 u = ub[d.kid0];
                                                 break;
                                 }
-                                val |= (uint64_t)v << i;
+                                val[i] = v;
                                 ub[i] = std::min<uint64_t>(u, ix.max_doc);
+                                if (d.parent != UINT32_MAX)
+                                        ntrue[d.parent] += v, sum[d.parent] += ub[i], mn[d.parent] = std::min(mn[d.parent], ub[i]);
                         }
-                        if ((val >> (nn - 1)) & 1ull)
+                        if (val[nn - 1])
                                 return leave_out("a tree that matches documents holding none of its terms cannot be enumerated from postings");
                         if (ub[nn - 1] > 0xffffffffull)
                                 return leave_out("a tree of more than 2^32 possible matches");
@@ -977,10 +1004,45 @@ namespace trip {
                                 }
                         }
                 }
+                t.tree_wide = wide;
                 t.q.fused_idx = (uint32_t)f.treepool.size();
                 f.treepool.resize(f.treepool.size() + TREE_HDR_WORDS + nn * (sizeof(DevTreeNode) / 4), 0u);
-                f.treepool[t.q.fused_idx] = nn;
-                memcpy(&f.treepool[t.q.fused_idx + TREE_HDR_WORDS], tn.data(), nn * sizeof(DevTreeNode));
+                uint32_t *const rec = &f.treepool[t.q.fused_idx];
+                rec[0] = nn;
+                if (wide) {
+                        rec[1] = TREE_KIND_WIDE, rec[2] = stack_need, rec[3] = depth_need;
+                        DevTreeNodeW *out = reinterpret_cast<DevTreeNodeW *>(rec + TREE_HDR_WORDS);
+                        for (uint32_t i = 0; i < nn; ++i) {
+                                const HNode &h = tn[i];
+                                DevTreeNodeW d{};
+                                d.op = (uint8_t)h.op;
+                                d.cbits = h.op == TRI_OP_SOME ? (uint8_t)tree_counter_planes(h.nkids) : 0;
+                                d.parent = h.parent == UINT32_MAX ? (uint16_t)TREE_NO_PARENT : (uint16_t)h.parent;
+                                d.arg = h.arg, d.row = h.row, d.score = h.score, d.rmask = h.rmask;
+                                d.ord = (uint16_t)h.ord, d.nkids = (uint16_t)h.nkids, d.thr = (uint16_t)std::min<uint32_t>(h.thr, 0xffffu);
+                                if (h.parent != UINT32_MAX) {
+                                        d.pop = (uint8_t)tn[h.parent].op;
+                                        d.pcbits = tn[h.parent].op == TRI_OP_SOME ? (uint8_t)tree_counter_planes(tn[h.parent].nkids) : 0;
+                                }
+                                out[i] = d;
+                        }
+                } else {
+                        DevTreeNode *out = reinterpret_cast<DevTreeNode *>(rec + TREE_HDR_WORDS);
+                        for (uint32_t i = 0; i < nn; ++i) {
+                                const HNode &h = tn[i];
+                                DevTreeNode d{};
+                                d.op = (uint8_t)h.op;
+                                d.parent = h.parent == UINT32_MAX ? 0xff : (uint8_t)h.parent;
+                                d.ord = (uint8_t)h.ord;
+                                d.thr = (uint8_t)std::min<uint32_t>(h.thr, 255);
+                                d.arg = h.arg, d.row = h.row, d.score = h.score, d.rmask = h.rmask;
+                                if (h.op == TRI_OP_NOT || h.op == TRI_OP_OPT)
+                                        d.kid0 = (uint8_t)h.kid0, d.kid1 = (uint8_t)h.kid1;
+                                out[i] = d;
+                        }
+                        for (uint32_t i = 0; i + 1 < nn; ++i)
+                                out[tn[i].parent].kids |= 1ull << i;
+                }
                 f.tmp.push_back(t);
                 return TRI_OK;
         }

@@ -59,6 +59,10 @@ struct tri_options {
         uint64_t result_bitmaps = 1;           // DocumentsOnly: a bitmap-window query whose expected matches outnumber the words of a bitmap over its docID range
                                                // delivers its docID set AS that bitmap (RESULT_BITMAP, dev_structs.hpp); 0: always ascending docIDs
         uint64_t tree_max_bytes = 16ull << 30; // scratch budget of a batch's TASK_TREE queries (a PL_PLANES-plane row per distinct term leaf, a plane per phrase leaf and per query)
+        uint64_t tree_max_nodes = 64;          // a tree of more than this many nodes is left out (TRI_ERR_UNSUPPORTED per query).  64 (TREE_MAX_NODES: all the narrow kernels of k_tree.hpp
+                                               // hold) .. 1024 (TREE_WIDE_MAX_NODES); any other value fails tri_batch_create.  Trees above 64 nodes run in k_tree_wide.hpp's kernels
+        uint64_t tree_wide_min_nodes = 65;     // a TASK_TREE query of at least this many nodes gets a wide record and k_tree_wide.hpp's kernels; 0: every tree query does — not a tuning
+                                               // knob: it lets the tests run the trees they have reference answers for through the wide kernels
         uint64_t probe_max_blocks = 0;         // > 0: a lead list of at most this many blocks against lists that all have planes runs in k_probe (a wave per task) instead of
                                                // k_and's candidate tiles.  Off by default — measured at cfg2 (step ms / k_probe / k_and): 0: 2.14 / - / 0.78; 64: 2.25 / 0.15 / 0.75;
                                                // 256: 2.26 / 0.22 / 0.70; 1024: 2.35 / 0.41 / 0.59; all: 2.55 / 0.82 / 0.41 — k_and's time is its tail, not its task count
@@ -155,6 +159,7 @@ struct BatchPlan : trip::PlanCounters {
         Span<uint32_t> tree_terms;  // the distinct term leaves of the batch's TASK_TREE queries, ascending: term -> row of the batch's tree rows
         Span<uint32_t> tree_hidden; // hidden phrase queries: their plan slots (position: the row of the batch's phrase rows)
         uint32_t n_tree = 0;        // TASK_TREE tasks (the last section of sched)
+        uint32_t n_tree_wide = 0;   // ... of them the last n_tree_wide have WIDE records (k_tree_wide.hpp); the narrow ones come first
         uint64_t tree_scratch_bytes = 0;
         std::vector<uint32_t> slot_of_query; // caller query -> plan slot (UINT32_MAX: can never match)
         std::vector<int32_t> qstatus;        // per caller query: TRI_OK, or why the planner left it out of the batch (it then reports no matches)
@@ -287,6 +292,7 @@ namespace trip {
                 bool tree;    // ... one the truth table does not hold: TASK_TREE (q.fused_idx: its record in the fragment's treepool; tree_ub: its matches at most)
                 bool hidden;  // a phrase evaluated for a TASK_TREE query of the batch (no caller query of its own); hidden_ord: which of the fragment's
                 uint64_t tree_ub;
+                bool tree_wide; // ... with a wide record (DevTreeNodeW)
                 uint32_t hidden_ord;
                 // execution class (second half of the first pass)
                 uint64_t sumdf, lead_docs;

@@ -495,6 +495,7 @@ struct tri_batch : BatchPlan {
 #include "k_phrase.hpp"
 #include "k_rich.hpp"
 #include "k_tree.hpp"
+#include "k_tree_wide.hpp"
 #include "k_commit.hpp"
 #include "k_lencode.hpp"
 #include "filtered_kernels.hpp"
@@ -569,7 +570,7 @@ namespace {
                              {"planes_rebuild", &tri_options::planes_rebuild},
                              {"cand_xcd", &tri_options::cand_xcd},
                              {"plan_threads", &tri_options::plan_threads},
-                             {"probe_max_blocks", &tri_options::probe_max_blocks}, {"phrase_task_div", &tri_options::phrase_task_div}, {"plan_hot_us", &tri_options::plan_hot_us}, {"plan_pin", &tri_options::plan_pin}, {"planes_order", &tri_options::planes_order}, {"pset_order", &tri_options::pset_order}, {"scatter_bitmap_slack", &tri_options::scatter_bitmap_slack}, {"tree_max_bytes", &tri_options::tree_max_bytes}, {"result_bitmaps", &tri_options::result_bitmaps}, {"cand_task_cost", &tri_options::cand_task_cost}, {"dense_window_cost", &tri_options::dense_window_cost}};
+                             {"probe_max_blocks", &tri_options::probe_max_blocks}, {"phrase_task_div", &tri_options::phrase_task_div}, {"plan_hot_us", &tri_options::plan_hot_us}, {"plan_pin", &tri_options::plan_pin}, {"planes_order", &tri_options::planes_order}, {"pset_order", &tri_options::pset_order}, {"scatter_bitmap_slack", &tri_options::scatter_bitmap_slack}, {"tree_max_bytes", &tri_options::tree_max_bytes}, {"tree_max_nodes", &tri_options::tree_max_nodes}, {"tree_wide_min_nodes", &tri_options::tree_wide_min_nodes}, {"result_bitmaps", &tri_options::result_bitmaps}, {"cand_task_cost", &tri_options::cand_task_cost}, {"dense_window_cost", &tri_options::dense_window_cost}};
                 for (const auto &e : table)
                         if (!strcmp(e.name, name))
                                 return &(o.*(e.field));
@@ -1449,19 +1450,34 @@ static int run_trees(tri_batch *b) {
                 }
                 const bool scored_run = b->flags & TRI_FLAG_ACCUMULATED_SCORE, rich_run = b->flags & TRI_FLAG_MATCHED_TERMS;
                 double *tscores = scored_run ? (b->topk ? b->d_tree_scores : b->d_all_scores) : nullptr;
-                for (uint32_t y0 = 0; y0 < b->n_tree; y0 += 65535u) {
-                        const dim3 grid(nchunks, std::min(65535u, b->n_tree - y0));
+                // the section's narrow records first (k_tree.hpp), then its wide ones (k_tree_wide.hpp: split_tree_section put them last); k_tree_expand reads no record
+                const uint32_t n_narrow = b->n_tree - b->n_tree_wide;
+                for (uint32_t y0 = 0; y0 < b->n_tree;) {
+                        const bool wide = y0 >= n_narrow;
+                        const uint32_t ny = std::min(65535u, (wide ? b->n_tree : n_narrow) - y0);
+                        const dim3 grid(nchunks, ny);
                         uint32_t *qbits = b->d_tree_qbits + (size_t)y0 * plw, *cc = b->d_tree_cc + (size_t)y0 * nchunks;
-                        hipLaunchKernelGGL(k_tree_eval, grid, dim3(TREE_WG), 0, dev->stream, b->dev_at(b->plan), b->dev_at(b->tasks), tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows,
-                                           (const uint32_t *)b->d_tree_prows, (const uint32_t *)ix->d_masked, qbits, cc, plw, filter_sel(b));
+#define TREE_EVAL_ARGS b->dev_at(b->plan), b->dev_at(b->tasks), tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows, (const uint32_t *)b->d_tree_prows, (const uint32_t *)ix->d_masked, qbits, cc, plw, filter_sel(b)
+                        if (wide)
+                                hipLaunchKernelGGL(k_tree_eval_wide, grid, dim3(TREE_WG), 0, dev->stream, TREE_EVAL_ARGS);
+                        else
+                                hipLaunchKernelGGL(k_tree_eval, grid, dim3(TREE_WG), 0, dev->stream, TREE_EVAL_ARGS);
+#undef TREE_EVAL_ARGS
                         hipLaunchKernelGGL(k_tree_expand, grid, dim3(TREE_WG), 0, dev->stream, b->dev_at(b->plan), b->dev_at(b->tasks), tsched + y0, (const uint32_t *)qbits, (const uint32_t *)cc,
                                            b->d_out, b->d_counts, plw);
-                        if (scored_run || rich_run)
-                                TRI_LAUNCH(k_tree_leaves, ix->codec, grid, dim3(TREE_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks),
-                                           tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows, (const uint32_t *)b->d_tree_prows, (const uint32_t *)cc, (const uint32_t *)b->d_out,
-                                           (const uint32_t *)b->d_counts, (const double *)b->dev_at(b->sweights), (const double *)b->d_pscore, tscores, rich_run ? b->d_rich_allow : nullptr,
-                                           plw, b->similarity);
+                        if (scored_run || rich_run) {
+#define TREE_LEAVES_ARGS                                                                                                                                                                   \
+        ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows,                          \
+                (const uint32_t *)b->d_tree_prows, (const uint32_t *)cc, (const uint32_t *)b->d_out, (const uint32_t *)b->d_counts, (const double *)b->dev_at(b->sweights),               \
+                (const double *)b->d_pscore, tscores, rich_run ? b->d_rich_allow : nullptr, plw, b->similarity
+                                if (wide)
+                                        TRI_LAUNCH(k_tree_leaves_wide, ix->codec, grid, dim3(TREE_WG), dev->stream, TREE_LEAVES_ARGS);
+                                else
+                                        TRI_LAUNCH(k_tree_leaves, ix->codec, grid, dim3(TREE_WG), dev->stream, TREE_LEAVES_ARGS);
+#undef TREE_LEAVES_ARGS
+                        }
                         HIP_TRY(hipGetLastError());
+                        y0 += ny;
                 }
                 if (scored_run && b->topk) {
                         hipLaunchKernelGGL(k_tree_topk, dim3(b->n_tree), dim3(AND_WG), 0, dev->stream, tsched, b->dev_at(b->tasks), (const uint32_t *)b->d_out, (const uint32_t *)b->d_counts,

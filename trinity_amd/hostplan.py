@@ -21,6 +21,11 @@ TASK_CAND, TASK_DENSE, TASK_FUSED, TASK_FUSED16, TASK_FUSED_GEN, TASK_PLANES, TA
 DEV_TREE_NODE = np.dtype([("op", "u1"), ("parent", "u1"), ("ord", "u1"), ("thr", "u1"), ("arg", "<u4"), ("row", "<u4"), ("score", "<u4"), ("rmask", "<u4"),
                           ("kid0", "u1"), ("kid1", "u1"), ("pad", "u1", 2), ("kids", "<u8")])  # fmt: skip
 TREE_HDR_WORDS = 8
+# a WIDE record's nodes (csrc/dev_structs.hpp DevTreeNodeW; header word 1 = TREE_KIND_WIDE, word 2 the evaluation stack's words, word 3 the counter depth)
+DEV_TREE_NODE_WIDE = np.dtype([("op", "u1"), ("cbits", "u1"), ("parent", "<u2"), ("arg", "<u4"), ("row", "<u4"), ("score", "<u4"), ("rmask", "<u4"),
+                               ("ord", "<u2"), ("nkids", "<u2"), ("thr", "<u2"), ("pop", "u1"), ("pcbits", "u1"), ("pad", "<u4")])  # fmt: skip
+TREE_KIND_NARROW, TREE_KIND_WIDE = 0, 1
+TREE_NO_PARENT = 0xFFFF
 DEV_UNIT = np.dtype([("out_off", "<u8"), ("begin", "<u4"), ("end", "<u4"), ("tix", "<u4"), ("nterms", "<u4"), ("term_base", "<u4"), ("first", "<u4"), ("tt", "<u4", 4), ("row", "<u4", 4)])
 SCHED_ORDER = [TASK_DENSE, TASK_PSET, TASK_PROBE, TASK_CAND, TASK_FUSED, TASK_FUSED16, TASK_FUSED_GEN, TASK_PLANES, TASK_PLANES8, TASK_TREE]
 
@@ -39,6 +44,8 @@ def _lib():
         L.tri_host_plan_block.restype = C.POINTER(C.c_uint8)
         L.tri_host_plan_block.argtypes = [vp]
         L.tri_host_plan_query_maps.argtypes = [vp, vp, vp]
+        L.tri_host_plan_last_unsupported.argtypes = [vp, C.c_char_p, C.c_uint64]
+        L.tri_host_plan_last_unsupported.restype = None
         L.tri_host_pfor128_group.argtypes = [vp, vp, C.POINTER(C.c_uint32), vp, C.POINTER(C.c_uint32)]
         L.tri_host_pfor128_group.restype = None
         for f in (L.tri_host_lucene_encode, L.tri_host_lucene_encode_units):
@@ -97,6 +104,9 @@ class HostPlan:
         self.slot_of_query = np.zeros(max(1, self.nq), dtype=np.uint32)
         self.qstatus = np.zeros(max(1, self.nq), dtype=np.int32)
         _lib().tri_host_plan_query_maps(self.h, self.slot_of_query.ctypes.data, self.qstatus.ctypes.data)
+        why = C.create_string_buffer(600)
+        _lib().tri_host_plan_last_unsupported(self.h, why, 600)
+        self.last_unsupported = why.value.decode()  # why the last left-out query was left out ("" when none was)
 
     def _view(self, off, n, dtype):
         dt = np.dtype(dtype)
@@ -153,6 +163,23 @@ class HostPlan:
         at = int(self.plan[slot]["fused_idx"])
         n = int(words[at])
         return words[at + TREE_HDR_WORDS : at + TREE_HDR_WORDS + 8 * n].view(DEV_TREE_NODE)
+
+    def tree_kind(self, slot):
+        """(kind, node count) of the record of the TASK_TREE query in plan slot `slot`: TREE_KIND_NARROW (tree_nodes reads it) or TREE_KIND_WIDE (tree_nodes_wide)."""
+        words = self._view("off_tree", self.s["n_tree_words"], "<u4")
+        at = int(self.plan[slot]["fused_idx"])
+        return int(words[at + 1]), int(words[at])
+
+    def tree_header(self, slot):
+        """The TREE_HDR_WORDS header words of that record."""
+        words = self._view("off_tree", self.s["n_tree_words"], "<u4")
+        at = int(self.plan[slot]["fused_idx"])
+        return words[at : at + TREE_HDR_WORDS]
+
+    def tree_nodes_wide(self, slot):
+        """The DevTreeNodeW records of a TASK_TREE query with a wide record."""
+        assert self.tree_kind(slot)[0] == TREE_KIND_WIDE
+        return self.tree_nodes(slot).view(DEV_TREE_NODE_WIDE)
 
     def close(self):
         if self.h:
