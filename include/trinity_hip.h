@@ -29,7 +29,8 @@ extern "C" {
                              8: tri_batch_docsets (every query's docID set in one call), tri_merge_lucene, option planes_rebuild;
                              9: tri_dev_memory (HBM in use), tri_batch_docsets_mixed (dense sets delivered as bitmap words), two planner contexts per handle (two threads may compile at once), plane rows built by need;
                                 within 9: tri_filter_create / tri_filter_from_docset / tri_filter_destroy / tri_batch_set_filters (per-query document filters on the device);
-                                within 9: options tree_max_nodes / tree_wide_min_nodes (query trees of up to 1024 nodes; no new export, no struct grew) */
+                                within 9: options tree_max_nodes / tree_wide_min_nodes (query trees of up to 1024 nodes; no new export, no struct grew);
+                                within 9: option rich_max_terms, tri_batch_query_terms_wide / tri_batch_matched_terms_wide (the default mode reports up to 64 matched terms per query; no struct grew) */
 
 /* status codes */
 #define TRI_OK 0
@@ -205,7 +206,15 @@ void *tri_dev_stream(tri_dev *);
  *                         kernels hold (csrc/k_tree.hpp).  64 .. 1024: trees above 64 nodes — a flat OR of 70 terms, an AND of 22 three-term ORs, a matchsome
  *                         over 100 alternatives — run in the wide tree kernels (csrc/k_tree_wide.hpp).  Any other value fails tri_batch_create with
  *                         TRI_ERR_INVALID.  Still left out: a tree whose evaluation needs more than 64 stack words (a word per nested AND / OR / NOT /
- *                         <optional> on the deepest path, ceil(log2(children + 1)) per nested matchsome), more than 16 reportable terms in the default mode
+ *                         <optional> on the deepest path, ceil(log2(children + 1)) per nested matchsome), more reportable terms in the default mode than option
+ *                         rich_max_terms allows
+ *   "rich_max_terms"      default mode (TRI_FLAG_MATCHED_TERMS): a query of more reportable terms than this is left out of the batch (TRI_ERR_UNSUPPORTED per
+ *                         query).  Default 16; 16 .. 64, any other value fails tri_batch_create with TRI_ERR_INVALID.  A query of 17 .. 64 reportable terms
+ *                         (a WIDE-REPORT query: a flat OR of 20 synonyms, an OR of 40 two-term conjunctions, a matchsome over 60 alternatives) runs as a
+ *                         tree query and is read through tri_batch_query_terms_wide / tri_batch_matched_terms_wide.  Off by default because of what such
+ *                         a query reserves: 2 x (its terms rounded up to 8) bytes of frequency row + 8 bytes of masks per OUTPUT SLOT — the tree's upper
+ *                         bound, not its matches: up to 136 bytes a slot; a flat OR of 64 head terms over 10 M documents reserves on the order of 1.3 GB.  A
+ *                         create that cannot get the memory fails with TRI_ERR_NOMEM.  Batches whose queries all report at most 16 terms are unaffected
  *   "tree_wide_min_nodes" a tree query of at least this many nodes runs in the wide kernels (default 65: only the trees the narrow ones cannot hold; 0: every
  *                         tree query).  Results do not depend on it; it is there so that the wide kernels can be checked on trees with pinned answers
  * ("fused" also takes 2: only pure unions run in one pass.)  The options are read when a batch is CREATED, except the two overlap_* ones and planes_rebuild,
@@ -291,7 +300,8 @@ int tri_decode_terms(tri_index *, const uint32_t *terms, size_t n, uint32_t *doc
 int tri_batch_create(tri_index *, const uint32_t *prog, size_t prog_len, const tri_query *queries, size_t nq,
                      const double *weights, uint32_t flags, uint32_t topk, int similarity, tri_batch **out);
 /* A query whose shape the planner does not lower (today: a tree of more nodes than option tree_max_nodes allows — 64 by default, up to 1024 —
- * or one whose evaluation needs more than 64 stack words, more than 16 reportable terms in the default mode, a tree that matches documents
+ * or one whose evaluation needs more than 64 stack words, more reportable terms in the default mode than option rich_max_terms allows — 16 by
+ * default, up to 64 —, a tree that matches documents
  * holding none of its terms) does NOT fail tri_batch_create: the query is left out of the batch — it reports no matches — and its status says so, so that one such
  * query among thousands costs the caller one CPU span (exec.cpp:509-1517 for that query alone), not the batch.  status[q]: TRI_OK or
  * TRI_ERR_UNSUPPORTED; tri_batch_info.unsupported_queries counts them; tri_last_error() after tri_batch_create describes the last one.
@@ -335,7 +345,7 @@ int tri_batch_docsets_mixed(tri_batch *, uint32_t *out, size_t cap /* words */, 
  * (id, score) stream MatchedIndexDocumentsFilter::consider(id, score) receives (matches.h:169; exec.cpp:1322-1341) */
 int tri_batch_scores(tri_batch *, size_t q, double *out, size_t cap, size_t *n);
 /* TRI_FLAG_MATCHED_TERMS batches.  tri_batch_query_terms: the query's reportable terms (every TERM / PHRASE-member of the
- * program outside the excluded side of a NOT, distinct, in order of first appearance; at most 16), i.e. the meaning of bit k
+ * program outside the excluded side of a NOT, distinct, in order of first appearance; at most 16 — a query of more, option rich_max_terms, is read through the _wide calls below), i.e. the meaning of bit k
  * and column k below.  tri_batch_matched_terms, for the n matches of query q in ascending docID order (n and the docIDs as
  * returned by tri_batch_docset): present[i] bit k = term k matched document i; freq[i * nterms + k] = its frequency there
  * (term_hits::freq, 0 when absent); positions = the hits' positions, match-major then term-minor (the run of (i, k) starts at
@@ -343,7 +353,14 @@ int tri_batch_scores(tri_batch *, size_t q, double *out, size_t cap, size_t *n);
 int tri_batch_query_terms(tri_batch *, size_t q, uint32_t *terms /* [16] */, uint32_t *nterms);
 int tri_batch_matched_terms(tri_batch *, size_t q, uint32_t *present /* [n] */, uint16_t *freq /* [n * nterms] */, uint16_t *positions,
                             size_t pos_cap, size_t *npos);
-/* TRI_FLAG_MATCHED_TERMS | TRI_FLAG_HIT_PAYLOADS batches: the payloads of query q's hits, parallel to `positions` above (same order,
+/* ... the same two calls with 64-bit masks: up to 64 reportable terms (option rich_max_terms).  Same conventions — the sizing call with NULLs, dense
+ * [n * nterms] frequencies, positions match-major then term-minor.  They serve EVERY query of a TRI_FLAG_MATCHED_TERMS batch (a query of at most 16 terms: its
+ * mask zero-extended).  The two calls above, on a query of more than 16 reportable terms, fail with TRI_ERR_INVALID and write nothing: never past terms[16],
+ * never a truncated mask. */
+int tri_batch_query_terms_wide(tri_batch *, size_t q, uint32_t *terms /* [64] */, uint32_t *nterms);
+int tri_batch_matched_terms_wide(tri_batch *, size_t q, uint64_t *present /* [n] */, uint16_t *freq /* [n * nterms] */, uint16_t *positions,
+                                 size_t pos_cap, size_t *npos);
+/* TRI_FLAG_MATCHED_TERMS | TRI_FLAG_HIT_PAYLOADS batches: the payloads of query q's hits, parallel to `positions` above (of either call; same order,
  * *n == *npos): lens[i] = term_hit::payloadLen, payloads[i] = term_hit::payload — the word as materialize_hits leaves it, i.e. only its
  * first lens[i] bytes belong to this hit (google_codec.cpp:533-594).  Pass lens == payloads == NULL to learn *n. */
 int tri_batch_matched_payloads(tri_batch *, size_t q, uint8_t *lens, uint64_t *payloads, size_t cap, size_t *n);

@@ -91,8 +91,23 @@ def build_mirror_filter_test(force=False):
     return MIRROR_FILTER_BIN
 
 
+MIRROR_WIDE_TERMS_SRC = os.path.join(ROOT, "tests", "cpp", "host_mirror_wide_terms_test.cpp")
+MIRROR_WIDE_TERMS_BIN = os.path.join(ROOT, "tests", "cpp", "host_mirror_wide_terms_test")
+
+
+def build_mirror_wide_terms_test(force=False):
+    """exec_query's default mode on queries of more than 16 terms (csrc/host/trinity_gpu.hpp: option rich_max_terms, the _wide result calls) compiled into its driver;
+    in-tree, so that it travels to the GPU box, where tests/test_host_mirror_wide_terms.py runs it."""
+    deps = [MIRROR_WIDE_TERMS_SRC, os.path.join(PKG, "csrc", "host", "trinity_gpu.hpp"), os.path.join(PKG, "csrc", "host", "google_encoder.hpp"), os.path.join(ROOT, "include", "trinity_hip.h")]
+    if force or _newer(MIRROR_WIDE_TERMS_BIN, deps):
+        build_hip()
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", MIRROR_WIDE_TERMS_BIN, MIRROR_WIDE_TERMS_SRC, "-L" + PKG, "-ltrinity_hip", "-Wl,-rpath,$ORIGIN/../../trinity_amd"]
+        subprocess.run(cmd, check=True)
+    return MIRROR_WIDE_TERMS_BIN
+
+
 def build_all(force=False):
-    return build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force)
+    return build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force), build_mirror_wide_terms_test(force)
 
 
 def kernels_stamp():

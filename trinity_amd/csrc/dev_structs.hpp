@@ -141,7 +141,8 @@ struct DevTreeNode {
         uint32_t score; // leaf: its scorer (index into the query's sterms / sweights slice), 0xffffffff: none (an excluded side scores nothing)
         uint32_t rmask; // leaf, default mode: the reportable terms (bits into the query's sterms slice) reported where the leaf sits on the document
         uint8_t kid0, kid1, pad0, pad1; // NOT / OPT: the two sides
-        uint64_t kids;  // inner node: bit k = node k is a child
+        uint64_t kids;  // inner node: bit k = node k is a child.  A leaf has no children: its low word holds bits 32 .. 63 of the leaf's report mask
+                        // (a wide-report query, option rich_max_terms; 0 for every query of at most 16 reportable terms)
 };
 static_assert(sizeof(DevTreeNode) == 32, "eight words per node");
 // ---- a WIDE record (k_tree_wide.hpp): a tree of more than TREE_MAX_NODES nodes (option tree_max_nodes lets them in), or any tree once option
@@ -163,9 +164,20 @@ struct DevTreeNodeW {
         uint16_t thr;    // SOME: the threshold (TRI_OP_SOME carries 12 bits of it)
         uint8_t pop;     // the parent's op (the root: 0) ...
         uint8_t pcbits;  // ... and its counter planes: how the node's value is folded into the accumulator beneath it
-        uint32_t pad;
+        uint32_t pad;    // leaf: bits 32 .. 63 of its report mask (a wide-report query; else 0)
 };
 static_assert(sizeof(DevTreeNodeW) == sizeof(DevTreeNode), "a wide record's nodes are eight words each too");
+// ---- default mode, WIDE-REPORT queries (option rich_max_terms): a query of RICH_NARROW_TERMS + 1 .. RICH_WIDE_TERMS reportable terms — always a TASK_TREE
+//      query.  Its matches' frequency rows live in a second array, `stride` cells apart (nscore rounded up to a multiple of 8: rows are 16-byte
+//      aligned), and the high halves of its per-match masks (present, allow) in second arrays that hold the wide-report queries' slots only.  One
+//      record per plan slot (BatchPlan::rich_wide; a batch without such a query has no table): stride == 0 says "not a wide-report query"
+constexpr uint32_t RICH_NARROW_TERMS = 16, RICH_WIDE_TERMS = 64;
+struct DevRichWide {
+        uint64_t cells; // the row of the query's first output slot, in 16-bit cells of the wide frequency array
+        uint64_t slots; // the query's first output slot in the high-half mask arrays
+        uint32_t stride, pad;
+};
+static_assert(sizeof(DevRichWide) == 24, "three 8-byte words per plan slot");
 TRI_HD constexpr uint32_t tree_counter_planes(const uint32_t nkids) { // bits that hold 0 .. nkids
         uint32_t b = 0;
         while ((1u << b) <= nkids)

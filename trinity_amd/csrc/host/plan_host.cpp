@@ -58,7 +58,7 @@ void *tri_host_plan(void *hindex, const uint32_t *prog, uint64_t prog_len, const
                                  : n == "fused_task_cost" ? &o.fused_task_cost : n == "fused_freq_cap" ? &o.fused_freq_cap : n == "fused_halfwords" ? &o.fused_halfwords
                                  : n == "account_needed_bytes" ? &o.account_needed_bytes : n == "planes" ? &o.planes : n == "planes_split" ? &o.planes_split
                                  : n == "plane_div" ? &o.plane_div : n == "plane_max_bytes" ? &o.plane_max_bytes : n == "probe_max_blocks" ? &o.probe_max_blocks : n == "tree_max_bytes" ? &o.tree_max_bytes : n == "tree_max_nodes" ? &o.tree_max_nodes : n == "tree_wide_min_nodes" ? &o.tree_wide_min_nodes : n == "result_bitmaps" ? &o.result_bitmaps : n == "cand_task_cost" ? &o.cand_task_cost : n == "dense_window_cost" ? &o.dense_window_cost
-                                 : n == "cand_xcd" ? &o.cand_xcd : n == "planes_order" ? &o.planes_order : n == "pset_order" ? &o.pset_order : n == "scatter_bitmap_slack" ? &o.scatter_bitmap_slack : n == "phrase_task_div" ? &o.phrase_task_div : n == "plane_amortize" ? &o.plane_amortize : nullptr;
+                                 : n == "cand_xcd" ? &o.cand_xcd : n == "planes_order" ? &o.planes_order : n == "pset_order" ? &o.pset_order : n == "scatter_bitmap_slack" ? &o.scatter_bitmap_slack : n == "phrase_task_div" ? &o.phrase_task_div : n == "plane_amortize" ? &o.plane_amortize : n == "rich_max_terms" ? &o.rich_max_terms : nullptr;
                 if (!slot) {
                         put_err(err, errcap, "unknown option " + n);
                         return nullptr;
@@ -117,6 +117,13 @@ void tri_host_plan_summary(void *p, uint64_t *out /* [65] */, double *ms /* [4] 
         memcpy(out, v, sizeof v);
         if (ms)
                 memcpy(ms, P.plan_ms, sizeof P.plan_ms);
+}
+// default mode, wide-report queries (option rich_max_terms): out[0..] = the side table's entries (0: the batch has none) and offset, the offset of k_rich's own
+// schedule, the tasks of wide-report queries, the wide frequency array's 16-bit cells, the high-half mask arrays' slots, sizeof(DevRichWide)
+void tri_host_plan_rich_wide(void *p, uint64_t *out /* [7] */) {
+        const BatchPlan &P = static_cast<HostPlan *>(p)->P;
+        const uint64_t v[] = {P.rich_wide.size(), P.rich_wide.off, P.rich_sched.off, P.n_rich_wide, P.rich_wide_cells, P.rich_wide_slots, sizeof(DevRichWide)};
+        memcpy(out, v, sizeof v);
 }
 // why the last left-out query was left out (what tri_batch_last_unsupported reports on the device side); "" when none was
 void tri_host_plan_last_unsupported(void *p, char *out, uint64_t cap) { put_err(out, cap, static_cast<HostPlan *>(p)->P.last_unsupported); }

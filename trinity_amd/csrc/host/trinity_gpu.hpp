@@ -458,6 +458,9 @@ namespace trinity_amd {
                 IndexSource(const IndexSource &) = delete;
 
                 tri_index *handle() const noexcept { return ix; }
+                // a planner / launch option of the source's device handle (tri_dev_set_option: read when a batch is created) — "rich_max_terms" = 64 lets the
+                // default mode deliver matched_documents for queries of up to 64 terms
+                void set_option(const char *name, const uint64_t value) { check(tri_dev_set_option(dev, name, value)); }
                 const std::string &term_name(const uint32_t row) const { return names.at(row); }
                 // The documents of this source that newer sources of the collection have updated or deleted — what
                 // IndexSourcesCollection::commit() derives per source (index_source.cpp:3-30) and exec_query tests through
@@ -752,12 +755,14 @@ namespace trinity_amd {
                 std::vector<docid_t> ids(n);
                 if (n)
                         check(tri_batch_docset(b.get(), 0, ids.data(), n, &n));
-                uint32_t terms[16], nt = 0;
-                check(tri_batch_query_terms(b.get(), 0, terms, &nt));
-                check(tri_batch_matched_terms(b.get(), 0, nullptr, nullptr, nullptr, 0, &npos));
-                std::vector<uint32_t> present(n);
+                // (the _wide calls: 64-bit masks — a query of up to 64 reportable terms once the caller has set option rich_max_terms on the device; they serve
+                //  every query, a narrow one's mask zero-extended)
+                uint32_t terms[64], nt = 0;
+                check(tri_batch_query_terms_wide(b.get(), 0, terms, &nt));
+                check(tri_batch_matched_terms_wide(b.get(), 0, nullptr, nullptr, nullptr, 0, &npos));
+                std::vector<uint64_t> present(n);
                 std::vector<uint16_t> freq(n * std::max<uint32_t>(nt, 1)), pos(npos);
-                check(tri_batch_matched_terms(b.get(), 0, present.data(), freq.data(), pos.data(), pos.size(), &npos));
+                check(tri_batch_matched_terms_wide(b.get(), 0, present.data(), freq.data(), pos.data(), pos.size(), &npos));
                 std::vector<query_term_ctx> qctx(nt);
                 for (uint32_t k = 0; k < nt; ++k) {
                         qctx[k].term.id = exec_term_id_t(k + 1);
@@ -774,7 +779,7 @@ namespace trinity_amd {
                                 md.matchedTerms = mts.data();
                                 for (uint32_t k = 0; k < nt; ++k) {
                                         const uint32_t f = freq[i * nt + k];
-                                        if ((present[i] >> k) & 1u) {
+                                        if ((present[i] >> k) & 1ull) {
                                                 store[k].resize(f);
                                                 for (uint32_t h = 0; h < f; ++h)
                                                         store[k][h].pos = pos[at + h];

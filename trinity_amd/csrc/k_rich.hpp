@@ -17,8 +17,25 @@
 //   WRITE  (after the host has turned the tasks' totals into pool offsets) positions of (match m, term k) go to
 //          pool[task_base + sum of freq over (m' < m, all k') + sum of freq over (m, k' < k)] — match-major, term-minor, so a
 //          task's (and therefore a query's) hits are one contiguous run and the offsets follow from the freqs alone
-// slot = task.out_off + index in the segment; R = the batch's widest reportable-term count.
+// slot = task.out_off + index in the segment; R = the batch's widest reportable-term count among its NARROW queries (at most RICH_NARROW_TERMS terms).
+//
+// WIDE (k_rich_wide; option rich_max_terms): the tasks of the batch's WIDE-REPORT queries — RICH_NARROW_TERMS + 1 .. RICH_WIDE_TERMS reportable
+// terms, always TASK_TREE queries — in a launch of their own over their section of the batch's rich schedule (BatchPlan::rich_sched); k_rich runs what it
+// always ran, unchanged (the two kernels share one body, rich_tasks: k_rich keeps its arguments, and with them its registers).  A wide-report query's masks are 64 bits — term k's bit lies in word k >> 5: the low words where they
+// always were (present[slot], allow[slot]), the high ones in second arrays that hold the wide-report queries' slots only — and its frequency rows lie in a
+// second array at the query's own base and stride (DevRichWide, one per plan slot: nscore rounded up to 8 cells), so that the batch-wide R stays what the
+// narrow queries need.  The WRITE pass does not sum the row cell by cell: freq is zero wherever present is clear, so the hits of a match before term k are
+// the cells of the SET bits of its present mask below k, and the row total those of every set bit — a match that holds 5 of 64 terms costs 5 loads per
+// (match, term), not 64 (the dense walk: up to ~2000 two-byte loads per match).  Chosen over 16-byte loads of the whole row because the cost then follows
+// the terms the document holds rather than the query's width, and needs no second copy of the row in registers.
 constexpr uint32_t RICH_TILE = 2048;
+
+struct RichWideArgs { // WIDE only (the narrow instantiations never read it)
+        uint32_t *present_hi;      // bits 32 .. 63 of a match's present mask, at DevRichWide::slots + its index in the query's region
+        const uint32_t *allow_hi;  // ... of the mask the tree leaf kernels left
+        uint16_t *freq;            // the wide frequency rows: DevRichWide::cells + index * stride + k
+        const DevRichWide *tab;    // per plan slot
+};
 
 struct RichShared {
         uint32_t cand[RICH_TILE];
@@ -30,15 +47,16 @@ struct RichShared {
         uint32_t hits; // COUNT: hits of the task so far
 };
 
-template <int CODEC, bool WRITE>
-__global__ __launch_bounds__(AND_WG) void k_rich(const uint8_t *__restrict__ index, const uint8_t *__restrict__ hits, const uint32_t *__restrict__ blk_hits,
-                                                 const uint32_t *__restrict__ hdir, const uint32_t *__restrict__ blk_last, const uint32_t *__restrict__ blk_off,
-                                                 const DevTerm *__restrict__ terms, const DevQuery *__restrict__ plan, const DevTask *__restrict__ tasks,
-                                                 const uint32_t *__restrict__ sched, const uint32_t *__restrict__ rterms, const uint32_t ntasks,
-                                                 uint32_t *__restrict__ ticket, const uint32_t *__restrict__ out, const uint32_t *__restrict__ counts, const uint32_t R,
-                                                 uint32_t *__restrict__ present, uint16_t *__restrict__ freq, uint32_t *__restrict__ task_hits,
-                                                 const uint64_t *__restrict__ task_pos_base, uint16_t *__restrict__ pool, const uint32_t *__restrict__ allow,
-                                                 uint8_t *__restrict__ pool_plen, uint64_t *__restrict__ pool_payload) {
+// the kernels' body (k_rich: WIDE = false, wd unused; k_rich_wide: WIDE = true) — every thread of the workgroup calls it
+template <int CODEC, bool WRITE, bool WIDE>
+__device__ __forceinline__ void rich_tasks(const uint8_t *__restrict__ index, const uint8_t *__restrict__ hits, const uint32_t *__restrict__ blk_hits,
+                                           const uint32_t *__restrict__ hdir, const uint32_t *__restrict__ blk_last, const uint32_t *__restrict__ blk_off,
+                                           const DevTerm *__restrict__ terms, const DevQuery *__restrict__ plan, const DevTask *__restrict__ tasks,
+                                           const uint32_t *__restrict__ sched, const uint32_t *__restrict__ rterms, const uint32_t ntasks,
+                                           uint32_t *__restrict__ ticket, const uint32_t *__restrict__ out, const uint32_t *__restrict__ counts, const uint32_t R,
+                                           uint32_t *__restrict__ present, uint16_t *__restrict__ freq, uint32_t *__restrict__ task_hits,
+                                           const uint64_t *__restrict__ task_pos_base, uint16_t *__restrict__ pool, const uint32_t *__restrict__ allow,
+                                           uint8_t *__restrict__ pool_plen, uint64_t *__restrict__ pool_payload, const RichWideArgs &wd) {
         // pool_plen / pool_payload (or null; TRI_FLAG_HIT_PAYLOADS): per hit, parallel to `pool`, term_hit::payloadLen and ::payload as
         // Google::Decoder::materialize_hits leaves them (google_codec.cpp:533-594) — the payload word is carried from hit to hit within a
         // document and only its first payloadLen bytes are rewritten, exactly as the reference's local variable is
@@ -63,6 +81,22 @@ __global__ __launch_bounds__(AND_WG) void k_rich(const uint8_t *__restrict__ ind
                 const DevQuery q = plan[task.slot];
                 const uint32_t M = counts[tix];
                 const uint32_t *seg = out + task.out_off;
+                // WIDE: the task's first match in the high-half mask arrays and its row in the wide frequency array
+                uint64_t wslot0 = 0, wcell0 = 0;
+                uint32_t wstride = 0;
+                if constexpr (WIDE) {
+                        const DevRichWide rw = wd.tab[task.slot];
+                        wstride = uni(rw.stride);
+                        wslot0 = rw.slots + (task.out_off - q.out_off);
+                        wcell0 = rw.cells + (task.out_off - q.out_off) * wstride;
+                }
+                // WIDE: the 64-bit present mask of the match at index m of the task's segment
+                auto present64 = [&](const uint32_t m) -> uint64_t {
+                        if constexpr (WIDE)
+                                return (uint64_t)present[(uint64_t)task.out_off + m] | ((uint64_t)wd.present_hi[wslot0 + m] << 32);
+                        else
+                                return 0ull;
+                };
                 sh.hits = 0;
                 uint32_t tile_base = 0; // WRITE: hits of the task before this tile
                 __syncthreads();
@@ -80,9 +114,15 @@ __global__ __launch_bounds__(AND_WG) void k_rich(const uint8_t *__restrict__ ind
                                         const uint32_t j = tid * PER + i;
                                         uint32_t f = 0;
                                         if (j < C) {
-                                                const uint64_t row = ((uint64_t)task.out_off + tb + j) * R;
-                                                for (uint32_t k = 0; k < q.nscore; ++k)
-                                                        f += freq[row + k];
+                                                if constexpr (WIDE) { // the cells of the terms the match holds: every other one is zero
+                                                        const uint16_t *row = wd.freq + wcell0 + (uint64_t)(tb + j) * wstride;
+                                                        for (uint64_t pm = present64(tb + j); pm; pm &= pm - 1ull)
+                                                                f += row[__builtin_ctzll(pm)];
+                                                } else {
+                                                        const uint64_t row = ((uint64_t)task.out_off + tb + j) * R;
+                                                        for (uint32_t k = 0; k < q.nscore; ++k)
+                                                                f += freq[row + k];
+                                                }
                                         }
                                         rowsum[i] = run;
                                         run += f;
@@ -137,7 +177,12 @@ __global__ __launch_bounds__(AND_WG) void k_rich(const uint8_t *__restrict__ ind
                                                         ptr = lo;
                                                         cv = ptr < C ? sh.cand[ptr] : 0xffffffffu;
                                                 }
-                                                if (cv == doc && (!allow || ((allow[(uint64_t)task.out_off + tb + ptr] >> ti) & 1u))) {
+                                                bool sits = cv == doc;
+                                                if constexpr (WIDE) // (term ti's bit: word ti >> 5 of the mask the leaf kernel left)
+                                                        sits = sits && (!allow || ((((ti >> 5) ? wd.allow_hi[wslot0 + tb + ptr] : allow[(uint64_t)task.out_off + tb + ptr]) >> (ti & 31u)) & 1u));
+                                                else
+                                                        sits = sits && (!allow || ((allow[(uint64_t)task.out_off + tb + ptr] >> ti) & 1u));
+                                                if (sits) {
                                                         mask |= 1u << i;
                                                         sh.mptr[nm++][tid] = (uint16_t)ptr;
                                                 }
@@ -152,9 +197,15 @@ __global__ __launch_bounds__(AND_WG) void k_rich(const uint8_t *__restrict__ ind
                                                 for (uint32_t i = 0; i < n && (mask >> i); ++i) {
                                                         const uint32_t f = fs.next() & HitStream<CODEC>::FREQ_MASK & 0xffffu; // term_hits::freq is tokenpos_t
                                                         if ((mask >> i) & 1u) {
-                                                                const uint64_t slot = (uint64_t)task.out_off + tb + sh.mptr[nm++][tid];
-                                                                atomicOr(&present[slot], 1u << ti);
-                                                                freq[slot * R + ti] = (uint16_t)f;
+                                                                if constexpr (WIDE) {
+                                                                        const uint32_t m = tb + sh.mptr[nm++][tid];
+                                                                        atomicOr((ti >> 5) ? &wd.present_hi[wslot0 + m] : &present[(uint64_t)task.out_off + m], 1u << (ti & 31u));
+                                                                        wd.freq[wcell0 + (uint64_t)m * wstride + ti] = (uint16_t)f;
+                                                                } else {
+                                                                        const uint64_t slot = (uint64_t)task.out_off + tb + sh.mptr[nm++][tid];
+                                                                        atomicOr(&present[slot], 1u << ti);
+                                                                        freq[slot * R + ti] = (uint16_t)f;
+                                                                }
                                                                 sum += f;
                                                         }
                                                 }
@@ -164,10 +215,16 @@ __global__ __launch_bounds__(AND_WG) void k_rich(const uint8_t *__restrict__ ind
                                         // WRITE: where this (match, term) run starts = the task's base + the match's row offset + the freqs of
                                         // the row's earlier terms
                                         auto dest = [&](const uint32_t m) -> uint16_t * {
-                                                const uint64_t row = ((uint64_t)task.out_off + tb + m) * R;
                                                 uint32_t before = 0;
-                                                for (uint32_t k = 0; k < ti; ++k)
-                                                        before += freq[row + k];
+                                                if constexpr (WIDE) { // the match's terms before ti: the set bits of its present mask below ti
+                                                        const uint16_t *row = wd.freq + wcell0 + (uint64_t)(tb + m) * wstride;
+                                                        for (uint64_t pm = present64(tb + m) & ((1ull << ti) - 1ull); pm; pm &= pm - 1ull)
+                                                                before += row[__builtin_ctzll(pm)];
+                                                } else {
+                                                        const uint64_t row = ((uint64_t)task.out_off + tb + m) * R;
+                                                        for (uint32_t k = 0; k < ti; ++k)
+                                                                before += freq[row + k];
+                                                }
                                                 return pool + task_pos_base[tix] + sh.rowoff[m] + before;
                                         };
                                         if constexpr (CODEC == CODEC_GOOGLE) {
@@ -292,3 +349,24 @@ __global__ __launch_bounds__(AND_WG) void k_rich(const uint8_t *__restrict__ ind
                 __syncthreads();
         }
 }
+
+#define RICH_PARAMS                                                                                                                                                                         \
+        const uint8_t *__restrict__ index, const uint8_t *__restrict__ hits, const uint32_t *__restrict__ blk_hits, const uint32_t *__restrict__ hdir,                                    \
+                const uint32_t *__restrict__ blk_last, const uint32_t *__restrict__ blk_off, const DevTerm *__restrict__ terms, const DevQuery *__restrict__ plan,                        \
+                const DevTask *__restrict__ tasks, const uint32_t *__restrict__ sched, const uint32_t *__restrict__ rterms, const uint32_t ntasks, uint32_t *__restrict__ ticket,         \
+                const uint32_t *__restrict__ out, const uint32_t *__restrict__ counts, const uint32_t R, uint32_t *__restrict__ present, uint16_t *__restrict__ freq,                     \
+                uint32_t *__restrict__ task_hits, const uint64_t *__restrict__ task_pos_base, uint16_t *__restrict__ pool, const uint32_t *__restrict__ allow,                            \
+                uint8_t *__restrict__ pool_plen, uint64_t *__restrict__ pool_payload
+#define RICH_PASS index, hits, blk_hits, hdir, blk_last, blk_off, terms, plan, tasks, sched, rterms, ntasks, ticket, out, counts, R, present, freq, task_hits, task_pos_base, pool, allow, pool_plen, pool_payload
+// every task of a batch without wide-report queries; of one with them: every task but theirs (the first part of BatchPlan::rich_sched)
+template <int CODEC, bool WRITE>
+__global__ __launch_bounds__(AND_WG) void k_rich(RICH_PARAMS) {
+        rich_tasks<CODEC, WRITE, false>(RICH_PASS, RichWideArgs{});
+}
+// the wide-report queries' tasks (the last part of BatchPlan::rich_sched)
+template <int CODEC, bool WRITE>
+__global__ __launch_bounds__(AND_WG) void k_rich_wide(RICH_PARAMS, const RichWideArgs wd) {
+        rich_tasks<CODEC, WRITE, true>(RICH_PASS, wd);
+}
+#undef RICH_PARAMS
+#undef RICH_PASS

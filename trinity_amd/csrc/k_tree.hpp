@@ -239,10 +239,17 @@ __global__ __launch_bounds__(TREE_WG) void k_tree_leaves(const uint8_t *__restri
                                                          const uint32_t *__restrict__ sched, const uint32_t *__restrict__ tree, const uint32_t *__restrict__ trows,
                                                          const uint32_t *__restrict__ prows, const uint32_t *__restrict__ chunk_counts, const uint32_t *__restrict__ out,
                                                          const uint32_t *__restrict__ counts, const double *__restrict__ sweights, const double *__restrict__ pscore,
-                                                         double *__restrict__ all_scores, uint32_t *__restrict__ allow, const uint32_t plw, const int sim) {
+                                                         double *__restrict__ all_scores, uint32_t *__restrict__ allow, const uint32_t plw, const int sim,
+                                                         uint32_t *__restrict__ allow_hi, const DevRichWide *__restrict__ rwide) {
+        // allow_hi / rwide (or null; default-mode batches with wide-report queries, option rich_max_terms): a wide-report query's matches get the high word of
+        // the report mask too — at the query's own slots of the high-half array (rwide[slot]; stride 0: not such a query, nothing is stored)
         __shared__ TreeNodes sh;
         const uint32_t tid = threadIdx.x, chunk = blockIdx.x, nchunks = gridDim.x, qi = blockIdx.y;
-        const DevQuery q = plan[tasks[sched[qi]].slot];
+        const uint32_t slot = tasks[sched[qi]].slot;
+        const DevQuery q = plan[slot];
+        uint32_t *hi = nullptr;
+        if (allow_hi && rwide[slot].stride)
+                hi = allow_hi + rwide[slot].slots;
         const uint32_t nn = tree_load(sh, tree + q.fused_idx);
         const uint32_t *cc = chunk_counts + (size_t)qi * nchunks;
         const uint32_t base = tree_chunk_base(sh, cc, chunk), cnt = uni(cc[chunk]);
@@ -289,12 +296,13 @@ __global__ __launch_bounds__(TREE_WG) void k_tree_leaves(const uint8_t *__restri
                         reach |= (uint64_t)(((reach >> nd.parent) & 1ull) && via) << n;
                 }
                 double s = 0.0;
-                uint32_t rep = 0;
+                uint32_t rep = 0, rep_hi = 0;
                 for (uint32_t n = 0; n < nn; ++n) {
                         const DevTreeNode &nd = sh.node[n];
                         if (!((reach >> n) & 1ull) || (nd.op != TRI_OP_TERM && nd.op != TRI_OP_PHRASE))
                                 continue;
                         rep |= nd.rmask;
+                        rep_hi |= (uint32_t)nd.kids; // (a leaf's `kids`: bits 32 .. 63 of its report mask)
                         if (!all_scores || nd.score == 0xffffffffu)
                                 continue;
                         if (nd.op == TRI_OP_TERM) {
@@ -322,6 +330,8 @@ __global__ __launch_bounds__(TREE_WG) void k_tree_leaves(const uint8_t *__restri
                         all_scores[o] = s;
                 if (allow)
                         allow[o] = rep;
+                if (hi)
+                        hi[base + j] = rep_hi; // (base + j < q.out_cap: the query's share of the array)
         }
 }
 

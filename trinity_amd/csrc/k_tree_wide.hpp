@@ -21,7 +21,7 @@
 #pragma once
 
 struct TreeWideNodes {
-        uint4 node4[2 * TREE_WIDE_MAX_NODES]; // DevTreeNodeW as two 16-byte halves: a { op | cbits << 8 | parent << 16, arg, row, score }, b { rmask, ord | nkids << 16, thr | pop << 16 | pcbits << 24, 0 }
+        uint4 node4[2 * TREE_WIDE_MAX_NODES]; // DevTreeNodeW as two 16-byte halves: a { op | cbits << 8 | parent << 16, arg, row, score }, b { rmask, ord | nkids << 16, thr | pop << 16 | pcbits << 24, pad (a leaf: the report mask's high word) }
         uint32_t red[TREE_WG / 64];
 };
 static_assert(sizeof(DevTreeNodeW) == 2 * sizeof(uint4), "a node is two 16-byte loads");
@@ -135,10 +135,16 @@ __global__ __launch_bounds__(TREE_WG) void k_tree_leaves_wide(const uint8_t *__r
                                                               const uint32_t *__restrict__ sched, const uint32_t *__restrict__ tree, const uint32_t *__restrict__ trows,
                                                               const uint32_t *__restrict__ prows, const uint32_t *__restrict__ chunk_counts, const uint32_t *__restrict__ out,
                                                               const uint32_t *__restrict__ counts, const double *__restrict__ sweights, const double *__restrict__ pscore,
-                                                              double *__restrict__ all_scores, uint32_t *__restrict__ allow, const uint32_t plw, const int sim) {
+                                                              double *__restrict__ all_scores, uint32_t *__restrict__ allow, const uint32_t plw, const int sim,
+                                                              uint32_t *__restrict__ allow_hi, const DevRichWide *__restrict__ rwide) {
+        // (allow_hi / rwide: as in k_tree_leaves — the high word of a wide-report query's report masks)
         __shared__ TreeLeavesWideShared sh;
         const uint32_t tid = threadIdx.x, chunk = blockIdx.x, nchunks = gridDim.x, qi = blockIdx.y;
-        const DevQuery q = plan[tasks[sched[qi]].slot];
+        const uint32_t slot = tasks[sched[qi]].slot;
+        const DevQuery q = plan[slot];
+        uint32_t *hi = nullptr;
+        if (allow_hi && rwide[slot].stride)
+                hi = allow_hi + rwide[slot].slots;
         const uint32_t nn = tree_wide_load(sh.t, tree + q.fused_idx);
         const uint32_t *cc = chunk_counts + (size_t)qi * nchunks;
         const uint32_t base = tree_chunk_base(sh.t, cc, chunk), cnt = uni(cc[chunk]);
@@ -197,7 +203,7 @@ __global__ __launch_bounds__(TREE_WG) void k_tree_leaves_wide(const uint8_t *__r
                                 sh.bits[n >> 5][tid] = cur;
                 }
                 double s = 0.0;
-                uint32_t rep = 0;
+                uint32_t rep = 0, rep_hi = 0;
                 for (uint32_t n = 0; n < nn; ++n) {
                         if ((n & 31u) == 0u)
                                 cur = sh.bits[n >> 5][tid];
@@ -205,7 +211,8 @@ __global__ __launch_bounds__(TREE_WG) void k_tree_leaves_wide(const uint8_t *__r
                         const uint32_t op = a.x & 0xffu;
                         if (!((cur >> (n & 31u)) & 1u) || (op != TRI_OP_TERM && op != TRI_OP_PHRASE))
                                 continue;
-                        rep |= sh.t.node4[2 * n + 1].x; // rmask
+                        rep |= sh.t.node4[2 * n + 1].x;    // rmask
+                        rep_hi |= sh.t.node4[2 * n + 1].w; // ... and its bits 32 .. 63 (DevTreeNodeW::pad)
                         if (!all_scores || a.w == 0xffffffffu)
                                 continue;
                         if (op == TRI_OP_TERM) {
@@ -233,5 +240,7 @@ __global__ __launch_bounds__(TREE_WG) void k_tree_leaves_wide(const uint8_t *__r
                         all_scores[o] = s;
                 if (allow)
                         allow[o] = rep;
+                if (hi)
+                        hi[base + j] = rep_hi; // (base + j < q.out_cap: the query's share of the array)
         }
 }

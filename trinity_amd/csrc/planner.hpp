@@ -193,6 +193,8 @@ namespace trip {
                 if (n.qterms > 0xfffffff0ull || n.sterms > 0xfffffff0ull || n.tasks > 0xfffffff0ull || n.pterms > 0xfffffff0ull)
                         return herr(S.err, TRI_ERR_UNSUPPORTED, "tri_batch_create: the batch exceeds 2^32 terms or tasks: split it");
                 P.out_capacity = off;
+                if (P.rich_wide_queries) // (default mode with wide-report queries: their side table and k_rich's own schedule — place_rich_wide)
+                        n.rich_wide = n.plan, n.rich_sched = n.tasks;
                 std::sort(S.tree_terms.begin(), S.tree_terms.end());
                 S.tree_terms.erase(std::unique(S.tree_terms.begin(), S.tree_terms.end()), S.tree_terms.end());
                 n.tree_terms = S.tree_terms.size();
@@ -519,6 +521,28 @@ namespace trip {
                         std::stable_partition(ts, ts + P.n_tree, narrow);
         }
 
+        // ---- default mode with wide-report queries (option rich_max_terms): the side table — per plan slot where the query's frequency rows (stride = nscore
+        //      rounded up to 8 cells: 16-byte rows) and high mask words lie, query after query in plan order, nothing for the other queries — and k_rich's own
+        //      schedule: sched's order, the wide-report queries' tasks moved behind everything else (the wide instantiation's launch)
+        inline void place_rich_wide(BatchPlan &P) {
+                if (P.rich_wide.empty())
+                        return;
+                uint64_t cells = 0, slots = 0;
+                for (size_t i = 0; i < P.plan.size(); ++i) {
+                        const DevQuery &q = P.plan[i];
+                        DevRichWide w{};
+                        if (q.nscore > RICH_NARROW_TERMS) {
+                                w.cells = cells, w.slots = slots, w.stride = (q.nscore + 7u) & ~7u;
+                                cells += (uint64_t)q.out_cap * w.stride, slots += q.out_cap;
+                                P.n_rich_wide += q.ntasks;
+                        }
+                        P.rich_wide[i] = w;
+                }
+                P.rich_wide_cells = cells, P.rich_wide_slots = slots;
+                std::copy(P.sched.begin(), P.sched.end(), P.rich_sched.begin());
+                std::stable_partition(P.rich_sched.begin(), P.rich_sched.end(), [&](const uint32_t ti) { return P.rich_wide[P.tasks[ti].slot].stride == 0; });
+        }
+
         // ---- k_and's queues.  A candidate tile probes the planes of the query's other terms: ONE bit per candidate, a 64-byte sector of a 1.25 MB row
         //      each — in cost order the tasks in flight probe a hundred rows at once and every sector comes from HBM (cfg2: 2.9 GB per step of them).
         //      The section is cut into one queue per XCD (workgroups draw from the queue of the XCD they run on, and from the next ones when theirs is
@@ -628,6 +652,8 @@ inline int plan_batch(const HostIndex &ix, const PlanEnv &env, const PlanInput &
         PlanState S{ix, env, env.opt, pool, P, err, Ctx{ix, env, in, mode == TRI_FLAG_ACCUMULATED_SCORE, mode == TRI_FLAG_MATCHED_TERMS, mode}, LapTimer{dbg_plan}};
         if (env.opt.tree_max_nodes < TREE_MAX_NODES || env.opt.tree_max_nodes > TREE_WIDE_MAX_NODES)
                 return herr(err, TRI_ERR_INVALID, "tri_batch_create: option tree_max_nodes = %llu (%u .. %u)", (unsigned long long)env.opt.tree_max_nodes, TREE_MAX_NODES, TREE_WIDE_MAX_NODES);
+        if (env.opt.rich_max_terms < RICH_NARROW_TERMS || env.opt.rich_max_terms > RICH_WIDE_TERMS)
+                return herr(err, TRI_ERR_INVALID, "tri_batch_create: option rich_max_terms = %llu (%u .. %u)", (unsigned long long)env.opt.rich_max_terms, RICH_NARROW_TERMS, RICH_WIDE_TERMS);
         P.slot_of_query.assign(in.nq, UINT32_MAX);
         P.qstatus.assign(in.nq, TRI_OK);
         eligible_planes(S);
@@ -661,6 +687,7 @@ inline int plan_batch(const HostIndex &ix, const PlanEnv &env, const PlanInput &
         place_schedule(S);
         deal_cand_queues(S);
         split_tree_section(P);
+        place_rich_wide(P);
         order_phrase_tasks(P);
         P.sparse_cap = (P.sparse_cap + 63u) & ~63u;
         S.dbg.lap("sched+rest");

@@ -677,9 +677,12 @@ namespace trip {
                 S.rt.clear();
                 if (rich) {
                         reportable_terms(S, prog, plen);
-                        if (S.rt.size() > 16) {
+                        if (S.rt.size() > RICH_NARROW_TERMS) {
+                                // (a wide-report query — option rich_max_terms — is always a TASK_TREE query: the tree path holds its 64-bit report masks)
+                                if (S.rt.size() <= C.env.opt.rich_max_terms)
+                                        return lower_tree(C, f, qi, prog, plen, wq, root);
                                 f.left_out.push_back(qi);
-                                herr(f.err, TRI_ERR_UNSUPPORTED, "query %zu: more than 16 reportable terms", qi);
+                                herr(f.err, TRI_ERR_UNSUPPORTED, "query %zu: more than %u reportable terms", qi, (unsigned)C.env.opt.rich_max_terms);
                                 return TRI_OK;
                         }
                 }
@@ -770,7 +773,7 @@ namespace trip {
                         uint32_t node, t0, n, tok;
                 };
                 struct HNode { // a node before it is written as a DevTreeNode or a DevTreeNodeW
-                        uint32_t op = 0, thr = 0, arg = 0, row = 0, score = 0xffffffffu, rmask = 0, parent = UINT32_MAX, ord = 0, nkids = 0, kid0 = 0, kid1 = 0;
+                        uint32_t op = 0, thr = 0, arg = 0, row = 0, score = 0xffffffffu, rmask = 0, rmask_hi = 0, parent = UINT32_MAX, ord = 0, nkids = 0, kid0 = 0, kid1 = 0;
                 };
                 const uint32_t max_nodes = (uint32_t)C.env.opt.tree_max_nodes;
                 std::vector<HNode> tn;
@@ -924,16 +927,21 @@ namespace trip {
                                 if (std::find(rt.begin(), rt.end(), x) == rt.end() && is_pos(x))
                                         rt.push_back(x);
                         }
-                        if (rt.size() > 16)
-                                return leave_out("more than 16 reportable terms");
-                        auto bit_of = [&](uint32_t term) { return 1u << (uint32_t)(std::find(rt.begin(), rt.end(), term) - rt.begin()); };
+                        if (rt.size() > C.env.opt.rich_max_terms) {
+                                char why[64];
+                                snprintf(why, sizeof why, "more than %u reportable terms", (unsigned)C.env.opt.rich_max_terms);
+                                return leave_out(why);
+                        }
+                        // a leaf's report mask: 64 bits, the low word in rmask, the high one in rmask_hi (a phrase's terms may fall on both sides of bit 32)
+                        auto bit_of = [&](uint32_t term) { return 1ull << (uint32_t)(std::find(rt.begin(), rt.end(), term) - rt.begin()); };
+                        auto report = [&](HNode &h, const uint64_t m) { h.rmask |= (uint32_t)m, h.rmask_hi |= (uint32_t)(m >> 32); };
                         for (uint32_t i = 0; i < nn; ++i)
                                 if (positive[i] && tn[i].op == TRI_OP_TERM)
-                                        tn[i].rmask = bit_of(tn[i].arg);
+                                        report(tn[i], bit_of(tn[i].arg));
                         for (const PhraseLeaf &p : phl)
                                 if (positive[p.node])
                                         for (uint32_t k = 0; k < p.n; ++k)
-                                                tn[p.node].rmask |= bit_of(phterms[p.t0 + k]);
+                                                report(tn[p.node], bit_of(phterms[p.t0 + k]));
                 }
                 if (!phl.empty() && ix.codec == TRI_CODEC_LUCENE && !ix.has_hdir)
                         return herr(f.err, TRI_ERR_INVALID, "query %zu: phrase over a LUCENE segment that was uploaded without hits.data", qi);
@@ -984,7 +992,10 @@ namespace trip {
                                 f.term_bytes += ix.hitbytes[x];
                         }
                         t.q.nscore = (uint32_t)rt.size();
-                        f.rich_R = std::max<uint32_t>(f.rich_R, t.q.nscore);
+                        if (t.q.nscore > RICH_NARROW_TERMS) // a wide-report query: rows of its own (BatchPlan::rich_wide), the batch-wide R stays the narrow queries'
+                                ++f.rich_wide_queries;
+                        else
+                                f.rich_R = std::max<uint32_t>(f.rich_R, t.q.nscore);
                         f.rich_allow = true;
                 } else if (C.scored) {
                         // one scorer per positive leaf, summed in tree order (docset_iterators_scorers.cpp:38-228)
@@ -1020,6 +1031,7 @@ namespace trip {
                                 d.parent = h.parent == UINT32_MAX ? (uint16_t)TREE_NO_PARENT : (uint16_t)h.parent;
                                 d.arg = h.arg, d.row = h.row, d.score = h.score, d.rmask = h.rmask;
                                 d.ord = (uint16_t)h.ord, d.nkids = (uint16_t)h.nkids, d.thr = (uint16_t)std::min<uint32_t>(h.thr, 0xffffu);
+                                d.pad = h.rmask_hi;
                                 if (h.parent != UINT32_MAX) {
                                         d.pop = (uint8_t)tn[h.parent].op;
                                         d.pcbits = tn[h.parent].op == TRI_OP_SOME ? (uint8_t)tree_counter_planes(tn[h.parent].nkids) : 0;
@@ -1038,6 +1050,7 @@ namespace trip {
                                 d.arg = h.arg, d.row = h.row, d.score = h.score, d.rmask = h.rmask;
                                 if (h.op == TRI_OP_NOT || h.op == TRI_OP_OPT)
                                         d.kid0 = (uint8_t)h.kid0, d.kid1 = (uint8_t)h.kid1;
+                                d.kids = h.rmask_hi; // (a leaf; an inner node's is 0 here and gets its children below)
                                 out[i] = d;
                         }
                         for (uint32_t i = 0; i + 1 < nn; ++i)

@@ -63,6 +63,9 @@ struct tri_options {
                                                // hold) .. 1024 (TREE_WIDE_MAX_NODES); any other value fails tri_batch_create.  Trees above 64 nodes run in k_tree_wide.hpp's kernels
         uint64_t tree_wide_min_nodes = 65;     // a TASK_TREE query of at least this many nodes gets a wide record and k_tree_wide.hpp's kernels; 0: every tree query does — not a tuning
                                                // knob: it lets the tests run the trees they have reference answers for through the wide kernels
+        uint64_t rich_max_terms = 16;          // default mode: a query of more reportable terms than this is left out (TRI_ERR_UNSUPPORTED per query).  16 (RICH_NARROW_TERMS) .. 64
+                                               // (RICH_WIDE_TERMS: one 64-bit mask, and what the CPU oracle holds); any other value fails tri_batch_create.  Off by default because
+                                               // of what a wide-report query reserves: 2 x stride bytes of frequency row + 8 bytes of masks per OUTPUT SLOT (its tree's upper bound)
         uint64_t probe_max_blocks = 0;         // > 0: a lead list of at most this many blocks against lists that all have planes runs in k_probe (a wave per task) instead of
                                                // k_and's candidate tiles.  Off by default — measured at cfg2 (step ms / k_probe / k_and): 0: 2.14 / - / 0.78; 64: 2.25 / 0.15 / 0.75;
                                                // 256: 2.26 / 0.22 / 0.70; 1024: 2.35 / 0.41 / 0.59; all: 2.55 / 0.82 / 0.41 — k_and's time is its tail, not its task count
@@ -114,7 +117,8 @@ namespace trip {
                 uint64_t cand_lead_docs = 0, cand_terms = 0;         // (candidate-tile and probe queries: their leads' documents, their terms)
                 uint64_t probe_demoted = 0, probe_demoted_bytes = 0; // (fill pass, a fragment's own) queries whose probes found no plane: candidate tiles after all
                 uint32_t sparse_cap = 0;                             // k_planes: list entries a task's decoded slots can need
-                uint32_t rich_R = 0;                                 // default mode: reportable terms of the widest query
+                uint32_t rich_R = 0;                                 // default mode: reportable terms of the widest NARROW query (at most RICH_NARROW_TERMS of them)
+                uint64_t rich_wide_queries = 0;                      // default mode: wide-report queries (option rich_max_terms; their rows: BatchPlan::rich_wide)
                 bool rich_allow = false;                             // default mode: the batch holds general trees (per match: which reportable terms the tree sits on)
                 void merge(const PlanCounters &o) {
                         term_bytes += o.term_bytes, term_bytes_dense += o.term_bytes_dense, term_bytes_fused += o.term_bytes_fused, term_bytes_planes += o.term_bytes_planes;
@@ -127,6 +131,7 @@ namespace trip {
                         probe_demoted += o.probe_demoted, probe_demoted_bytes += o.probe_demoted_bytes;
                         sparse_cap = std::max(sparse_cap, o.sparse_cap);
                         rich_R = std::max(rich_R, o.rich_R);
+                        rich_wide_queries += o.rich_wide_queries;
                         rich_allow |= o.rich_allow;
                 }
         };
@@ -158,6 +163,11 @@ struct BatchPlan : trip::PlanCounters {
         Span<uint32_t> tree;        // TASK_TREE records: TREE_HDR_WORDS header words + DevTreeNode per node (DevQuery::fused_idx: the record's first word)
         Span<uint32_t> tree_terms;  // the distinct term leaves of the batch's TASK_TREE queries, ascending: term -> row of the batch's tree rows
         Span<uint32_t> tree_hidden; // hidden phrase queries: their plan slots (position: the row of the batch's phrase rows)
+        Span<DevRichWide> rich_wide; // default mode, batches with wide-report queries (else empty): per plan slot, where the query's wide rows and high masks lie
+        Span<uint32_t> rich_sched;  // ... and k_rich's own schedule (else it runs off sched): sched's order with the wide-report queries' tasks moved to the end —
+                                    // [0, tasks - n_rich_wide) the existing instantiations' launch, the last n_rich_wide the wide one's
+        uint32_t n_rich_wide = 0;   // tasks of wide-report queries
+        uint64_t rich_wide_cells = 0, rich_wide_slots = 0; // 16-bit cells of the wide frequency array; slots of the high-half mask arrays
         uint32_t n_tree = 0;        // TASK_TREE tasks (the last section of sched)
         uint32_t n_tree_wide = 0;   // ... of them the last n_tree_wide have WIDE records (k_tree_wide.hpp); the narrow ones come first
         uint64_t tree_scratch_bytes = 0;
@@ -182,7 +192,7 @@ namespace trip {
         // choose_planes) — the three conditional ones (qplane, splane, sweights) there and nowhere else
         struct SectionCounts {
                 size_t plan = 0, qterms = 0, tasks = 0, fused = 0, qplane = 0, plane_terms = 0, splane = 0, sterms = 0, sweights = 0, phrases = 0, pterms = 0, ptasks = 0, units = 0,
-                       tree = 0, tree_terms = 0, tree_hidden = 0;
+                       tree = 0, tree_terms = 0, tree_hidden = 0, rich_wide = 0, rich_sched = 0;
         };
         // THE list of the block's sections, in block order: fn(the section's Span, its element count).  The layout, the host spans, the device
         // addresses (tri_batch::dev_at) and the offsets the summary reports all come from it
@@ -207,6 +217,10 @@ namespace trip {
                 fn(P.tree, n.tree);
                 fn(P.tree_terms, n.tree_terms);
                 fn(P.tree_hidden, n.tree_hidden);
+                if (n.rich_wide) { // (only a batch with wide-report queries has them: every other batch's block is what it was)
+                        fn(P.rich_wide, n.rich_wide);
+                        fn(P.rich_sched, n.rich_sched);
+                }
         }
         // the sections one after the other from offset 0 (every Span's off and n); returns the block's size
         inline size_t layout_sections(BatchPlan &P, const SectionCounts &n) {

@@ -114,11 +114,12 @@ constexpr size_t TICKET_SCORE_WORD = 32;      // k_score ...
 constexpr size_t TICKET_RICH_COUNT_WORD = TICKET_SCORE_WORD; // ... and k_rich's count pass share it: a batch is either scored or reports matched terms, never both
                                                             // (tri_batch_create: the modes are mutually exclusive)
 constexpr size_t TICKET_RICH_WRITE_WORD = 40; // k_rich's write pass (cleared again before it)
+constexpr size_t TICKET_RICH_WIDE = 2;        // ... + this: the same pass of the wide-report instantiation (its own launch, its own section of rich_sched)
 constexpr size_t TICKET_SCAT_WORD = 44;       // k_psets_prep's cursor into the batch's scatter list (+ 1: k_psets_prep_list's count of scatter queries)
 constexpr size_t TICKET_PHRASE_WORD = 48;     // k_phrase
 constexpr size_t TICKET_FUSED_WORD = 56;      // k_fused: + 2 * variant (32-bit window words, 16-bit ones, general trees)
 constexpr size_t TICKET_CAND_WORD = 64;
-static_assert(std::max({TICKET_DENSE_WORD, TICKET_PSET_WORD, TICKET_PROBE_WORD, TICKET_PLANES_WORD + 2, TICKET_SCORE_WORD, TICKET_RICH_COUNT_WORD, TICKET_RICH_WRITE_WORD,
+static_assert(std::max({TICKET_DENSE_WORD, TICKET_PSET_WORD, TICKET_PROBE_WORD, TICKET_PLANES_WORD + 2, TICKET_SCORE_WORD, TICKET_RICH_COUNT_WORD + TICKET_RICH_WIDE, TICKET_RICH_WRITE_WORD + TICKET_RICH_WIDE,
                         TICKET_SCAT_WORD + 1, TICKET_PHRASE_WORD, TICKET_FUSED_WORD + 2 * 2}) < TICKET_CAND_WORD,
               "every kernel's ticket word lies below k_and's queues");
 constexpr size_t TICKET_BYTES = (TICKET_CAND_WORD + CAND_QUEUES * CAND_TICKET_STRIDE) * 4;
@@ -428,6 +429,10 @@ struct tri_batch : BatchPlan {
         // TRI_FLAG_MATCHED_TERMS (k_rich.hpp): sterms[] holds every query's reportable terms; R = the widest query's count
         uint32_t *d_rich_present = nullptr, *d_task_hits = nullptr;
         uint16_t *d_rich_freq = nullptr, *d_rich_pool = nullptr;
+        // ... with wide-report queries (option rich_max_terms; BatchPlan::rich_wide says where a query's share of each lies): their frequency rows, and the high
+        // halves of their matches' present / allow masks — d_rich_present / d_rich_allow keep the low halves of every query, laid out as ever
+        uint16_t *d_rich_freq_wide = nullptr;
+        uint32_t *d_rich_present_hi = nullptr, *d_rich_allow_hi = nullptr;
         uint8_t *d_rich_plen = nullptr;     // TRI_FLAG_HIT_PAYLOADS: per hit of the pool, term_hit::payloadLen ...
         uint64_t *d_rich_payload = nullptr; // ... and term_hit::payload
         uint64_t *d_task_pos_base = nullptr;
@@ -469,6 +474,9 @@ struct tri_batch : BatchPlan {
                 pool_free(dev, d_all_scores);
                 pool_free(dev, d_rich_present);
                 pool_free(dev, d_rich_freq);
+                pool_free(dev, d_rich_freq_wide);
+                pool_free(dev, d_rich_present_hi);
+                pool_free(dev, d_rich_allow_hi);
                 hipFree(d_rich_pool);
                 hipFree(d_rich_plen);
                 hipFree(d_rich_payload);
@@ -570,7 +578,7 @@ namespace {
                              {"planes_rebuild", &tri_options::planes_rebuild},
                              {"cand_xcd", &tri_options::cand_xcd},
                              {"plan_threads", &tri_options::plan_threads},
-                             {"probe_max_blocks", &tri_options::probe_max_blocks}, {"phrase_task_div", &tri_options::phrase_task_div}, {"plan_hot_us", &tri_options::plan_hot_us}, {"plan_pin", &tri_options::plan_pin}, {"planes_order", &tri_options::planes_order}, {"pset_order", &tri_options::pset_order}, {"scatter_bitmap_slack", &tri_options::scatter_bitmap_slack}, {"tree_max_bytes", &tri_options::tree_max_bytes}, {"tree_max_nodes", &tri_options::tree_max_nodes}, {"tree_wide_min_nodes", &tri_options::tree_wide_min_nodes}, {"result_bitmaps", &tri_options::result_bitmaps}, {"cand_task_cost", &tri_options::cand_task_cost}, {"dense_window_cost", &tri_options::dense_window_cost}};
+                             {"probe_max_blocks", &tri_options::probe_max_blocks}, {"phrase_task_div", &tri_options::phrase_task_div}, {"plan_hot_us", &tri_options::plan_hot_us}, {"plan_pin", &tri_options::plan_pin}, {"planes_order", &tri_options::planes_order}, {"pset_order", &tri_options::pset_order}, {"scatter_bitmap_slack", &tri_options::scatter_bitmap_slack}, {"tree_max_bytes", &tri_options::tree_max_bytes}, {"tree_max_nodes", &tri_options::tree_max_nodes}, {"tree_wide_min_nodes", &tri_options::tree_wide_min_nodes}, {"rich_max_terms", &tri_options::rich_max_terms}, {"result_bitmaps", &tri_options::result_bitmaps}, {"cand_task_cost", &tri_options::cand_task_cost}, {"dense_window_cost", &tri_options::dense_window_cost}};
                 for (const auto &e : table)
                         if (!strcmp(e.name, name))
                                 return &(o.*(e.field));
@@ -1102,6 +1110,12 @@ extern "C" int tri_batch_create(tri_index *ix, const uint32_t *prog, size_t prog
                         HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_allow, (off + 64) * 4));
                         HIP_TRY(hipMemsetAsync(b->d_rich_allow, 0xff, (off + 64) * 4, dev->stream_up)); // (every other query's matches: all terms allowed)
                 }
+                if (b->n_rich_wide) { // wide-report queries: rows and high mask halves of their own (2 x stride + 8 bytes per output slot of theirs)
+                        HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_freq_wide, (b->rich_wide_cells + 64) * 2));
+                        HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_present_hi, (b->rich_wide_slots + 64) * 4));
+                        HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_allow_hi, (b->rich_wide_slots + 64) * 4));
+                        HIP_TRY(hipMemsetAsync(b->d_rich_allow_hi, 0xff, (b->rich_wide_slots + 64) * 4, dev->stream_up));
+                }
         }
         if (scored) {
                 if (!topk)
@@ -1139,7 +1153,7 @@ extern "C" int tri_batch_create(tri_index *ix, const uint32_t *prog, size_t prog
         b->info.unsupported_queries = b->unsupported_queries;
         b->info.plane_terms = b->plane_terms.size();
         b->info.plane_bytes = (uint64_t)b->plane_terms.size() * (b->planes_hi ? PL_PLANES : 1u) * b->plw * 4; // (what this batch reads of its rows of the index's plane cache: plane 0, a scored batch the high parts too)
-        b->info.launches = (!b->plane_terms.empty()) + (!b->ptasks.empty()) + (rich ? 2 : 0) + ((scored && trip::sched_first(*b, TASK_FUSED)) ? 1 : 0) + ((scored && topk) ? 1 : 0);
+        b->info.launches = (!b->plane_terms.empty()) + (!b->ptasks.empty()) + (rich ? 2 : 0) + (b->n_rich_wide ? 2 : 0) + ((scored && trip::sched_first(*b, TASK_FUSED)) ? 1 : 0) + ((scored && topk) ? 1 : 0);
         for (uint32_t kind = 0; kind < TASK_KINDS; ++kind) // (a launch per schedule section; the tree kernels are not counted)
                 b->info.launches += kind != TASK_TREE && b.get()->*trip::SCHED_COUNT[kind];
         b->info.create_plan_ms = (float)(b->plan_ms[0] + b->plan_ms[1] + b->plan_ms[2] + b->plan_ms[3]);
@@ -1469,7 +1483,8 @@ static int run_trees(tri_batch *b) {
 #define TREE_LEAVES_ARGS                                                                                                                                                                   \
         ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows,                          \
                 (const uint32_t *)b->d_tree_prows, (const uint32_t *)cc, (const uint32_t *)b->d_out, (const uint32_t *)b->d_counts, (const double *)b->dev_at(b->sweights),               \
-                (const double *)b->d_pscore, tscores, rich_run ? b->d_rich_allow : nullptr, plw, b->similarity
+                (const double *)b->d_pscore, tscores, rich_run ? b->d_rich_allow : nullptr, plw, b->similarity, b->d_rich_allow_hi,                                                     \
+                (const DevRichWide *)b->dev_opt(b->rich_wide)
                                 if (wide)
                                         TRI_LAUNCH(k_tree_leaves_wide, ix->codec, grid, dim3(TREE_WG), dev->stream, TREE_LEAVES_ARGS);
                                 else
@@ -1495,12 +1510,22 @@ template <bool WRITE>
 static int launch_rich(tri_batch *b) {
         tri_dev *dev = b->dev;
         tri_index *ix = b->ix;
-        const uint32_t n = (uint32_t)b->tasks.size();
-        tri_launch(ix->codec, [](auto c) { return k_rich<c.value, WRITE>; }, dim3(std::min<uint32_t>(n, (uint32_t)dev->cus * 3)), dim3(AND_WG), dev->stream, ix->d_index,
-                   ix->d_hits, ix->d_blk_hits, ix->d_hdir, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->sched), b->dev_at(b->sterms), n,
-                   b->d_ticket + (WRITE ? TICKET_RICH_WRITE_WORD : TICKET_RICH_COUNT_WORD), b->d_out, b->d_counts, b->rich_R, b->d_rich_present, b->d_rich_freq, b->d_task_hits,
-                   WRITE ? (const uint64_t *)b->d_task_pos_base : nullptr, WRITE ? b->d_rich_pool : nullptr, (const uint32_t *)b->d_rich_allow, WRITE ? b->d_rich_plen : nullptr,
-                   WRITE ? b->d_rich_payload : nullptr);
+        // a batch with wide-report queries runs off its own schedule (BatchPlan::rich_sched): every other task first — the launch below, what it always
+        // covered —, the wide-report queries' tasks last: a second launch, of k_rich_wide, with a ticket word of its own
+        const uint32_t n_wide = b->n_rich_wide, n = (uint32_t)b->tasks.size() - n_wide;
+        const uint32_t *sched = n_wide ? b->dev_at(b->rich_sched) : b->dev_at(b->sched);
+        const RichWideArgs wd{b->d_rich_present_hi, b->d_rich_allow_hi, b->d_rich_freq_wide, b->dev_opt(b->rich_wide)};
+#define RICH_ARGS(SCHED, N, TICKET)                                                                                                                                                        \
+        ix->d_index, ix->d_hits, ix->d_blk_hits, ix->d_hdir, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), SCHED, b->dev_at(b->sterms), N,         \
+                b->d_ticket + (WRITE ? TICKET_RICH_WRITE_WORD : TICKET_RICH_COUNT_WORD) + TICKET, b->d_out, b->d_counts, b->rich_R, b->d_rich_present, b->d_rich_freq, b->d_task_hits,     \
+                WRITE ? (const uint64_t *)b->d_task_pos_base : nullptr, WRITE ? b->d_rich_pool : nullptr, (const uint32_t *)b->d_rich_allow, WRITE ? b->d_rich_plen : nullptr,             \
+                WRITE ? b->d_rich_payload : nullptr
+        if (n)
+                tri_launch(ix->codec, [](auto c) { return k_rich<c.value, WRITE>; }, dim3(std::min<uint32_t>(n, (uint32_t)dev->cus * 3)), dim3(AND_WG), dev->stream, RICH_ARGS(sched, n, 0));
+        if (n_wide)
+                tri_launch(ix->codec, [](auto c) { return k_rich_wide<c.value, WRITE>; }, dim3(std::min<uint32_t>(n_wide, (uint32_t)dev->cus * 3)), dim3(AND_WG), dev->stream,
+                           RICH_ARGS(sched + n, n_wide, TICKET_RICH_WIDE), wd);
+#undef RICH_ARGS
         HIP_TRY(hipGetLastError());
         return TRI_OK;
 }
@@ -1512,6 +1537,10 @@ static int run_rich_count(tri_batch *b) {
         HIP_TRY(hipMemsetAsync(b->d_rich_present, 0, (b->out_capacity + 64) * 4, dev->stream));
         HIP_TRY(hipMemsetAsync(b->d_rich_freq, 0, (b->out_capacity + 64) * 2 * b->rich_R, dev->stream));
         HIP_TRY(hipMemsetAsync(b->d_task_hits, 0, (b->tasks.size() + 1) * 4, dev->stream));
+        if (b->n_rich_wide) { // (the wide-report queries' rows and high mask halves: cleared per run like the narrow ones)
+                HIP_TRY(hipMemsetAsync(b->d_rich_present_hi, 0, (b->rich_wide_slots + 64) * 4, dev->stream));
+                HIP_TRY(hipMemsetAsync(b->d_rich_freq_wide, 0, (b->rich_wide_cells + 64) * 2, dev->stream));
+        }
         return launch_rich<false>(b);
 }
 
@@ -1871,7 +1900,7 @@ static int rich_write_pass(tri_batch *b) {
                 }
         }
         HIP_TRY(hipMemcpy(b->d_task_pos_base, b->h_task_pos_base.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemsetAsync(b->d_ticket + TICKET_RICH_WRITE_WORD, 0, 4, dev->stream));
+        HIP_TRY(hipMemsetAsync(b->d_ticket + TICKET_RICH_WRITE_WORD, 0, (TICKET_RICH_WIDE + 1) * 4, dev->stream)); // (the wide instantiation's word too)
         if (const int rc = launch_rich<true>(b))
                 return rc;
         HIP_TRY(hipStreamSynchronize(dev->stream));
@@ -1934,13 +1963,32 @@ extern "C" int tri_batch_query_terms(tri_batch *b, size_t q, uint32_t *terms, ui
         if (slot == UINT32_MAX)
                 return TRI_OK;
         const DevQuery &dq = b->plan[slot];
+        if (dq.nscore > RICH_NARROW_TERMS) // (never past terms[16])
+                return fail(TRI_ERR_INVALID, "tri_batch_query_terms: query %zu reports %u terms (option rich_max_terms): call tri_batch_query_terms_wide", q, dq.nscore);
         for (uint32_t k = 0; k < dq.nscore; ++k)
                 terms[k] = b->sterms[dq.score_base + k];
         *nterms = dq.nscore;
         return TRI_OK;
 }
 
-extern "C" int tri_batch_matched_terms(tri_batch *b, size_t q, uint32_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos) {
+extern "C" int tri_batch_query_terms_wide(tri_batch *b, size_t q, uint32_t *terms, uint32_t *nterms) {
+        if (!b || !terms || !nterms || q >= b->nq)
+                return fail(TRI_ERR_INVALID, "bad argument");
+        if (!(b->flags & TRI_FLAG_MATCHED_TERMS))
+                return fail(TRI_ERR_INVALID, "not a TRI_FLAG_MATCHED_TERMS batch");
+        const uint32_t slot = b->slot_of_query[q];
+        *nterms = 0;
+        if (slot == UINT32_MAX)
+                return TRI_OK;
+        const DevQuery &dq = b->plan[slot];
+        for (uint32_t k = 0; k < dq.nscore && k < RICH_WIDE_TERMS; ++k)
+                terms[k] = b->sterms[dq.score_base + k];
+        *nterms = std::min(dq.nscore, RICH_WIDE_TERMS);
+        return TRI_OK;
+}
+
+// tri_batch_matched_terms (present: 32-bit masks) and tri_batch_matched_terms_wide (wide_call; present64: a narrow query's mask zero-extended)
+static int matched_terms_impl(tri_batch *b, size_t q, uint32_t *present, uint64_t *present64, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos, const bool wide_call) {
         if (!b || !npos || q >= b->nq)
                 return fail(TRI_ERR_INVALID, "bad argument");
         if (!(b->flags & TRI_FLAG_MATCHED_TERMS))
@@ -1952,6 +2000,9 @@ extern "C" int tri_batch_matched_terms(tri_batch *b, size_t q, uint32_t *present
         if (slot == UINT32_MAX)
                 return TRI_OK;
         const DevQuery &dq = b->plan[slot];
+        const bool wide_q = dq.nscore > RICH_NARROW_TERMS; // a wide-report query: rows and high mask halves of its own (BatchPlan::rich_wide)
+        if (wide_q && !wide_call) // (a 32-bit mask would be truncated)
+                return fail(TRI_ERR_INVALID, "tri_batch_matched_terms: query %zu reports %u terms (option rich_max_terms): call tri_batch_matched_terms_wide", q, dq.nscore);
         tri_dev *dev = b->ix->dev;
         HIP_TRY(hipSetDevice(dev->device));
         // the query's tasks are consecutive, so its hits are one contiguous run of the pool
@@ -1966,6 +2017,17 @@ extern "C" int tri_batch_matched_terms(tri_batch *b, size_t q, uint32_t *present
         // per-match rows live at the tasks' out[] slots; freq rows are R wide on the device, nscore wide for the caller
         size_t w = 0;
         std::vector<uint16_t> rows;
+        // present64: a segment's low words are copied (asynchronously, like the narrow call's) into the UPPER half of the segment's own u64 cells and widened in
+        // place once the copies have landed (front to back: cell i is written from word c + i, which no earlier cell's store reaches); a wide-report query's
+        // high words wait in a staging array meanwhile
+        std::vector<uint32_t> hi;
+        std::vector<std::pair<size_t, uint32_t>> segs; // (first cell, matches) per task segment
+        if (present64 && wide_q) {
+                size_t n = 0;
+                for (uint32_t t = 0; t < dq.ntasks; ++t)
+                        n += b->h_counts[dq.first_task + t];
+                hi.resize(n);
+        }
         for (uint32_t t = 0; t < dq.ntasks; ++t) {
                 const uint32_t c = b->h_counts[dq.first_task + t];
                 if (!c)
@@ -1973,7 +2035,20 @@ extern "C" int tri_batch_matched_terms(tri_batch *b, size_t q, uint32_t *present
                 const uint64_t off = b->tasks[dq.first_task + t].out_off;
                 if (present)
                         HIP_TRY(hipMemcpyAsync(present + w, b->d_rich_present + off, (size_t)c * 4, hipMemcpyDeviceToHost, dev->stream));
-                if (freq) {
+                if (present64) { // the low words from where they always were; a wide-report query's high words from its slots of the second array
+                        HIP_TRY(hipMemcpyAsync(reinterpret_cast<uint32_t *>(present64 + w) + c, b->d_rich_present + off, (size_t)c * 4, hipMemcpyDeviceToHost, dev->stream));
+                        if (wide_q)
+                                HIP_TRY(hipMemcpyAsync(hi.data() + w, b->d_rich_present_hi + b->rich_wide[slot].slots + (off - dq.out_off), (size_t)c * 4, hipMemcpyDeviceToHost, dev->stream));
+                        segs.emplace_back(w, c);
+                }
+                if (freq && wide_q) { // rows `stride` cells apart on the device, nscore wide for the caller
+                        const DevRichWide &rw = b->rich_wide[slot];
+                        rows.resize((size_t)c * rw.stride);
+                        HIP_TRY(hipMemcpy(rows.data(), b->d_rich_freq_wide + rw.cells + (off - dq.out_off) * rw.stride, (size_t)c * 2 * rw.stride, hipMemcpyDeviceToHost));
+                        for (size_t i = 0; i < c; ++i)
+                                for (uint32_t k = 0; k < dq.nscore; ++k)
+                                        freq[(w + i) * dq.nscore + k] = rows[i * rw.stride + k];
+                } else if (freq) {
                         if (b->rich_R == dq.nscore)
                                 HIP_TRY(hipMemcpyAsync(freq + w * dq.nscore, b->d_rich_freq + off * b->rich_R, (size_t)c * 2 * b->rich_R, hipMemcpyDeviceToHost, dev->stream));
                         else {
@@ -1987,10 +2062,26 @@ extern "C" int tri_batch_matched_terms(tri_batch *b, size_t q, uint32_t *present
                 w += c;
         }
         HIP_TRY(hipStreamSynchronize(dev->stream));
+        for (const auto &sg : segs) {
+                const uint32_t *lo = reinterpret_cast<const uint32_t *>(present64 + sg.first) + sg.second;
+                for (size_t i = 0; i < sg.second; ++i) {
+                        uint32_t l;
+                        memcpy(&l, lo + i, 4);
+                        present64[sg.first + i] = (uint64_t)l | (wide_q ? (uint64_t)hi[sg.first + i] << 32 : 0ull);
+                }
+        }
         return TRI_OK;
 }
 
-// the payloads of query q's hits, parallel to the positions tri_batch_matched_terms returns (same order, same count)
+extern "C" int tri_batch_matched_terms(tri_batch *b, size_t q, uint32_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos) {
+        return matched_terms_impl(b, q, present, nullptr, freq, positions, pos_cap, npos, false);
+}
+extern "C" int tri_batch_matched_terms_wide(tri_batch *b, size_t q, uint64_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos) {
+        return matched_terms_impl(b, q, nullptr, present, freq, positions, pos_cap, npos, true);
+}
+
+// the payloads of query q's hits, parallel to the positions tri_batch_matched_terms returns (same order, same count); for a wide-report query: to those of
+// tri_batch_matched_terms_wide
 extern "C" int tri_batch_matched_payloads(tri_batch *b, size_t q, uint8_t *lens, uint64_t *payloads, size_t cap, size_t *n) {
         if (!b || !n || q >= b->nq)
                 return fail(TRI_ERR_INVALID, "bad argument");

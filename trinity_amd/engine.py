@@ -106,7 +106,7 @@ ABI_SYMBOLS = [
     "tri_last_error", "tri_abi_version", "tri_dev_open", "tri_dev_close", "tri_dev_sync", "tri_dev_stream", "tri_dev_set_option", "tri_dev_get_option", "tri_dev_memory",
     "tri_index_upload", "tri_index_destroy", "tri_index_get_info", "tri_index_term_docbytes", "tri_index_set_masked", "tri_decode_terms",
     "tri_batch_create", "tri_batch_query_status", "tri_batch_destroy", "tri_batch_run", "tri_batch_sync", "tri_batch_get_info",
-    "tri_batch_match_counts", "tri_batch_docset", "tri_batch_docset_bitmap", "tri_batch_docsets", "tri_batch_docsets_mixed", "tri_batch_scores", "tri_batch_query_terms", "tri_batch_matched_terms", "tri_batch_matched_payloads", "tri_batch_topk", "tri_batch_topk_device", "tri_batch_counts_device", "tri_batch_docset_hashes",
+    "tri_batch_match_counts", "tri_batch_docset", "tri_batch_docset_bitmap", "tri_batch_docsets", "tri_batch_docsets_mixed", "tri_batch_scores", "tri_batch_query_terms", "tri_batch_matched_terms", "tri_batch_query_terms_wide", "tri_batch_matched_terms_wide", "tri_batch_matched_payloads", "tri_batch_topk", "tri_batch_topk_device", "tri_batch_counts_device", "tri_batch_docset_hashes",
     "tri_cbatch_create", "tri_cbatch_destroy", "tri_cbatch_query_status", "tri_cbatch_run", "tri_cbatch_sync", "tri_cbatch_match_counts", "tri_cbatch_topk", "tri_cbatch_docset", "tri_encode_google", "tri_encode_google_payloads", "tri_commit_google", "tri_commit_lucene", "tri_merge_google", "tri_merge_lucene", "tri_encode_lucene",
     "tri_comm_unique_id", "tri_comm_create", "tri_comm_create_custom", "tri_comm_destroy", "tri_gather_results",
     "tri_filter_create", "tri_filter_from_docset", "tri_filter_destroy", "tri_batch_set_filters",
@@ -149,6 +149,8 @@ def hip_lib():
     L.tri_batch_get_info.argtypes = [vp, C.POINTER(TriBatchInfo)]
     L.tri_batch_query_terms.argtypes = [vp, C.c_size_t, vp, C.POINTER(C.c_uint32)]
     L.tri_batch_matched_terms.argtypes = [vp, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.tri_batch_query_terms_wide.argtypes = L.tri_batch_query_terms.argtypes
+    L.tri_batch_matched_terms_wide.argtypes = L.tri_batch_matched_terms.argtypes
     L.tri_batch_matched_payloads.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.tri_batch_match_counts.argtypes = [vp, vp]
     L.tri_batch_docset.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -590,18 +592,36 @@ class Batch:
 
     def matched_terms(self, q, n):
         """FLAG_MATCHED_TERMS batches: (terms u32[nt], present u32[n], freq u16[n, nt], positions u16[npos]) for the n matches of
-        query q (ascending docID, as docset(q, n) returns them); positions are match-major then term-minor."""
+        query q (ascending docID, as docset(q, n) returns them); positions are match-major then term-minor.  A wide-report query (17 .. 64 reportable
+        terms, option rich_max_terms) goes through the _wide calls: the same shape, present as u64[n]."""
         L = hip_lib()
-        terms = np.zeros(16, dtype=np.uint32)
+        terms = np.zeros(64, dtype=np.uint32)
         nt = C.c_uint32()
-        _check(L.tri_batch_query_terms(self.h, q, terms.ctypes.data, C.byref(nt)))
+        _check(L.tri_batch_query_terms_wide(self.h, q, terms.ctypes.data, C.byref(nt)))
         nt = nt.value
+        wide = nt > 16
+        matched = L.tri_batch_matched_terms_wide if wide else L.tri_batch_matched_terms
         npos = C.c_size_t()
-        _check(L.tri_batch_matched_terms(self.h, q, None, None, None, 0, C.byref(npos)))
-        present = np.zeros(n, dtype=np.uint32)
+        _check(matched(self.h, q, None, None, None, 0, C.byref(npos)))
+        present = np.zeros(n, dtype=np.uint64 if wide else np.uint32)
         freq = np.zeros((n, max(nt, 1)), dtype=np.uint16)
         pos = np.zeros(max(1, npos.value), dtype=np.uint16)
-        _check(L.tri_batch_matched_terms(self.h, q, present.ctypes.data, freq.ctypes.data, pos.ctypes.data, pos.size, C.byref(npos)))
+        _check(matched(self.h, q, present.ctypes.data, freq.ctypes.data, pos.ctypes.data, pos.size, C.byref(npos)))
+        return terms[:nt], present, freq[:, :nt], pos[: npos.value]
+
+    def matched_terms_wide(self, q, n):
+        """... through the _wide calls whatever the query's width: present as u64[n] (a query of at most 16 terms: zero-extended)."""
+        L = hip_lib()
+        terms = np.zeros(64, dtype=np.uint32)
+        nt = C.c_uint32()
+        _check(L.tri_batch_query_terms_wide(self.h, q, terms.ctypes.data, C.byref(nt)))
+        nt = nt.value
+        npos = C.c_size_t()
+        _check(L.tri_batch_matched_terms_wide(self.h, q, None, None, None, 0, C.byref(npos)))
+        present = np.zeros(n, dtype=np.uint64)
+        freq = np.zeros((n, max(nt, 1)), dtype=np.uint16)
+        pos = np.zeros(max(1, npos.value), dtype=np.uint16)
+        _check(L.tri_batch_matched_terms_wide(self.h, q, present.ctypes.data, freq.ctypes.data, pos.ctypes.data, pos.size, C.byref(npos)))
         return terms[:nt], present, freq[:, :nt], pos[: npos.value]
 
     def counts(self):

@@ -25,6 +25,9 @@ TREE_HDR_WORDS = 8
 DEV_TREE_NODE_WIDE = np.dtype([("op", "u1"), ("cbits", "u1"), ("parent", "<u2"), ("arg", "<u4"), ("row", "<u4"), ("score", "<u4"), ("rmask", "<u4"),
                                ("ord", "<u2"), ("nkids", "<u2"), ("thr", "<u2"), ("pop", "u1"), ("pcbits", "u1"), ("pad", "<u4")])  # fmt: skip
 TREE_KIND_NARROW, TREE_KIND_WIDE = 0, 1
+# default mode, wide-report queries (option rich_max_terms; csrc/dev_structs.hpp DevRichWide): one record per plan slot, stride 0 = not a wide-report query
+DEV_RICH_WIDE = np.dtype([("cells", "<u8"), ("slots", "<u8"), ("stride", "<u4"), ("pad", "<u4")])
+_RICH_WIDE = ["n_rich_wide_tab", "off_rich_wide", "off_rich_sched", "n_rich_wide", "rich_wide_cells", "rich_wide_slots", "sizeof_rich_wide"]
 TREE_NO_PARENT = 0xFFFF
 DEV_UNIT = np.dtype([("out_off", "<u8"), ("begin", "<u4"), ("end", "<u4"), ("tix", "<u4"), ("nterms", "<u4"), ("term_base", "<u4"), ("first", "<u4"), ("tt", "<u4", 4), ("row", "<u4", 4)])
 SCHED_ORDER = [TASK_DENSE, TASK_PSET, TASK_PROBE, TASK_CAND, TASK_FUSED, TASK_FUSED16, TASK_FUSED_GEN, TASK_PLANES, TASK_PLANES8, TASK_TREE]
@@ -46,6 +49,8 @@ def _lib():
         L.tri_host_plan_query_maps.argtypes = [vp, vp, vp]
         L.tri_host_plan_last_unsupported.argtypes = [vp, C.c_char_p, C.c_uint64]
         L.tri_host_plan_last_unsupported.restype = None
+        L.tri_host_plan_rich_wide.argtypes = [vp, vp]
+        L.tri_host_plan_rich_wide.restype = None
         L.tri_host_pfor128_group.argtypes = [vp, vp, C.POINTER(C.c_uint32), vp, C.POINTER(C.c_uint32)]
         L.tri_host_pfor128_group.restype = None
         for f in (L.tri_host_lucene_encode, L.tri_host_lucene_encode_units):
@@ -97,6 +102,10 @@ class HostPlan:
         _lib().tri_host_plan_summary(self.h, out.ctypes.data, ms.ctypes.data)
         self.s = {k: int(v) for k, v in zip(_SUMMARY, out)}
         self.ms = ms
+        wide = np.zeros(len(_RICH_WIDE), dtype=np.uint64)
+        _lib().tri_host_plan_rich_wide(self.h, wide.ctypes.data)
+        self.s.update({k: int(v) for k, v in zip(_RICH_WIDE, wide)})
+        assert self.s["sizeof_rich_wide"] == DEV_RICH_WIDE.itemsize
         assert self.s["sizeof_query"] == DEV_QUERY.itemsize and self.s["sizeof_task"] == DEV_TASK.itemsize
         p = _lib().tri_host_plan_block(self.h)
         # (a copy of its own: the arrays handed out below are views of it and stay readable after close() — a failing test's report formats them then)
@@ -156,6 +165,25 @@ class HostPlan:
     @property
     def tree_hidden(self):
         return self._view("off_tree_hidden", self.s["n_tree_hidden"], "<u4")
+
+    @property
+    def rich_wide(self):
+        """Default mode: per plan slot, where a wide-report query's frequency rows and high mask words lie (empty: the batch holds no such query)."""
+        return self._view("off_rich_wide", self.s["n_rich_wide_tab"], DEV_RICH_WIDE)
+
+    @property
+    def rich_sched(self):
+        """... and k_rich's own schedule of such a batch: the narrow queries' tasks, then the n_rich_wide tasks of the wide-report queries."""
+        return self._view("off_rich_sched", self.s["n_tasks"] if self.s["n_rich_wide_tab"] else 0, "<u4")
+
+    def leaf_report_mask(self, slot, node):
+        """The 64-bit report mask of leaf `node` of the TASK_TREE query in plan slot `slot` (narrow record: the high word rides in the leaf's unused `kids`;
+        wide record: in `pad`)."""
+        if self.tree_kind(slot)[0] == TREE_KIND_WIDE:
+            nd = self.tree_nodes_wide(slot)[node]
+            return int(nd["rmask"]) | (int(nd["pad"]) << 32)
+        nd = self.tree_nodes(slot)[node]
+        return int(nd["rmask"]) | ((int(nd["kids"]) & 0xFFFFFFFF) << 32)
 
     def tree_nodes(self, slot):
         """The DevTreeNode records of the TASK_TREE query in plan slot `slot`."""
