@@ -1571,26 +1571,7 @@ def test_device_encoder_refuses_what_the_reference_encoder_would_not_take(T, dev
 
 
 # ------------------------------------------------------------------------------------------ write side on the device
-def random_postings(rng, nterms):
-    """Postings that reach every corner of the encoder: empty terms, 1 / 31 / 32 / 33 / 64 / 65 documents, runs long enough for skiplist
-    entries, deltas of every varint length, frequencies 0 .. 300, positions up to 65535 with repeats."""
-    docs, freqs, pos, tf = [], [], [], [0]
-    sizes = [0, 1, 31, 32, 33, 64, 65, 300, 1000, 2, 5]
-    for t in range(nterms):
-        n = sizes[t % len(sizes)] if t < 3 * len(sizes) else int(rng.integers(0, 200))
-        scale = [1, 3, 200, 20000, 3_000_000][t % 5]
-        d = np.cumsum(rng.integers(1, scale + 1, size=n, dtype=np.int64))
-        d = d[d < 2**32 - 1]
-        f = np.where(rng.random(d.size) < 0.1, 0, rng.integers(1, 4, size=d.size))
-        if d.size and t % 7 == 0:
-            f[int(rng.integers(0, d.size))] = 300
-        for k in f.tolist():
-            p = np.sort(rng.integers(1, [12, 200, 65536][t % 3], size=k))
-            pos += p.tolist()
-        docs += d.tolist()
-        freqs += f.tolist()
-        tf.append(len(docs))
-    return np.array(docs, dtype=np.uint32), np.array(freqs, dtype=np.uint32), np.array(pos, dtype=np.uint16), np.array(tf, dtype=np.uint64)
+from write_cases import random_postings  # noqa: E402  (the i.i.d. postings; the structured cases are tests/test_gpu_write_structured.py's)
 
 
 def test_google_encoder_on_the_device(T, dev):
