@@ -30,7 +30,8 @@ extern "C" {
                              9: tri_dev_memory (HBM in use), tri_batch_docsets_mixed (dense sets delivered as bitmap words), two planner contexts per handle (two threads may compile at once), plane rows built by need;
                                 within 9: tri_filter_create / tri_filter_from_docset / tri_filter_destroy / tri_batch_set_filters (per-query document filters on the device);
                                 within 9: options tree_max_nodes / tree_wide_min_nodes (query trees of up to 1024 nodes; no new export, no struct grew);
-                                within 9: option rich_max_terms, tri_batch_query_terms_wide / tri_batch_matched_terms_wide (the default mode reports up to 64 matched terms per query; no struct grew) */
+                                within 9: option rich_max_terms, tri_batch_query_terms_wide / tri_batch_matched_terms_wide (the default mode reports up to 64 matched terms per query; no struct grew);
+                                within 9: tri_decode_hits / tri_decode_hits_at (the codec seam's materialize_hits: the hits of whole lists and of chosen documents; no struct grew) */
 
 /* status codes */
 #define TRI_OK 0
@@ -281,6 +282,33 @@ int tri_batch_set_filters(tri_batch *, tri_filter *const *filters, size_t nf, co
  * unpack_block :596-639): decodes whole postings lists on the GPU.  out_offsets[n+1] receives the prefix
  * offsets into docs/freqs (host buffers with room for sum(documents)). */
 int tri_decode_terms(tri_index *, const uint32_t *terms, size_t n, uint32_t *docs, uint32_t *freqs, uint64_t *out_offsets);
+
+/* The hits of postings lists: Codecs::PostingsListIterator::materialize_hits(DocWordsSpace *, term_hit *) (codecs.h:211-246; google_codec.cpp:533-594;
+ * lucene_codec.cpp:767-856) without a query around it — what an iterator the application keeps on the CPU (a proximity scorer, a DocsSetIterators subclass
+ * of its own) asks of the codec for its candidates (candidate_document::materialize_term_hits, queryexec_ctx.cpp:317-351).
+ *
+ * Per hit k: positions[k] = term_hit::pos, the u16 running sum of the document's position deltas (it restarts at 0 with every document);
+ * payload_lens[k] = term_hit::payloadLen; payloads[k] = term_hit::payload, the word as materialize_hits leaves it: the word and the current length restart at
+ * 0 with each document, a new payload overwrites only the word's first min(len, 8) bytes, length 0 clears it (what tri_batch_matched_payloads delivers for the
+ * matches of a query).  A LUCENE index gives lengths and words of 0: these segments carry no payloads.  payload_lens and payloads are both NULL (positions
+ * only) or both given.
+ *
+ * tri_decode_hits — whole lists, for EVERY document of each term, in list order.  out_offsets[n + 1] are prefix offsets in hits; term i's hits lie document
+ * after document, document j of the term owning freq[j] hits, freq being exactly what tri_decode_terms returns for it: the caller's cumulative sum of those
+ * frequencies addresses a document.  A frequency-0 document owns no hits.  A document's hit count is its STORED frequency (u32), not the tokenpos_t wrap of
+ * it: the reference's own walk decodes (u16)freq hits of a document of more than 65 535 and so loses its place in the block behind it; the
+ * engine decodes all of that document's hits and stays in place for the next document.  positions == NULL: offsets only (the sizing call).
+ *
+ * tri_decode_hits_at — selected documents: the hits of term terms[i] in document docids[i].  Pairs come in any order and may repeat.  freqs[i] = the
+ * document's stored frequency, or 0xffffffff when the term's list does not hold docids[i] (docID 0, UINT32_MAX and anything past the list's last document
+ * included); an absent document owns no hits.  n == 0 is legal.  positions == NULL: freqs and offsets only.
+ *
+ * TRI_ERR_INVALID, nothing written: a term index >= the index's terms, a LUCENE index uploaded without hits.data, cap (in hits) smaller than the total, one
+ * of payload_lens / payloads without the other. */
+int tri_decode_hits(tri_index *, const uint32_t *terms, size_t n, uint16_t *positions, uint8_t *payload_lens, uint64_t *payloads, size_t cap /* hits */,
+                    uint64_t *out_offsets /* [n + 1] */);
+int tri_decode_hits_at(tri_index *, const uint32_t *terms, const uint32_t *docids, size_t n, uint32_t *freqs /* [n] */, uint16_t *positions, uint8_t *payload_lens,
+                       uint64_t *payloads, size_t cap /* hits */, uint64_t *out_offsets /* [n + 1] */);
 
 /* ---- batched query execution (span seam) -----------------------------------------------------------
  * Replaces, for a whole batch of queries at once: queryexec_ctx::build_iterator + build_span

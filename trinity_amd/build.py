@@ -106,8 +106,24 @@ def build_mirror_wide_terms_test(force=False):
     return MIRROR_WIDE_TERMS_BIN
 
 
+MIRROR_HITS_SRC = os.path.join(ROOT, "tests", "cpp", "host_mirror_hits_test.cpp")
+MIRROR_HITS_BIN = os.path.join(ROOT, "tests", "cpp", "host_mirror_hits_test")
+
+
+def build_mirror_hits_test(force=False):
+    """PostingsListIterator::materialize_hits, DocWordsSpace and IndexSource::term_hits_at (csrc/host/trinity_gpu.hpp: tri_decode_hits / tri_decode_hits_at) compiled
+    into their driver; in-tree, so that it travels to the GPU box, where tests/test_host_mirror_hits.py runs it."""
+    deps = [MIRROR_HITS_SRC, os.path.join(PKG, "csrc", "host", "trinity_gpu.hpp"), os.path.join(PKG, "csrc", "host", "google_encoder.hpp"), os.path.join(ROOT, "include", "trinity_hip.h")]
+    if force or _newer(MIRROR_HITS_BIN, deps):
+        build_hip()
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", MIRROR_HITS_BIN, MIRROR_HITS_SRC, "-L" + PKG, "-ltrinity_hip", "-Wl,-rpath,$ORIGIN/../../trinity_amd"]
+        subprocess.run(cmd, check=True)
+    return MIRROR_HITS_BIN
+
+
 def build_all(force=False):
-    return build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force), build_mirror_wide_terms_test(force)
+    return (build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force), build_mirror_wide_terms_test(force),
+            build_mirror_hits_test(force))
 
 
 def kernels_stamp():

@@ -245,6 +245,19 @@ uint32_t tri_host_pool_cpus(uint32_t threads, int32_t *out, uint32_t cap) {
 
 uint32_t tri_host_cpu_budget() { return host_cpu_budget(); } // (host_pool.hpp: what the planner's pools are sized to)
 
+// where the hits of a term's directory rows start, as the upload records it (index_host.hpp blk_hits[]: GOOGLE, bytes past the block's payload offset, bit 31 =
+// BLK_HITS_PLAIN; LUCENE with hits.data, the hit ordinal within the term) and, LUCENE, the term's full 128-hit groups (hdir[]'s nfull).  out: room for the
+// term's blocks (null: only count them).  Returns the term's blocks
+uint32_t tri_host_index_hits_dir(void *h, uint32_t term, uint32_t *out, uint32_t *nfull) {
+        const HostIndex &H = *static_cast<HostIndex *>(h);
+        const DevTerm &t = H.terms[term];
+        const bool have = H.codec == TRI_CODEC_GOOGLE || H.has_hdir;
+        for (uint32_t b = 0; out && have && b < t.nblocks; ++b)
+                out[b] = H.blk_hits[t.first_block + b];
+        *nfull = H.has_hdir && t.nblocks ? H.hdir[t.pad] : 0;
+        return t.nblocks;
+}
+
 void tri_host_index_facts(void *h, uint64_t *info6, uint32_t *per_term3) {
         const HostIndex &H = *static_cast<HostIndex *>(h);
         info6[0] = H.info.postings, info6[1] = H.info.blocks, info6[2] = H.info.doc_bytes, info6[3] = H.info.hit_bytes, info6[4] = H.transcoded_groups, info6[5] = H.dev_index.size();

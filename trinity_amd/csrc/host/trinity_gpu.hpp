@@ -23,6 +23,7 @@
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 namespace trinity_amd {
@@ -156,6 +157,39 @@ namespace trinity_amd {
 
         inline isrc_docid_t IteratorScorer::document() const noexcept { return it->current(); }
 
+        // ------------------------------------------------------------------ positions scratch
+        // docwordspace.h:16-92, restated: which query term sits at each position of the CURRENT document.  ONE term per position — set() replaces whatever
+        // was there, the last writer wins —, test(term, pos) asks "is it this term", reset() forgets the document in O(1): a cell carries the sequence number
+        // of the document that wrote it and counts only while that is the current one (every 65 535 resets the cells are cleared and the numbers start
+        // again at 1).  Position 0 means "no position" in the index and is never set (the callers skip it: materialize_hits).  The reference sizes the space
+        // by the largest indexed position and leaves a set() past it to the caller's care; here every tokenpos_t is a valid cell (and MaxPhraseSize more, so
+        // that a phrase test may run past the last position without a bound check)
+        class DocWordsSpace final {
+                static constexpr uint32_t MaxPhraseSize = 16; // trinity_limits.h:12
+                std::vector<uint32_t> cells;                   // termID << 16 | sequence number of the writing document (0: never written)
+                const uint32_t maxPos;
+                uint16_t curSeq{1};
+
+              public:
+                explicit DocWordsSpace(const uint32_t max = 16383) // trinity_limits.h:15 MaxPosition
+                    : cells(size_t(std::numeric_limits<tokenpos_t>::max()) + 1 + MaxPhraseSize, 0u), maxPos{max} {
+                        if (!max || max > std::numeric_limits<tokenpos_t>::max())
+                                throw invalid_argument("DocWordsSpace: max position out of range");
+                }
+                void reset() {
+                        if (curSeq == std::numeric_limits<uint16_t>::max()) {
+                                std::fill(cells.begin(), cells.end(), 0u);
+                                curSeq = 1;
+                        } else
+                                ++curSeq;
+                }
+                void set(const exec_term_id_t termID, const tokenpos_t pos) noexcept { cells[pos] = uint32_t(termID) << 16 | curSeq; }
+                bool test(const exec_term_id_t termID, const uint32_t pos) const noexcept { return pos < cells.size() && cells[pos] == (uint32_t(termID) << 16 | curSeq); }
+                void unset(const tokenpos_t pos) noexcept { cells[pos] = 0; }
+                uint32_t max_pos() const noexcept { return maxPos; }
+        };
+        struct term_hit;
+
         // ------------------------------------------------------------------ codecs
         namespace Codecs { // codecs.h:211-317
                 struct Decoder;
@@ -176,16 +210,26 @@ namespace trinity_amd {
                         Decoder *decoder() noexcept { return dec; }
                         uint64_t cost() const override;
                         void lower(std::vector<uint32_t> &prog, std::vector<double> &w, Similarity::IndexSourceTermsScorer *scorer) const override;
+                        // codecs.h:229-235: the hits of the CURRENT document into out[0 .. freq) — term_hit{payload, pos, payloadLen} — and dws->set(termID, pos) for
+                        // every pos != 0 (termID = the decoder's execCtxTermID).  The first call of a list fetches all its hits ONCE from the device
+                        // (tri_decode_hits); later calls copy.  Unlike the reference's it may be called again for the same document, and in any order
+                        inline void materialize_hits(DocWordsSpace *dws, term_hit *out);
 
                       protected:
                         std::vector<uint32_t> freqs;
                         void materialize() override; // tri_decode_terms: the whole list, docIDs + freqs
+                        // materialize_hits' copy of the list's hits, and where each document's begin (the running sum of the STORED frequencies)
+                        bool hitsFetched{false};
+                        std::vector<uint16_t> hitPos;
+                        std::vector<uint8_t> hitLen;
+                        std::vector<uint64_t> hitPayload, hitFirst;
                 };
 
                 struct AccessProxy;
                 struct Decoder {
                         term_index_ctx indexTermCtx;
                         uint32_t termId{0}; // row of the uploaded term table
+                        exec_term_id_t execCtxTermID{0}; // the query's id of the term (codecs.h Decoder::execCtxTermID): what materialize_hits sets in the DocWordsSpace
                         std::string term;
                         IndexSource *isrc{nullptr};
                         virtual ~Decoder() = default;
@@ -356,9 +400,12 @@ namespace trinity_amd {
                 virtual ~MatchesProxy() = default;
         };
 
-        // ---- what the default execution mode hands to the application (matches.h:34-130), positions only (no payloads)
-        struct term_hit {
-                tokenpos_t pos;
+        // ---- what the default execution mode hands to the application (matches.h:34-130); it fills positions only (payload and payloadLen stay 0 there:
+        //      PostingsListIterator::materialize_hits and IndexSource::term_hits_at fill all three)
+        struct term_hit { // runtime.h:8-20
+                uint64_t payload{0};
+                tokenpos_t pos{0};
+                uint8_t payloadLen{0};
         };
         struct term_hits {
                 tokenpos_t freq{0};
@@ -490,6 +537,40 @@ namespace trinity_amd {
                         d->isrc = this;
                         decoders.emplace_back(d);
                         return d;
+                }
+
+                // The hits of chosen (term, document) pairs in one engine call (tri_decode_hits_at) — what candidate_document::materialize_term_hits
+                // (queryexec_ctx.cpp:317-351) asks of the codec, for a caller that holds many candidates at once.  pairs: (row of the term table, document), in
+                // any order, repeats allowed.  freqs[i]: the document's stored frequency, 0xffffffff when the list does not hold it; pair i's hits are
+                // hits[offsets[i] .. offsets[i + 1])
+                struct pair_hits {
+                        std::vector<uint32_t> freqs;
+                        std::vector<uint64_t> offsets;
+                        std::vector<term_hit> hits;
+                };
+                pair_hits term_hits_at(const std::vector<std::pair<uint32_t, isrc_docid_t>> &pairs) const {
+                        std::vector<uint32_t> t(pairs.size()), d(pairs.size());
+                        for (size_t i = 0; i < pairs.size(); ++i) {
+                                t[i] = pairs[i].first;
+                                d[i] = pairs[i].second;
+                        }
+                        pair_hits r;
+                        r.freqs.resize(pairs.size());
+                        r.offsets.resize(pairs.size() + 1);
+                        check(tri_decode_hits_at(ix, t.data(), d.data(), t.size(), r.freqs.data(), nullptr, nullptr, nullptr, 0, r.offsets.data()));
+                        const size_t n = size_t(r.offsets.back());
+                        std::vector<uint16_t> pos(n);
+                        std::vector<uint8_t> len(n);
+                        std::vector<uint64_t> word(n);
+                        if (n)
+                                check(tri_decode_hits_at(ix, t.data(), d.data(), t.size(), r.freqs.data(), pos.data(), len.data(), word.data(), n, r.offsets.data()));
+                        r.hits.resize(n);
+                        for (size_t k = 0; k < n; ++k) {
+                                r.hits[k].payload = word[k];
+                                r.hits[k].pos = pos[k];
+                                r.hits[k].payloadLen = len[k];
+                        }
+                        return r;
                 }
 
                 // ---- iterator factories == queryexec_ctx::build_iterator's leaves and combinators (exec.cpp:253-449)
@@ -989,5 +1070,30 @@ namespace trinity_amd {
                         return;
                 uint64_t offs[2];
                 check(tri_decode_terms(isrc->handle(), &dec->termId, 1, docs.data(), freqs.data(), offs));
+        }
+        inline void Codecs::PostingsListIterator::materialize_hits(DocWordsSpace *dws, term_hit *out) {
+                if (!cursor || curDocument.id == DocIDsEND)
+                        return; // (no current document)
+                if (!hitsFetched) {
+                        hitsFetched = true;
+                        hitFirst.assign(freqs.size() + 1, 0);
+                        for (size_t j = 0; j < freqs.size(); ++j)
+                                hitFirst[j + 1] = hitFirst[j] + freqs[j];
+                        const size_t n = size_t(hitFirst.back());
+                        hitPos.resize(n);
+                        hitLen.resize(n);
+                        hitPayload.resize(n);
+                        uint64_t offs[2];
+                        if (n)
+                                check(tri_decode_hits(isrc->handle(), &dec->termId, 1, hitPos.data(), hitLen.data(), hitPayload.data(), n, offs));
+                }
+                const uint64_t at = hitFirst[cursor - 1];
+                for (uint32_t h = 0; h < freq; ++h) { // (freq: tokenpos_t, what the caller sized `out` by)
+                        out[h].payload = hitPayload[at + h];
+                        out[h].pos = hitPos[at + h];
+                        out[h].payloadLen = hitLen[at + h];
+                        if (dws && out[h].pos)
+                                dws->set(dec->execCtxTermID, out[h].pos);
+                }
         }
 } // namespace trinity_amd

@@ -502,6 +502,7 @@ struct tri_batch : BatchPlan {
 #include "k_encode.hpp"
 #include "k_phrase.hpp"
 #include "k_rich.hpp"
+#include "k_decode_hits.hpp"
 #include "k_tree.hpp"
 #include "k_tree_wide.hpp"
 #include "k_commit.hpp"
@@ -793,6 +794,153 @@ extern "C" int tri_decode_terms(tri_index *ix, const uint32_t *terms, size_t n, 
         hipFree(d_docs);
         hipFree(d_freqs);
         return TRI_OK;
+}
+
+// ---- the hits of whole lists / of (term, document) pairs (k_decode_hits.hpp)
+namespace {
+        struct DevBuf { // a device allocation of one call, released on every way out of it
+                void *p = nullptr;
+                ~DevBuf() { hipFree(p); }
+                template <class T>
+                T *as() const { return static_cast<T *>(p); }
+        };
+        int decode_hits_args(const tri_index *ix, const char *what, const uint32_t *terms, const size_t n, const uint8_t *payload_lens, const uint64_t *payloads) {
+                if ((payload_lens == nullptr) != (payloads == nullptr))
+                        return fail(TRI_ERR_INVALID, "%s: payload_lens and payloads are given together or not at all", what);
+                if (ix->codec == TRI_CODEC_LUCENE && !ix->has_hdir)
+                        return fail(TRI_ERR_INVALID, "%s: a LUCENE index uploaded without hits.data holds no positions", what);
+                for (size_t i = 0; i < n; ++i)
+                        if (terms[i] >= ix->terms.size())
+                                return fail(TRI_ERR_INVALID, "%s: term %u out of range", what, terms[i]);
+                return TRI_OK;
+        }
+        // the three output columns of `tot` hits on the device -> the caller's buffers
+        int decode_hits_fetch(tri_dev *dev, const uint64_t tot, const DevBuf &d_pos, const DevBuf &d_len, const DevBuf &d_pay, uint16_t *positions, uint8_t *payload_lens, uint64_t *payloads) {
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(positions, d_pos.p, tot * 2, hipMemcpyDeviceToHost, dev->stream));
+                if (payload_lens) {
+                        HIP_TRY(hipMemcpyAsync(payload_lens, d_len.p, tot, hipMemcpyDeviceToHost, dev->stream));
+                        HIP_TRY(hipMemcpyAsync(payloads, d_pay.p, tot * 8, hipMemcpyDeviceToHost, dev->stream));
+                }
+                HIP_TRY(hipStreamSynchronize(dev->stream));
+                return TRI_OK;
+        }
+} // namespace
+
+extern "C" int tri_decode_hits(tri_index *ix, const uint32_t *terms, size_t n, uint16_t *positions, uint8_t *payload_lens, uint64_t *payloads, size_t cap, uint64_t *out_offsets) {
+        if (!ix || (!terms && n) || !out_offsets)
+                return fail(TRI_ERR_INVALID, "tri_decode_hits: null argument");
+        if (const int rc = decode_hits_args(ix, "tri_decode_hits", terms, n, payload_lens, payloads))
+                return rc;
+        if (n > 0xffffffffull)
+                return fail(TRI_ERR_INVALID, "tri_decode_hits: too many terms");
+        tri_dev *dev = ix->dev;
+        HIP_TRY(hipSetDevice(dev->device));
+        std::vector<HitsJob> jobs(n);
+        std::vector<uint64_t> totals(n + 1, 0), offs(n + 1, 0);
+        uint64_t nblk = 0;
+        uint32_t maxblocks = 0;
+        for (size_t i = 0; i < n; ++i) {
+                const DevTerm &t = ix->terms[terms[i]];
+                jobs[i] = {terms[i], 0, nblk, 0};
+                nblk += t.nblocks;
+                maxblocks = std::max(maxblocks, t.nblocks);
+        }
+        const bool google = ix->codec == TRI_CODEC_GOOGLE;
+        DevBuf d_jobs, d_totals, d_cnt, d_pos, d_len, d_pay;
+        const uint32_t nj = (uint32_t)n, gy = std::min<uint32_t>(nj, 32768), gx = std::min<uint32_t>((maxblocks + 255) / 256, 4096);
+        if (nblk) {
+                // pass 1: hits per block (GOOGLE) and per job
+                HIP_TRY(hipMalloc(&d_jobs.p, n * sizeof(HitsJob)));
+                HIP_TRY(hipMalloc(&d_totals.p, n * 8));
+                HIP_TRY(hipMemcpyAsync(d_jobs.p, jobs.data(), n * sizeof(HitsJob), hipMemcpyHostToDevice, dev->stream));
+                HIP_TRY(hipMemsetAsync(d_totals.p, 0, n * 8, dev->stream));
+                if (google)
+                        HIP_TRY(hipMalloc(&d_cnt.p, nblk * 8));
+                TRI_LAUNCH(k_hits_count, ix->codec, google ? dim3(gx, gy) : dim3(1, gy), dim3(google ? 256 : 64), dev->stream, (const uint8_t *)ix->d_index, (const uint32_t *)ix->d_blk_off,
+                           (const uint32_t *)ix->d_blk_hits, (const DevTerm *)ix->d_terms, (const HitsJob *)d_jobs.as<HitsJob>(), nj, d_cnt.as<uint64_t>(), d_totals.as<uint64_t>());
+                if (google)
+                        hipLaunchKernelGGL(k_hits_scan, dim3(std::min<uint32_t>(nj, 4096)), dim3(256), 0, dev->stream, (const DevTerm *)ix->d_terms, (const HitsJob *)d_jobs.as<HitsJob>(), nj,
+                                           d_cnt.as<uint64_t>(), d_totals.as<uint64_t>());
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(totals.data(), d_totals.p, n * 8, hipMemcpyDeviceToHost, dev->stream));
+                HIP_TRY(hipStreamSynchronize(dev->stream));
+        }
+        for (size_t i = 0; i < n; ++i) {
+                jobs[i].hit_off = offs[i];
+                offs[i + 1] = offs[i] + totals[i];
+        }
+        const uint64_t tot = offs[n];
+        if (positions && tot > cap)
+                return fail(TRI_ERR_INVALID, "tri_decode_hits: %llu hits, room for %zu", (unsigned long long)tot, cap);
+        std::copy(offs.begin(), offs.end(), out_offsets);
+        if (!positions || !tot)
+                return TRI_OK;
+        // pass 2: the hits
+        HIP_TRY(hipMemcpyAsync(d_jobs.p, jobs.data(), n * sizeof(HitsJob), hipMemcpyHostToDevice, dev->stream));
+        HIP_TRY(hipMalloc(&d_pos.p, tot * 2 + 64));
+        if (payload_lens) {
+                HIP_TRY(hipMalloc(&d_len.p, tot + 64));
+                HIP_TRY(hipMalloc(&d_pay.p, tot * 8 + 64));
+        }
+        TRI_LAUNCH(k_decode_hits, ix->codec, dim3(gx, gy), dim3(256), dev->stream, (const uint8_t *)ix->d_index, (const uint8_t *)ix->d_hits, (const uint32_t *)ix->d_blk_off,
+                   (const uint32_t *)ix->d_blk_hits, (const uint32_t *)ix->d_hdir, (const DevTerm *)ix->d_terms, (const HitsJob *)d_jobs.as<HitsJob>(), nj,
+                   (const uint64_t *)d_cnt.as<uint64_t>(), d_pos.as<uint16_t>(), d_len.as<uint8_t>(), d_pay.as<uint64_t>());
+        return decode_hits_fetch(dev, tot, d_pos, d_len, d_pay, positions, payload_lens, payloads);
+}
+
+extern "C" int tri_decode_hits_at(tri_index *ix, const uint32_t *terms, const uint32_t *docids, size_t n, uint32_t *freqs, uint16_t *positions, uint8_t *payload_lens, uint64_t *payloads,
+                                  size_t cap, uint64_t *out_offsets) {
+        if (!ix || ((!terms || !docids || !freqs) && n) || !out_offsets)
+                return fail(TRI_ERR_INVALID, "tri_decode_hits_at: null argument");
+        if (const int rc = decode_hits_args(ix, "tri_decode_hits_at", terms, n, payload_lens, payloads))
+                return rc;
+        if (n > 0xffffffffull)
+                return fail(TRI_ERR_INVALID, "tri_decode_hits_at: too many pairs");
+        if (!n) {
+                out_offsets[0] = 0;
+                return TRI_OK;
+        }
+        tri_dev *dev = ix->dev;
+        HIP_TRY(hipSetDevice(dev->device));
+        const uint32_t np = (uint32_t)n;
+        const dim3 grid((np + 255) / 256);
+        DevBuf d_terms, d_docs, d_freqs, d_loc, d_off, d_pos, d_len, d_pay;
+        HIP_TRY(hipMalloc(&d_terms.p, n * 4));
+        HIP_TRY(hipMalloc(&d_docs.p, n * 4));
+        HIP_TRY(hipMalloc(&d_freqs.p, n * 4));
+        HIP_TRY(hipMalloc(&d_loc.p, n * 12)); // block, slot, hits of the block before the document
+        HIP_TRY(hipMemcpyAsync(d_terms.p, terms, n * 4, hipMemcpyHostToDevice, dev->stream));
+        HIP_TRY(hipMemcpyAsync(d_docs.p, docids, n * 4, hipMemcpyHostToDevice, dev->stream));
+        uint32_t *at_block = d_loc.as<uint32_t>(), *at_slot = at_block + n, *at_before = at_slot + n;
+        TRI_LAUNCH(k_hits_at_freq, ix->codec, grid, dim3(256), dev->stream, (const uint8_t *)ix->d_index, (const uint32_t *)ix->d_blk_last, (const uint32_t *)ix->d_blk_off,
+                   (const DevTerm *)ix->d_terms, (const uint32_t *)d_terms.as<uint32_t>(), (const uint32_t *)d_docs.as<uint32_t>(), np, d_freqs.as<uint32_t>(), at_block, at_slot, at_before);
+        HIP_TRY(hipGetLastError());
+        std::vector<uint32_t> fr(n);
+        HIP_TRY(hipMemcpyAsync(fr.data(), d_freqs.p, n * 4, hipMemcpyDeviceToHost, dev->stream));
+        HIP_TRY(hipStreamSynchronize(dev->stream));
+        std::vector<uint64_t> offs(n + 1, 0);
+        for (size_t i = 0; i < n; ++i)
+                offs[i + 1] = offs[i] + (fr[i] == DH_ABSENT ? 0u : fr[i]);
+        const uint64_t tot = offs[n];
+        if (positions && tot > cap)
+                return fail(TRI_ERR_INVALID, "tri_decode_hits_at: %llu hits, room for %zu", (unsigned long long)tot, cap);
+        std::copy(fr.begin(), fr.end(), freqs);
+        std::copy(offs.begin(), offs.end(), out_offsets);
+        if (!positions || !tot)
+                return TRI_OK;
+        HIP_TRY(hipMalloc(&d_off.p, n * 8));
+        HIP_TRY(hipMemcpyAsync(d_off.p, offs.data(), n * 8, hipMemcpyHostToDevice, dev->stream));
+        HIP_TRY(hipMalloc(&d_pos.p, tot * 2 + 64));
+        if (payload_lens) {
+                HIP_TRY(hipMalloc(&d_len.p, tot + 64));
+                HIP_TRY(hipMalloc(&d_pay.p, tot * 8 + 64));
+        }
+        TRI_LAUNCH(k_hits_at_write, ix->codec, grid, dim3(256), dev->stream, (const uint8_t *)ix->d_index, (const uint8_t *)ix->d_hits, (const uint32_t *)ix->d_blk_off,
+                   (const uint32_t *)ix->d_blk_hits, (const uint32_t *)ix->d_hdir, (const DevTerm *)ix->d_terms, (const uint32_t *)d_terms.as<uint32_t>(), np,
+                   (const uint32_t *)d_freqs.as<uint32_t>(), (const uint32_t *)at_block, (const uint32_t *)at_slot, (const uint32_t *)at_before, (const uint64_t *)d_off.as<uint64_t>(),
+                   d_pos.as<uint16_t>(), d_len.as<uint8_t>(), d_pay.as<uint64_t>());
+        return decode_hits_fetch(dev, tot, d_pos, d_len, d_pay, positions, payload_lens, payloads);
 }
 
 // ------------------------------------------------------------------------------------------ host: batches

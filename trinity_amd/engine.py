@@ -104,7 +104,7 @@ class TriBatchInfo(C.Structure):
 # every symbol include/trinity_hip.h declares (tests/test_abi.py checks the library exports all of them)
 ABI_SYMBOLS = [
     "tri_last_error", "tri_abi_version", "tri_dev_open", "tri_dev_close", "tri_dev_sync", "tri_dev_stream", "tri_dev_set_option", "tri_dev_get_option", "tri_dev_memory",
-    "tri_index_upload", "tri_index_destroy", "tri_index_get_info", "tri_index_term_docbytes", "tri_index_set_masked", "tri_decode_terms",
+    "tri_index_upload", "tri_index_destroy", "tri_index_get_info", "tri_index_term_docbytes", "tri_index_set_masked", "tri_decode_terms", "tri_decode_hits", "tri_decode_hits_at",
     "tri_batch_create", "tri_batch_query_status", "tri_batch_destroy", "tri_batch_run", "tri_batch_sync", "tri_batch_get_info",
     "tri_batch_match_counts", "tri_batch_docset", "tri_batch_docset_bitmap", "tri_batch_docsets", "tri_batch_docsets_mixed", "tri_batch_scores", "tri_batch_query_terms", "tri_batch_matched_terms", "tri_batch_query_terms_wide", "tri_batch_matched_terms_wide", "tri_batch_matched_payloads", "tri_batch_topk", "tri_batch_topk_device", "tri_batch_counts_device", "tri_batch_docset_hashes",
     "tri_cbatch_create", "tri_cbatch_destroy", "tri_cbatch_query_status", "tri_cbatch_run", "tri_cbatch_sync", "tri_cbatch_match_counts", "tri_cbatch_topk", "tri_cbatch_docset", "tri_encode_google", "tri_encode_google_payloads", "tri_commit_google", "tri_commit_lucene", "tri_merge_google", "tri_merge_lucene", "tri_encode_lucene",
@@ -141,6 +141,8 @@ def hip_lib():
     L.tri_index_term_docbytes.argtypes = [vp, vp, C.c_size_t, vp]
     L.tri_index_set_masked.argtypes = [vp, vp, C.c_size_t]
     L.tri_decode_terms.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+    L.tri_decode_hits.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp]
+    L.tri_decode_hits_at.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t, vp]
     L.tri_batch_create.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(vp)]
     L.tri_batch_query_status.argtypes = [vp, vp]
     L.tri_batch_destroy.argtypes = [vp]
@@ -496,6 +498,38 @@ class Index:
         _check(hip_lib().tri_decode_terms(self.h, t.ctypes.data, t.size, docs.ctypes.data, freqs.ctypes.data if want_freqs else None, offs.ctypes.data))
         assert int(offs[-1]) == tot, (int(offs[-1]), tot)
         return docs, freqs, offs
+
+    def decode_hits(self, terms, want_payloads=False):
+        """The hits of whole postings lists (tri_decode_hits: materialize_hits for every document, in list order), sized then filled.
+        -> (positions u16, payload lengths u8, payload words u64, offsets u64[n + 1] in hits); lengths and words are None unless want_payloads."""
+        t = np.ascontiguousarray(terms, dtype=np.uint32)
+        offs = np.zeros(t.size + 1, dtype=np.uint64)
+        _check(hip_lib().tri_decode_hits(self.h, t.ctypes.data, t.size, None, None, None, 0, offs.ctypes.data))
+        tot = int(offs[-1])
+        pos = np.zeros(max(1, tot), dtype=np.uint16)
+        lens = np.zeros(max(1, tot), dtype=np.uint8) if want_payloads else None
+        words = np.zeros(max(1, tot), dtype=np.uint64) if want_payloads else None
+        _check(hip_lib().tri_decode_hits(self.h, t.ctypes.data, t.size, pos.ctypes.data, lens.ctypes.data if want_payloads else None, words.ctypes.data if want_payloads else None,
+                                         tot, offs.ctypes.data))  # fmt: skip
+        assert int(offs[-1]) == tot
+        return pos[:tot], lens[:tot] if want_payloads else None, words[:tot] if want_payloads else None, offs
+
+    def decode_hits_at(self, terms, docids, want_payloads=False):
+        """The hits of terms[i] in document docids[i] (tri_decode_hits_at), sized then filled.  -> (freqs u32[n]: the stored frequency, 0xffffffff where the
+        list does not hold the document; positions, payload lengths, payload words as decode_hits; offsets u64[n + 1])."""
+        t = np.ascontiguousarray(terms, dtype=np.uint32)
+        d = np.ascontiguousarray(docids, dtype=np.uint32)
+        assert t.size == d.size
+        freqs = np.zeros(max(1, t.size), dtype=np.uint32)
+        offs = np.zeros(t.size + 1, dtype=np.uint64)
+        _check(hip_lib().tri_decode_hits_at(self.h, t.ctypes.data, d.ctypes.data, t.size, freqs.ctypes.data, None, None, None, 0, offs.ctypes.data))
+        tot = int(offs[-1])
+        pos = np.zeros(max(1, tot), dtype=np.uint16)
+        lens = np.zeros(max(1, tot), dtype=np.uint8) if want_payloads else None
+        words = np.zeros(max(1, tot), dtype=np.uint64) if want_payloads else None
+        _check(hip_lib().tri_decode_hits_at(self.h, t.ctypes.data, d.ctypes.data, t.size, freqs.ctypes.data, pos.ctypes.data, lens.ctypes.data if want_payloads else None,
+                                            words.ctypes.data if want_payloads else None, tot, offs.ctypes.data))  # fmt: skip
+        return freqs[: t.size], pos[:tot], lens[:tot] if want_payloads else None, words[:tot] if want_payloads else None, offs
 
     def close(self):
         if self.h:

@@ -74,6 +74,18 @@ class HostIndex:
     def from_segment(cls, seg):
         return cls(seg.index, seg.terms, seg.docs_cnt, codec=seg.codec, hits=seg.hits)
 
+    def hits_dir(self, term):
+        """(blk_hits[] of the term's directory rows, nfull): where each row's hits start as the upload records it — GOOGLE: bytes past the block's payload
+        offset, bit 31 = BLK_HITS_PLAIN; LUCENE with hits.data: the hit ordinal within the term — and the term's full 128-hit groups in hits.data."""
+        L = _lib()
+        L.tri_host_index_hits_dir.restype = C.c_uint32
+        L.tri_host_index_hits_dir.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+        nfull = C.c_uint32()
+        n = L.tri_host_index_hits_dir(self.h, term, None, C.byref(nfull))
+        out = np.zeros(max(1, n), dtype=np.uint32)
+        L.tri_host_index_hits_dir(self.h, term, out.ctypes.data, C.byref(nfull))
+        return out[:n], nfull.value
+
     def close(self):
         if self.h:
             _lib().tri_host_index_free(self.h)
