@@ -31,7 +31,8 @@ extern "C" {
                                 within 9: tri_filter_create / tri_filter_from_docset / tri_filter_destroy / tri_batch_set_filters (per-query document filters on the device);
                                 within 9: options tree_max_nodes / tree_wide_min_nodes (query trees of up to 1024 nodes; no new export, no struct grew);
                                 within 9: option rich_max_terms, tri_batch_query_terms_wide / tri_batch_matched_terms_wide (the default mode reports up to 64 matched terms per query; no struct grew);
-                                within 9: tri_decode_hits / tri_decode_hits_at (the codec seam's materialize_hits: the hits of whole lists and of chosen documents; no struct grew) */
+                                within 9: tri_decode_hits / tri_decode_hits_at (the codec seam's materialize_hits: the hits of whole lists and of chosen documents; no struct grew);
+                                within 9: tri_batch_set_ranker / tri_batch_ranked (the default mode ranks its matches on the device: a proximity score, top-K per query; no struct grew) */
 
 /* status codes */
 #define TRI_OK 0
@@ -392,6 +393,41 @@ int tri_batch_matched_terms_wide(tri_batch *, size_t q, uint64_t *present /* [n]
  * *n == *npos): lens[i] = term_hit::payloadLen, payloads[i] = term_hit::payload — the word as materialize_hits leaves it, i.e. only its
  * first lens[i] bytes belong to this hit (google_codec.cpp:533-594).  Pass lens == payloads == NULL to learn *n. */
 int tri_batch_matched_payloads(tri_batch *, size_t q, uint8_t *lens, uint64_t *payloads, size_t cap, size_t *n);
+/* TRI_FLAG_MATCHED_TERMS batches (with or without TRI_FLAG_HIT_PAYLOADS): RANK the matches on the device.  The default mode exists for application-side
+ * relevance: consider(const matched_document &) receives matchedTerms[] and their hits (matches.h:109-153; queryexec_ctx.cpp:382-648) and the application
+ * scores them, usually by proximity.  With a ranker set, tri_batch_sync computes that score on the device, from the masks, frequency rows and positions the
+ * two k_rich passes wrote, and keeps per query the top-K (docID, score) pairs; only those leave the device.  The score is a function of exactly what
+ * tri_batch_matched_terms reports.  Query q has reportable terms in slots 0 .. R-1, in tri_batch_query_terms[_wide]'s order; w[k] = the weight of the program
+ * token where slot k's term first appears among the reportable tokens (every TERM token outside the excluded side of a NOT; weights: one double per program
+ * token, as tri_batch_create's; NULL: 1.0 each).  For a match d, with freq[k] and pos(k) as tri_batch_matched_terms reports them:
+ *
+ *   score(d) = ( sum over present slots k, ascending k:  w[k] * double(min(freq[k], freq_cap)) )
+ *              + adjacency * double( sum over k = 0 .. R-2 with slots k and k+1 both present:
+ *                                    #{ hits h of slot k with pos(h) != 0 and pos(h) + 1 in pos(k+1) } )
+ *
+ * Position 0 never pairs: it is the position of a payload-only hit, and DocWordsSpace never holds it.  A term missing from the document contributes nothing,
+ * nor does one the document holds but the query does not report there (the allow mask of general trees, the excluded side of a NOT).  IEEE double, in exactly
+ * the order written — the sum over k first, then one multiply and one add for the pair term —, never contracted into fused multiply-adds: a sequential
+ * restatement in host doubles is bit-equal.  Ranking: score descending, docID ascending (tri_batch_topk's rule).  Slots follow first appearance in the query, so
+ * slots k and k+1 are consecutive query tokens: what an application detects with toNextSpan and dws->test(next, pos + 1).
+ *
+ * tri_batch_set_ranker: before tri_batch_run; holds for every later run until replaced or removed (spec == NULL).  TRI_ERR_INVALID, the batch left as it was:
+ * another mode, topk 0 or above 256, freq_cap 0, an unknown kind, non-zero reserved, a non-finite weight or adjacency, a negative adjacency.  Negative weights
+ * are legal.  tri_batch_ranked: after tri_batch_sync — docids / scores [nq][topk] row-major, counts[nq] = min(matches, topk); rows past counts[q] are zero; a
+ * query the planner left out (tri_batch_query_status) has count 0.  TRI_ERR_INVALID when no ranker is set or the batch has not been synced since it was.
+ * tri_batch_matched_terms*, tri_batch_docset and the rest keep working on a ranked batch; a caller that wants only the ranking does not call them, and then
+ * nothing but the top-K block is copied.  (tri_dev_get_option "rich_write_last_us" / "rank_last_us", read-only: the device time of the last ranked batch's
+ * WRITE pass and rank pass.)  Not ranked: the collections of tri_cbatch_*, tri_gather_results. */
+#define TRI_RANK_PROXIMITY 1u
+typedef struct tri_ranker {
+        uint32_t kind;     /* TRI_RANK_PROXIMITY */
+        uint32_t topk;     /* 1 .. 256 (TOPK_MAX) */
+        uint32_t freq_cap; /* >= 1: a term's frequency counts up to this */
+        uint32_t reserved; /* 0 */
+        double adjacency;  /* added per adjacent pair; finite, >= 0 */
+} tri_ranker;
+int tri_batch_set_ranker(tri_batch *, const tri_ranker *spec /* NULL: remove */, const double *weights /* one per program token, as tri_batch_create's; NULL: 1.0 */);
+int tri_batch_ranked(tri_batch *, uint32_t *docids /* [nq][topk] */, double *scores /* [nq][topk] */, uint32_t *counts /* [nq] = min(matches, topk) */);
 /* AccumulatedScore with topk >= 1: docids/scores are [nq][topk] row-major, counts[nq] = min(matches, topk) */
 int tri_batch_topk(tri_batch *, uint32_t *docids, float *scores, uint32_t *counts);
 /* device-resident result blocks for the multi-GPU gather (per rank: [nq][topk] u32 + f32, [nq] u32); valid once the run has

@@ -121,9 +121,24 @@ def build_mirror_hits_test(force=False):
     return MIRROR_HITS_BIN
 
 
+MIRROR_RANK_SRC = os.path.join(ROOT, "tests", "cpp", "host_mirror_rank_test.cpp")
+MIRROR_RANK_BIN = os.path.join(ROOT, "tests", "cpp", "host_mirror_rank_test")
+
+
+def build_mirror_rank_test(force=False):
+    """exec_query's default mode with a ProximityRanker (csrc/host/trinity_gpu.hpp: ranked on the device through tri_batch_set_ranker, and through the per-match replay)
+    compiled into its driver; in-tree, so that it travels to the GPU box, where tests/test_host_mirror_rank.py runs it."""
+    deps = [MIRROR_RANK_SRC, os.path.join(PKG, "csrc", "host", "trinity_gpu.hpp"), os.path.join(PKG, "csrc", "host", "google_encoder.hpp"), os.path.join(ROOT, "include", "trinity_hip.h")]
+    if force or _newer(MIRROR_RANK_BIN, deps):
+        build_hip()
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", MIRROR_RANK_BIN, MIRROR_RANK_SRC, "-L" + PKG, "-ltrinity_hip", "-Wl,-rpath,$ORIGIN/../../trinity_amd"]
+        subprocess.run(cmd, check=True)
+    return MIRROR_RANK_BIN
+
+
 def build_all(force=False):
     return (build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force), build_mirror_wide_terms_test(force),
-            build_mirror_hits_test(force))
+            build_mirror_hits_test(force), build_mirror_rank_test(force))
 
 
 def kernels_stamp():

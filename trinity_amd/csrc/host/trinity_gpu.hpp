@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <memory>
 #include <stdexcept>
@@ -435,7 +436,86 @@ namespace trinity_amd {
                                 consider(ids[i]);
                 }
                 virtual void consider(const docid_t, const double) {}
+                // A filter whose consider(const matched_document &) is the engine's own proximity ranker (ProximityRanker below) says so here: it fills in the
+                // tri_ranker and the weights of the query's terms (per matchedTerms[].queryCtx->term.id - 1) and returns where the ranked list goes; the default
+                // mode's exec_query then ranks on the device (tri_batch_set_ranker) and replays no match.  nullptr (every other filter): consider() per match.
+                virtual std::vector<std::pair<docid_t, double>> *device_ranker(tri_ranker *, std::vector<double> *) { return nullptr; }
                 virtual ~MatchedIndexDocumentsFilter() = default;
+        };
+
+        // The application-side definition of tri_batch_set_ranker's TRI_RANK_PROXIMITY score, in C++: what an application's consider(const matched_document &)
+        // (matches.h:109-153) computes from matchedTerms[] (queryexec_ctx.cpp:382-648) when it ranks by capped term frequency and adjacency of consecutive
+        // query terms —
+        //   score = (sum over the matched terms, ascending term id: weight[id - 1] * double(min(freq, freq_cap)))
+        //           + adjacency * double(hits of term id at a position p != 0 with term id + 1 at p + 1, over the ids matched together with their successor)
+        // — and a K-heap under the rule score descending, docID ascending.  exec_query's default mode recognises it (device_ranker) and, with device == true, has
+        // the engine compute the same list on the device; device = false keeps the per-match replay through consider(), for comparison.
+        struct ProximityRanker : public MatchedIndexDocumentsFilter {
+                uint32_t topk, freq_cap;
+                double adjacency;
+                std::vector<double> weights; // per query term, in the order of the query's terms (term.id - 1); a term past the end weighs 1.0
+                bool device{true};
+                std::vector<std::pair<docid_t, double>> list; // the kept matches; ranked() orders them
+
+                explicit ProximityRanker(uint32_t k, uint32_t cap = 65535, double adj = 0.0, std::vector<double> w = {})
+                    : topk{k}, freq_cap{cap}, adjacency{adj}, weights(std::move(w)) {}
+
+                static bool better(const std::pair<docid_t, double> &a, const std::pair<docid_t, double> &b) {
+                        return a.second > b.second || (a.second == b.second && a.first < b.first);
+                }
+                // (one rounding per operation, as the contract writes it: the products are kept out of fused multiply-adds)
+                static double score_of(const matched_document &md, const std::vector<double> &weights, const uint32_t freq_cap, const double adjacency) {
+                        const term_hits *by[65] = {};
+                        for (uint16_t i = 0; i < md.matchedTermsCnt; ++i) {
+                                const uint32_t id = md.matchedTerms[i].queryCtx->term.id;
+                                if (id >= 1 && id <= 64)
+                                        by[id] = md.matchedTerms[i].hits;
+                        }
+                        double sum = 0.0;
+                        uint64_t pairs = 0;
+                        for (uint32_t id = 1; id <= 64; ++id) {
+                                if (!by[id])
+                                        continue;
+                                const double w = id - 1 < weights.size() ? weights[id - 1] : 1.0;
+                                volatile double term = w * double(std::min<uint32_t>(by[id]->freq, freq_cap));
+                                sum += term;
+                                if (id < 64 && by[id + 1]) {
+                                        const term_hits *a = by[id], *b = by[id + 1];
+                                        uint32_t j = 0;
+                                        for (uint32_t i = 0; i < a->freq; ++i) {
+                                                const uint32_t p = a->all[i].pos;
+                                                if (!p)
+                                                        continue;
+                                                while (j < b->freq && b->all[j].pos < p + 1u)
+                                                        ++j;
+                                                pairs += j < b->freq && b->all[j].pos == p + 1u;
+                                        }
+                                }
+                        }
+                        volatile double bonus = adjacency * double(pairs);
+                        return sum + bonus;
+                }
+                void consider(const matched_document &md) override {
+                        list.emplace_back(md.id, score_of(md, weights, freq_cap, adjacency));
+                        std::push_heap(list.begin(), list.end(), better); // (the heap's top: the worst kept match)
+                        if (list.size() > topk) {
+                                std::pop_heap(list.begin(), list.end(), better);
+                                list.pop_back();
+                        }
+                }
+                std::vector<std::pair<docid_t, double>> *device_ranker(tri_ranker *spec, std::vector<double> *w) override {
+                        if (!device)
+                                return nullptr;
+                        *spec = tri_ranker{TRI_RANK_PROXIMITY, topk, freq_cap, 0, adjacency};
+                        *w = weights;
+                        return &list;
+                }
+                // best first: score descending, docID ascending
+                std::vector<std::pair<docid_t, double>> ranked() const {
+                        auto out = list;
+                        std::sort(out.begin(), out.end(), better);
+                        return out;
+                }
         };
 
         struct IndexDocumentsFilter { // matches.h:198-201: return true to disregard the document
@@ -714,7 +794,8 @@ namespace trinity_amd {
         // (docset_iterators_scorers.cpp:16-22), create + run one batch.
         // docFilters: per query its device filter (IndexDocumentsFilter::device_filter; nullptr: none), installed before the run; empty: no query has one.
         inline BatchPtr run_batch(IndexSource *src, const std::vector<DocsSetIterators::Iterator *> &roots, uint32_t flags, uint32_t topk,
-                                  Similarity::IndexSourceTermsScorer *scorer, const std::vector<tri_filter *> &docFilters = {}) {
+                                  Similarity::IndexSourceTermsScorer *scorer, const std::vector<tri_filter *> &docFilters = {},
+                                  const std::function<void(tri_batch *, const std::vector<uint32_t> &, const std::vector<tri_query> &)> &beforeRun = nullptr) {
                 validate_flags(flags);
                 const bool scored = flags & unsigned(ExecFlags::AccumulatedScoreScheme);
                 if (!(flags & (unsigned(ExecFlags::DocumentsOnly) | unsigned(ExecFlags::AccumulatedScoreScheme))))
@@ -755,6 +836,8 @@ namespace trinity_amd {
                         if (!distinct.empty())
                                 check(tri_batch_set_filters(b, distinct.data(), distinct.size(), of_query.data()));
                 }
+                if (beforeRun) // (the default mode's device ranker: set on the compiled batch, from the program it was compiled from)
+                        beforeRun(b, prog, qs);
                 check(tri_batch_run(b));
                 check(tri_batch_sync(b));
                 return bp;
@@ -828,6 +911,35 @@ namespace trinity_amd {
         // (prepare_match, queryexec_ctx.cpp:522-648) — rebuilt here from the engine's packed arrays.
         inline void exec_query_default_mode(DocsSetIterators::Iterator *root, IndexSource *src, MatchedIndexDocumentsFilter *mf, IndexDocumentsFilter *df) {
                 tri_filter *const onDevice = df ? df->device_filter() : nullptr;
+                // a filter that IS the engine's proximity ranker (and no document filter the device does not hold): the ranking is computed on the device, K pairs
+                // come back, no match is replayed
+                tri_ranker spec{};
+                std::vector<double> termWeights;
+                std::vector<std::pair<docid_t, double>> *const rankedInto = (!df || onDevice) ? mf->device_ranker(&spec, &termWeights) : nullptr;
+                if (rankedInto) {
+                        auto b = run_batch(src, {root}, 0, 0, nullptr, onDevice ? std::vector<tri_filter *>{onDevice} : std::vector<tri_filter *>{},
+                                           [&](tri_batch *bt, const std::vector<uint32_t> &prog, const std::vector<tri_query> &qs) {
+                                                   // the ABI takes a weight per program token: every TERM token gets the weight of its term's place among the query's terms
+                                                   uint32_t terms[64], nt = 0;
+                                                   check(tri_batch_query_terms_wide(bt, 0, terms, &nt));
+                                                   std::vector<double> w(prog.size(), 1.0);
+                                                   for (uint32_t i = qs[0].prog_off; i < qs[0].prog_off + qs[0].prog_len; ++i)
+                                                           if ((prog[i] >> 28) == TRI_OP_TERM) {
+                                                                   const uint32_t k = uint32_t(std::find(terms, terms + nt, prog[i] & 0x0fffffffu) - terms);
+                                                                   if (k < nt && k < termWeights.size())
+                                                                           w[i] = termWeights[k];
+                                                           }
+                                                   check(tri_batch_set_ranker(bt, &spec, w.data()));
+                                           });
+                        std::vector<uint32_t> ids(spec.topk);
+                        std::vector<double> scores(spec.topk);
+                        uint32_t cnt = 0;
+                        check(tri_batch_ranked(b.get(), ids.data(), scores.data(), &cnt));
+                        rankedInto->clear();
+                        for (uint32_t i = 0; i < cnt; ++i)
+                                rankedInto->emplace_back(ids[i], scores[i]);
+                        return;
+                }
                 auto b = run_batch(src, {root}, 0, 0, nullptr, onDevice ? std::vector<tri_filter *>{onDevice} : std::vector<tri_filter *>{});
                 if (onDevice)
                         df = nullptr; // (the batch has dropped its documents: nothing to ask per match)

@@ -72,6 +72,7 @@ struct tri_dev {
         hipEvent_t ev_fork, ev_join;
         int cus;
         tri_options opt;
+        uint64_t rich_write_last_us = 0, rank_last_us = 0; // the last ranked batch's WRITE pass and rank pass (tri_dev_get_option, read-only)
         int refs = 0;         // indexes and batches alive on this handle ...
         bool closing = false; // ... tri_dev_close with some left: the handle goes with the last of them
         // The large buffers of a batch (output regions, score streams, term planes, decoded lists) and its plan arena are recycled from
@@ -449,6 +450,15 @@ struct tri_batch : BatchPlan {
         uint8_t *d_filter_tab = nullptr;
         uint32_t *d_filter_rows = nullptr;
         size_t filter_rows_cap = 0; // rows d_filter_rows holds
+        // tri_batch_set_ranker (k_rich_rank.hpp): the spec, ONE pooled block — [a weight per sterms[] entry][the tasks' partial lists][the queries' ranked lists] —
+        // and the caller's program (kept by default-mode batches: the ranker's weights come one per program token)
+        bool rank_on = false, rank_done = false;
+        tri_ranker rank{};
+        uint8_t *d_rank_block = nullptr;
+        double *d_rank_w = nullptr, *d_rank_part_scores = nullptr, *d_rank_scores = nullptr;
+        uint32_t *d_rank_part_docs = nullptr, *d_rank_part_counts = nullptr, *d_rank_docs = nullptr, *d_rank_counts = nullptr;
+        std::vector<uint32_t> h_prog;
+        std::vector<tri_query> h_queries;
         tri_batch_info info{};
         ~tri_batch() { // also runs when tri_batch_create fails half-way: nothing allocated so far is leaked
                 if (dev) {
@@ -486,6 +496,7 @@ struct tri_batch : BatchPlan {
                 pool_free(dev, d_scat_docs);
                 pool_free(dev, d_filter_tab);
                 pool_free(dev, d_filter_rows);
+                pool_free(dev, d_rank_block);
                 dev_release(dev);
         }
 };
@@ -502,6 +513,7 @@ struct tri_batch : BatchPlan {
 #include "k_encode.hpp"
 #include "k_phrase.hpp"
 #include "k_rich.hpp"
+#include "k_rich_rank.hpp"
 #include "k_decode_hits.hpp"
 #include "k_tree.hpp"
 #include "k_tree_wide.hpp"
@@ -600,6 +612,11 @@ extern "C" int tri_dev_set_option(tri_dev *d, const char *name, uint64_t value) 
 extern "C" int tri_dev_get_option(tri_dev *d, const char *name, uint64_t *value) {
         if (!d || !name || !value)
                 return fail(TRI_ERR_INVALID, "tri_dev_get_option: null argument");
+        // (read-only: the device time of the last ranked batch's WRITE pass and rank pass — HIP events around them, tri_batch_sync)
+        if (!strcmp(name, "rich_write_last_us") || !strcmp(name, "rank_last_us")) {
+                *value = !strcmp(name, "rich_write_last_us") ? d->rich_write_last_us : d->rank_last_us;
+                return TRI_OK;
+        }
         const uint64_t *slot = option_slot(d->opt, name);
         if (!slot)
                 return fail(TRI_ERR_INVALID, "tri_dev_get_option: unknown option '%s'", name);
@@ -1251,6 +1268,8 @@ extern "C" int tri_batch_create(tri_index *ix, const uint32_t *prog, size_t prog
                                                                                   //  the matches of queries that hold a phrase are ever read — k_score, k_tree_leaves)
         }
         if (rich) {
+                b->h_prog.assign(prog, prog + prog_len); // (tri_batch_set_ranker maps its per-token weights onto the reportable terms)
+                b->h_queries.assign(queries, queries + nq);
                 b->rich_R = std::max<uint32_t>(b->rich_R, 1);
                 HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_present, (off + 64) * 4));
                 HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_freq, (off + 64) * 2 * b->rich_R));
@@ -1735,6 +1754,7 @@ extern "C" int tri_batch_run(tri_batch *b) {
         DevLock dev_lock(dev->mu);
         HIP_TRY(hipSetDevice(dev->device));
         b->synced = false;
+        b->rank_done = false;
 #ifdef TRI_TRACE
         if (!g_trace_host) {
                 HIP_TRY(hipHostMalloc((void **)&g_trace_host, 64 * 16, hipHostMallocMapped | hipHostMallocCoherent));
@@ -2020,6 +2040,31 @@ static int account_matches(tri_batch *b) {
         return TRI_OK;
 }
 
+// a ranked default-mode batch (tri_batch_set_ranker), right behind the WRITE pass: every task's matches scored and cut to the task's best K (k_rich_rank,
+// over the same two sections of the rich schedule as launch_rich), then the tasks' lists folded per query (k_rank_merge)
+static int launch_rank(tri_batch *b) {
+        tri_dev *dev = b->dev;
+        const uint32_t n_wide = b->n_rich_wide, n = (uint32_t)b->tasks.size() - n_wide;
+        const uint32_t *sched = n_wide ? b->dev_at(b->rich_sched) : b->dev_at(b->sched);
+        const RichWideArgs wd{b->d_rich_present_hi, b->d_rich_allow_hi, b->d_rich_freq_wide, b->dev_opt(b->rich_wide)};
+#define RANK_ARGS(SCHED, N)                                                                                                                                                                \
+        b->dev_at(b->plan), b->dev_at(b->tasks), SCHED, N, (const uint32_t *)b->d_out, (const uint32_t *)b->d_counts, b->rich_R, (const uint32_t *)b->d_rich_present,                     \
+                (const uint16_t *)b->d_rich_freq, (const uint64_t *)b->d_task_pos_base, (const uint16_t *)b->d_rich_pool, (const double *)b->d_rank_w, b->rank.freq_cap,                  \
+                b->rank.adjacency, b->rank.topk, b->d_rank_part_docs, b->d_rank_part_scores, b->d_rank_part_counts
+        if (n)
+                hipLaunchKernelGGL(k_rich_rank<false>, dim3(std::min<uint32_t>(n, (uint32_t)dev->cus * 8)), dim3(AND_WG), 0, dev->stream, RANK_ARGS(sched, n), RichWideArgs{});
+        if (n_wide)
+                hipLaunchKernelGGL(k_rich_rank<true>, dim3(std::min<uint32_t>(n_wide, (uint32_t)dev->cus * 8)), dim3(AND_WG), 0, dev->stream, RANK_ARGS(sched + n, n_wide), wd);
+#undef RANK_ARGS
+        HIP_TRY(hipGetLastError());
+        const uint32_t nqs = (uint32_t)b->plan.size();
+        hipLaunchKernelGGL(k_rank_merge, dim3(std::min<uint32_t>(nqs, (uint32_t)dev->cus * 8)), dim3(AND_WG), 0, dev->stream, b->dev_at(b->plan), nqs, b->rank.topk,
+                           (const uint32_t *)b->d_rank_part_docs, (const double *)b->d_rank_part_scores, (const uint32_t *)b->d_rank_part_counts, b->d_rank_docs, b->d_rank_scores,
+                           b->d_rank_counts);
+        HIP_TRY(hipGetLastError());
+        return TRI_OK;
+}
+
 // TRI_FLAG_MATCHED_TERMS: the COUNT pass left every task's hit total — turned into pool offsets here (the pool is packed: task after task in
 // query order, inside a task match-major then term-minor) —, then the WRITE pass fills in the positions
 static int rich_write_pass(tri_batch *b) {
@@ -2049,9 +2094,40 @@ static int rich_write_pass(tri_batch *b) {
         }
         HIP_TRY(hipMemcpy(b->d_task_pos_base, b->h_task_pos_base.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemsetAsync(b->d_ticket + TICKET_RICH_WRITE_WORD, 0, (TICKET_RICH_WIDE + 1) * 4, dev->stream)); // (the wide instantiation's word too)
+        // (a ranked batch: the WRITE pass and the rank pass timed apart — options rich_write_last_us / rank_last_us; the events go back to the handle's pool on
+        //  every way out of the function)
+        struct RankEvents {
+                tri_dev *dev;
+                hipEvent_t e[3] = {};
+                ~RankEvents() {
+                        for (hipEvent_t x : e)
+                                if (x)
+                                        event_put(dev, x);
+                }
+        } rk{dev};
+        hipEvent_t(&rev)[3] = rk.e;
+        if (b->rank_on) {
+                for (hipEvent_t &e : rev)
+                        HIP_TRY(event_get(dev, &e));
+                HIP_TRY(hipEventRecord(rev[0], dev->stream));
+        }
         if (const int rc = launch_rich<true>(b))
                 return rc;
+        if (b->rank_on) {
+                HIP_TRY(hipEventRecord(rev[1], dev->stream));
+                if (const int rc = launch_rank(b))
+                        return rc;
+                HIP_TRY(hipEventRecord(rev[2], dev->stream));
+        }
         HIP_TRY(hipStreamSynchronize(dev->stream));
+        if (b->rank_on) {
+                float w_ms = 0, r_ms = 0;
+                HIP_TRY(hipEventElapsedTime(&w_ms, rev[0], rev[1]));
+                HIP_TRY(hipEventElapsedTime(&r_ms, rev[1], rev[2]));
+                dev->rich_write_last_us = (uint64_t)(w_ms * 1000.0f);
+                dev->rank_last_us = (uint64_t)(r_ms * 1000.0f);
+                b->rank_done = true;
+        }
         b->info.algorithmic_bytes += 2 * total + 4 * b->info.matches; // + the positions handed over and a present mask per match
         return TRI_OK;
 }
@@ -2253,6 +2329,135 @@ extern "C" int tri_batch_matched_payloads(tri_batch *b, size_t q, uint8_t *lens,
                 HIP_TRY(hipMemcpy(lens, b->d_rich_plen + p0, *n, hipMemcpyDeviceToHost));
         if (*n && payloads)
                 HIP_TRY(hipMemcpy(payloads, b->d_rich_payload + p0, *n * 8, hipMemcpyDeviceToHost));
+        return TRI_OK;
+}
+
+// tri_batch_set_ranker: which program tokens the default mode reports — every TERM token outside the excluded side of a NOT (the second operand's subtree)
+static void reportable_tokens(const uint32_t *prog, const uint32_t plen, std::vector<uint8_t> &rep) {
+        rep.assign(plen, 1);
+        std::vector<uint32_t> start; // per sub-program on the evaluation stack: its first token
+        for (uint32_t i = 0; i < plen; ++i) {
+                const uint32_t op = prog[i] >> 28, arg = prog[i] & 0x0fffffffu;
+                uint32_t kids = 0;
+                if (op == TRI_OP_AND || op == TRI_OP_OR || op == TRI_OP_PHRASE)
+                        kids = arg;
+                else if (op == TRI_OP_NOT || op == TRI_OP_OPT)
+                        kids = 2;
+                else if (op == TRI_OP_SOME)
+                        kids = arg & 0xffffu;
+                if (op == TRI_OP_TERM || kids == 0 || kids > start.size()) { // (a malformed program never got past tri_batch_create)
+                        start.push_back(i);
+                        continue;
+                }
+                if (op == TRI_OP_NOT)
+                        for (uint32_t t = start.back(); t < i; ++t)
+                                rep[t] = 0;
+                const uint32_t first = start[start.size() - kids];
+                start.resize(start.size() - kids);
+                start.push_back(first);
+        }
+}
+
+extern "C" int tri_batch_set_ranker(tri_batch *b, const tri_ranker *spec, const double *weights) {
+        if (!b)
+                return fail(TRI_ERR_INVALID, "tri_batch_set_ranker: null batch");
+        if (!(b->flags & TRI_FLAG_MATCHED_TERMS))
+                return fail(TRI_ERR_INVALID, "tri_batch_set_ranker: mode: not a TRI_FLAG_MATCHED_TERMS batch (the ranker scores the default mode's matched terms)");
+        tri_dev *dev = b->dev;
+        if (spec) {
+                if (spec->kind != TRI_RANK_PROXIMITY)
+                        return fail(TRI_ERR_INVALID, "tri_batch_set_ranker: kind %u is unknown (TRI_RANK_PROXIMITY)", spec->kind);
+                if (spec->topk < 1 || spec->topk > TOPK_MAX)
+                        return fail(TRI_ERR_INVALID, "tri_batch_set_ranker: topk %u (1 .. %u)", spec->topk, TOPK_MAX);
+                if (spec->freq_cap < 1)
+                        return fail(TRI_ERR_INVALID, "tri_batch_set_ranker: freq_cap 0 (>= 1)");
+                if (spec->reserved)
+                        return fail(TRI_ERR_INVALID, "tri_batch_set_ranker: reserved must be 0");
+                if (!std::isfinite(spec->adjacency) || spec->adjacency < 0)
+                        return fail(TRI_ERR_INVALID, "tri_batch_set_ranker: adjacency must be finite and >= 0");
+                if (weights)
+                        for (size_t i = 0; i < b->h_prog.size(); ++i)
+                                if (!std::isfinite(weights[i]))
+                                        return fail(TRI_ERR_INVALID, "tri_batch_set_ranker: weights[%zu] is not finite", i);
+        }
+        DevLock dev_lock(dev->mu);
+        HIP_TRY(hipSetDevice(dev->device));
+        const uint32_t had = b->rank_on ? 2u + (b->n_rich_wide && b->tasks.size() > b->n_rich_wide ? 1u : 0u) : 0u; // (k_rich_rank per section of the schedule + k_rank_merge)
+        if (!spec) {
+                pool_free(dev, b->d_rank_block);
+                b->d_rank_block = nullptr;
+                b->rank_on = b->rank_done = false;
+                b->info.launches -= had;
+                return TRI_OK;
+        }
+        // slot k's weight: that of the first reportable token that names the slot's term
+        const size_t ns = b->sterms.size(), nt = b->tasks.size(), nq = b->nq, K = spec->topk;
+        std::vector<double> w(ns + 1, 1.0);
+        if (weights) {
+                std::vector<uint8_t> rep;
+                for (size_t qi = 0; qi < nq; ++qi) {
+                        const uint32_t slot = b->slot_of_query[qi];
+                        if (slot == UINT32_MAX)
+                                continue;
+                        const DevQuery &dq = b->plan[slot];
+                        const uint32_t *prog = b->h_prog.data() + b->h_queries[qi].prog_off;
+                        const uint32_t plen = b->h_queries[qi].prog_len;
+                        reportable_tokens(prog, plen, rep);
+                        for (uint32_t k = 0; k < dq.nscore; ++k) {
+                                const uint32_t term = b->sterms[dq.score_base + k];
+                                uint32_t at = UINT32_MAX;
+                                for (uint32_t i = 0; i < plen && at == UINT32_MAX; ++i)
+                                        if ((prog[i] >> 28) == TRI_OP_TERM && (prog[i] & 0x0fffffffu) == term && rep[i])
+                                                at = i;
+                                if (at != UINT32_MAX)
+                                        w[dq.score_base + k] = weights[b->h_queries[qi].prog_off + at];
+                        }
+                }
+        }
+        size_t a = 0;
+        auto carve = [&](size_t bytes) {
+                const size_t at = a;
+                a += (bytes + 255) & ~(size_t)255;
+                return at;
+        };
+        const size_t a_w = carve((ns + 1) * 8), a_ps = carve((nt * K + 1) * 8), a_pd = carve((nt * K + 1) * 4), a_pc = carve((nt + 1) * 4), a_zero = a;
+        const size_t a_s = carve((nq * K + 1) * 8), a_d = carve((nq * K + 1) * 4), a_c = carve((nq + 1) * 4);
+        uint8_t *blk = nullptr;
+        HIP_TRY(pool_alloc(dev, (void **)&blk, a + 256));
+        // (the rows of queries the planner left out are never written: they stay zero)
+        if (hipMemsetAsync(blk + a_zero, 0, a - a_zero, dev->stream) != hipSuccess || hipMemcpyAsync(blk + a_w, w.data(), (ns + 1) * 8, hipMemcpyHostToDevice, dev->stream) != hipSuccess ||
+            hipStreamSynchronize(dev->stream) != hipSuccess) {
+                pool_free(dev, blk);
+                return fail(TRI_ERR_DEVICE, "tri_batch_set_ranker: %s", hipGetErrorString(hipGetLastError()));
+        }
+        pool_free(dev, b->d_rank_block);
+        b->d_rank_block = blk;
+        b->d_rank_w = (double *)(blk + a_w);
+        b->d_rank_part_scores = (double *)(blk + a_ps);
+        b->d_rank_part_docs = (uint32_t *)(blk + a_pd);
+        b->d_rank_part_counts = (uint32_t *)(blk + a_pc);
+        b->d_rank_scores = (double *)(blk + a_s);
+        b->d_rank_docs = (uint32_t *)(blk + a_d);
+        b->d_rank_counts = (uint32_t *)(blk + a_c);
+        b->rank = *spec;
+        b->rank_on = true;
+        b->rank_done = false;
+        b->info.launches += 2u + (b->n_rich_wide && nt > b->n_rich_wide ? 1u : 0u) - had;
+        return TRI_OK;
+}
+
+extern "C" int tri_batch_ranked(tri_batch *b, uint32_t *docids, double *scores, uint32_t *counts) {
+        if (!b || !docids || !scores || !counts)
+                return fail(TRI_ERR_INVALID, "tri_batch_ranked: null argument");
+        if (!b->rank_on)
+                return fail(TRI_ERR_INVALID, "tri_batch_ranked: no ranker is set (tri_batch_set_ranker)");
+        if (!b->synced || (!b->rank_done && !b->tasks.empty()))
+                return fail(TRI_ERR_INVALID, "tri_batch_ranked: tri_batch_sync first (a run that follows tri_batch_set_ranker)");
+        HIP_TRY(hipSetDevice(b->dev->device));
+        const size_t K = b->rank.topk;
+        HIP_TRY(hipMemcpy(docids, b->d_rank_docs, b->nq * K * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(scores, b->d_rank_scores, b->nq * K * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(counts, b->d_rank_counts, b->nq * 4, hipMemcpyDeviceToHost));
         return TRI_OK;
 }
 

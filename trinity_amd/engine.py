@@ -35,6 +35,13 @@ class TriQuery(C.Structure):
     _fields_ = [("prog_off", C.c_uint32), ("prog_len", C.c_uint32)]
 
 
+class TriRanker(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("topk", C.c_uint32), ("freq_cap", C.c_uint32), ("reserved", C.c_uint32), ("adjacency", C.c_double)]
+
+
+RANK_PROXIMITY = 1
+
+
 class TriIndexInfo(C.Structure):
     _fields_ = [
         ("index_bytes", C.c_uint64),
@@ -106,7 +113,7 @@ ABI_SYMBOLS = [
     "tri_last_error", "tri_abi_version", "tri_dev_open", "tri_dev_close", "tri_dev_sync", "tri_dev_stream", "tri_dev_set_option", "tri_dev_get_option", "tri_dev_memory",
     "tri_index_upload", "tri_index_destroy", "tri_index_get_info", "tri_index_term_docbytes", "tri_index_set_masked", "tri_decode_terms", "tri_decode_hits", "tri_decode_hits_at",
     "tri_batch_create", "tri_batch_query_status", "tri_batch_destroy", "tri_batch_run", "tri_batch_sync", "tri_batch_get_info",
-    "tri_batch_match_counts", "tri_batch_docset", "tri_batch_docset_bitmap", "tri_batch_docsets", "tri_batch_docsets_mixed", "tri_batch_scores", "tri_batch_query_terms", "tri_batch_matched_terms", "tri_batch_query_terms_wide", "tri_batch_matched_terms_wide", "tri_batch_matched_payloads", "tri_batch_topk", "tri_batch_topk_device", "tri_batch_counts_device", "tri_batch_docset_hashes",
+    "tri_batch_match_counts", "tri_batch_docset", "tri_batch_docset_bitmap", "tri_batch_docsets", "tri_batch_docsets_mixed", "tri_batch_scores", "tri_batch_query_terms", "tri_batch_matched_terms", "tri_batch_query_terms_wide", "tri_batch_matched_terms_wide", "tri_batch_matched_payloads", "tri_batch_set_ranker", "tri_batch_ranked", "tri_batch_topk", "tri_batch_topk_device", "tri_batch_counts_device", "tri_batch_docset_hashes",
     "tri_cbatch_create", "tri_cbatch_destroy", "tri_cbatch_query_status", "tri_cbatch_run", "tri_cbatch_sync", "tri_cbatch_match_counts", "tri_cbatch_topk", "tri_cbatch_docset", "tri_encode_google", "tri_encode_google_payloads", "tri_commit_google", "tri_commit_lucene", "tri_merge_google", "tri_merge_lucene", "tri_encode_lucene",
     "tri_comm_unique_id", "tri_comm_create", "tri_comm_create_custom", "tri_comm_destroy", "tri_gather_results",
     "tri_filter_create", "tri_filter_from_docset", "tri_filter_destroy", "tri_batch_set_filters",
@@ -190,6 +197,8 @@ def hip_lib():
     L.tri_filter_destroy.argtypes = [vp]
     L.tri_filter_destroy.restype = None
     L.tri_batch_set_filters.argtypes = [vp, vp, C.c_size_t, vp]
+    L.tri_batch_set_ranker.argtypes = [vp, vp, vp]
+    L.tri_batch_ranked.argtypes = [vp, vp, vp, vp]
     _hip = L
     return L
 
@@ -612,6 +621,29 @@ class Batch:
         arr = (C.c_void_p * max(1, len(filters)))(*[f.h for f in filters])
         _check(hip_lib().tri_batch_set_filters(self.h, arr if filters else None, len(filters), foq.ctypes.data if filters else None))
         self._filters = filters
+
+    def set_ranker(self, topk, freq_cap=65535, adjacency=0.0, weights=None):
+        """FLAG_MATCHED_TERMS batches: rank every query's matches on the device for the runs that follow (tri_batch_set_ranker, TRI_RANK_PROXIMITY):
+        score = sum over the present reportable terms of weight * min(freq, freq_cap), + adjacency per hit of term k that term k + 1 follows at the next
+        position.  weights: one per token of the flattened program (as tri_batch_create's), None: 1.0 each.  Results: ranked()."""
+        spec = TriRanker(RANK_PROXIMITY, topk, freq_cap, 0, adjacency)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        _check(hip_lib().tri_batch_set_ranker(self.h, C.byref(spec), None if w is None else w.ctypes.data))
+        self.rank_topk = topk
+
+    def clear_ranker(self):
+        _check(hip_lib().tri_batch_set_ranker(self.h, None, None))
+        self.rank_topk = 0
+
+    def ranked(self):
+        """After sync(): (docids u32[nq, topk], scores f64[nq, topk], counts u32[nq]) — per query its best min(matches, topk) documents, score descending,
+        docID ascending; rows past counts[q] are zero."""
+        k = max(1, getattr(self, "rank_topk", 0))
+        d = np.zeros((self.nq, k), dtype=np.uint32)
+        s = np.zeros((self.nq, k), dtype=np.float64)
+        c = np.zeros(self.nq, dtype=np.uint32)
+        _check(hip_lib().tri_batch_ranked(self.h, d.ctypes.data, s.ctypes.data, c.ctypes.data))
+        return d, s, c
 
     def run(self):
         _check(hip_lib().tri_batch_run(self.h))
