@@ -9,7 +9,9 @@
  * Threading: one tri_dev per (host thread, device) — with ONE exception, made for a caller that keeps the engine stream fed: while one
  * thread runs, awaits, reads and destroys batches of a device (tri_batch_run / _sync / the result calls / _destroy), other threads may
  * compile the next ones (tri_batch_create) on the same device; the handle's pools, the index's plane cache and everything that enqueues on
- * its streams are locked for that.  The host planner — most of a create — runs outside that lock, in one of the handle's TWO planner
+ * its streams are locked for that.  The result calls keep ONE rule: a result copy of a synced batch is enqueued on the handle's read-back stream
+ * under that lock and awaited OUTSIDE it — no result call touches the engine stream, none holds the lock while it waits, so a read waits for nothing
+ * queued behind its batch and holds up no thread that compiles or runs the next one.  The host planner — most of a create — runs outside that lock, in one of the handle's TWO planner
  * contexts (a pool of host threads each): two creates plan side by side, a third waits for a context.  Everything else (uploads, options,
  * the write side) stays one thread at a time.  tri_last_error() is per thread.
  */

@@ -34,7 +34,7 @@ def hipcc():
 
 
 def build_hip(force=False):
-    if force or _newer(LIB_HIP, _deps(HIP_SRCS)):
+    if force or _newer(LIB_HIP, _deps(HIP_SRCS) + [os.path.join(PKG, "csrc", "host", "result_rows.hpp")]):  # (read_side.hpp's host transforms)
         cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-o", LIB_HIP] + HIP_SRCS + ["-ldl"]
         subprocess.run(cmd, check=True)
     return LIB_HIP

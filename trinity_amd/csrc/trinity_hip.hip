@@ -17,8 +17,9 @@
 //                    one lane per needed block, merging the decoded docs against the candidates in LDS
 //                    (Conjuction::next_impl leapfrog, docset_iterators.cpp:308-348, as a set operation)
 //
-// The write side — the encoders, commit and merge on the device (tri_encode_*, tri_commit_*, tri_merge_*) — is write_side.hpp, included
-// at the end of this file: the same translation unit, as the k_*.hpp kernel files are.
+// The read side — every result call of a batch and of a collection batch — is read_side.hpp, included behind the batch runtime; the write side — the
+// encoders, commit and merge on the device (tri_encode_*, tri_commit_*, tri_merge_*) — is write_side.hpp, included at the end of this file: the same
+// translation unit, as the k_*.hpp kernel files are.
 #include "../../include/trinity_hip.h"
 #include <chrono>
 #include <hip/hip_runtime.h>
@@ -229,6 +230,12 @@ static void pool_free(tri_dev *dev, void *p) {
                 P.idle.erase(P.idle.begin() + (ptrdiff_t)big);
         }
 }
+struct DevBuf { // a device allocation of one call (not pooled), released on every way out of it
+        void *p = nullptr;
+        ~DevBuf() { hipFree(p); }
+        template <class T>
+        T *as() const { return static_cast<T *>(p); }
+};
 // pinned host block of at least `bytes` (64-byte aligned: hipHostMalloc is page-aligned); *cap = its size
 static uint8_t *pinned_alloc(tri_dev *dev, const size_t bytes, size_t *cap) {
         DevLock g(dev->mu);
@@ -786,13 +793,14 @@ extern "C" int tri_decode_terms(tri_index *ix, const uint32_t *terms, size_t n, 
         out_offsets[n] = tot;
         if (!tot || !docs)
                 return TRI_OK;
-        DecodeJob *d_jobs = nullptr;
-        uint32_t *d_docs = nullptr, *d_freqs = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_jobs, n * sizeof(DecodeJob)));
-        HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), n * sizeof(DecodeJob), hipMemcpyHostToDevice, dev->stream));
-        HIP_TRY(hipMalloc((void **)&d_docs, padded * 4));
+        DevBuf jobs_buf, docs_buf, freqs_buf;
+        HIP_TRY(hipMalloc(&jobs_buf.p, n * sizeof(DecodeJob)));
+        HIP_TRY(hipMemcpyAsync(jobs_buf.p, jobs.data(), n * sizeof(DecodeJob), hipMemcpyHostToDevice, dev->stream));
+        HIP_TRY(hipMalloc(&docs_buf.p, padded * 4));
         if (freqs)
-                HIP_TRY(hipMalloc((void **)&d_freqs, padded * 4));
+                HIP_TRY(hipMalloc(&freqs_buf.p, padded * 4));
+        DecodeJob *d_jobs = jobs_buf.as<DecodeJob>();
+        uint32_t *d_docs = docs_buf.as<uint32_t>(), *d_freqs = freqs_buf.as<uint32_t>();
         dim3 grid(std::min<uint32_t>((maxblocks + 255) / 256, 4096), (uint32_t)n);
         TRI_LAUNCH(k_decode_terms, ix->codec, grid, dim3(256), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_terms, d_jobs, d_docs,
                            d_freqs);
@@ -807,20 +815,11 @@ extern "C" int tri_decode_terms(tri_index *ix, const uint32_t *terms, size_t n, 
                         HIP_TRY(hipMemcpyAsync(freqs + out_offsets[i], d_freqs + jobs[i].out_off, (size_t)t.documents * 4, hipMemcpyDeviceToHost, dev->stream));
         }
         HIP_TRY(hipStreamSynchronize(dev->stream));
-        hipFree(d_jobs);
-        hipFree(d_docs);
-        hipFree(d_freqs);
         return TRI_OK;
 }
 
 // ---- the hits of whole lists / of (term, document) pairs (k_decode_hits.hpp)
 namespace {
-        struct DevBuf { // a device allocation of one call, released on every way out of it
-                void *p = nullptr;
-                ~DevBuf() { hipFree(p); }
-                template <class T>
-                T *as() const { return static_cast<T *>(p); }
-        };
         int decode_hits_args(const tri_index *ix, const char *what, const uint32_t *terms, const size_t n, const uint8_t *payload_lens, const uint64_t *payloads) {
                 if ((payload_lens == nullptr) != (payloads == nullptr))
                         return fail(TRI_ERR_INVALID, "%s: payload_lens and payloads are given together or not at all", what);
@@ -2177,161 +2176,6 @@ extern "C" int tri_batch_sync(tri_batch *b) {
         return TRI_OK;
 }
 
-extern "C" int tri_batch_query_terms(tri_batch *b, size_t q, uint32_t *terms, uint32_t *nterms) {
-        if (!b || !terms || !nterms || q >= b->nq)
-                return fail(TRI_ERR_INVALID, "bad argument");
-        if (!(b->flags & TRI_FLAG_MATCHED_TERMS))
-                return fail(TRI_ERR_INVALID, "not a TRI_FLAG_MATCHED_TERMS batch");
-        const uint32_t slot = b->slot_of_query[q];
-        *nterms = 0;
-        if (slot == UINT32_MAX)
-                return TRI_OK;
-        const DevQuery &dq = b->plan[slot];
-        if (dq.nscore > RICH_NARROW_TERMS) // (never past terms[16])
-                return fail(TRI_ERR_INVALID, "tri_batch_query_terms: query %zu reports %u terms (option rich_max_terms): call tri_batch_query_terms_wide", q, dq.nscore);
-        for (uint32_t k = 0; k < dq.nscore; ++k)
-                terms[k] = b->sterms[dq.score_base + k];
-        *nterms = dq.nscore;
-        return TRI_OK;
-}
-
-extern "C" int tri_batch_query_terms_wide(tri_batch *b, size_t q, uint32_t *terms, uint32_t *nterms) {
-        if (!b || !terms || !nterms || q >= b->nq)
-                return fail(TRI_ERR_INVALID, "bad argument");
-        if (!(b->flags & TRI_FLAG_MATCHED_TERMS))
-                return fail(TRI_ERR_INVALID, "not a TRI_FLAG_MATCHED_TERMS batch");
-        const uint32_t slot = b->slot_of_query[q];
-        *nterms = 0;
-        if (slot == UINT32_MAX)
-                return TRI_OK;
-        const DevQuery &dq = b->plan[slot];
-        for (uint32_t k = 0; k < dq.nscore && k < RICH_WIDE_TERMS; ++k)
-                terms[k] = b->sterms[dq.score_base + k];
-        *nterms = std::min(dq.nscore, RICH_WIDE_TERMS);
-        return TRI_OK;
-}
-
-// tri_batch_matched_terms (present: 32-bit masks) and tri_batch_matched_terms_wide (wide_call; present64: a narrow query's mask zero-extended)
-static int matched_terms_impl(tri_batch *b, size_t q, uint32_t *present, uint64_t *present64, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos, const bool wide_call) {
-        if (!b || !npos || q >= b->nq)
-                return fail(TRI_ERR_INVALID, "bad argument");
-        if (!(b->flags & TRI_FLAG_MATCHED_TERMS))
-                return fail(TRI_ERR_INVALID, "not a TRI_FLAG_MATCHED_TERMS batch");
-        if (!b->synced)
-                return fail(TRI_ERR_INVALID, "tri_batch_sync first");
-        *npos = 0;
-        const uint32_t slot = b->slot_of_query[q];
-        if (slot == UINT32_MAX)
-                return TRI_OK;
-        const DevQuery &dq = b->plan[slot];
-        const bool wide_q = dq.nscore > RICH_NARROW_TERMS; // a wide-report query: rows and high mask halves of its own (BatchPlan::rich_wide)
-        if (wide_q && !wide_call) // (a 32-bit mask would be truncated)
-                return fail(TRI_ERR_INVALID, "tri_batch_matched_terms: query %zu reports %u terms (option rich_max_terms): call tri_batch_matched_terms_wide", q, dq.nscore);
-        tri_dev *dev = b->ix->dev;
-        HIP_TRY(hipSetDevice(dev->device));
-        // the query's tasks are consecutive, so its hits are one contiguous run of the pool
-        const uint64_t p0 = b->h_task_pos_base[dq.first_task], p1 = b->h_task_pos_base[dq.first_task + dq.ntasks];
-        *npos = (size_t)(p1 - p0);
-        if (positions) {
-                if (pos_cap < *npos)
-                        return fail(TRI_ERR_INVALID, "positions need %zu slots, %zu given", *npos, pos_cap);
-                if (*npos)
-                        HIP_TRY(hipMemcpyAsync(positions, b->d_rich_pool + p0, *npos * 2, hipMemcpyDeviceToHost, dev->stream));
-        }
-        // per-match rows live at the tasks' out[] slots; freq rows are R wide on the device, nscore wide for the caller
-        size_t w = 0;
-        std::vector<uint16_t> rows;
-        // present64: a segment's low words are copied (asynchronously, like the narrow call's) into the UPPER half of the segment's own u64 cells and widened in
-        // place once the copies have landed (front to back: cell i is written from word c + i, which no earlier cell's store reaches); a wide-report query's
-        // high words wait in a staging array meanwhile
-        std::vector<uint32_t> hi;
-        std::vector<std::pair<size_t, uint32_t>> segs; // (first cell, matches) per task segment
-        if (present64 && wide_q) {
-                size_t n = 0;
-                for (uint32_t t = 0; t < dq.ntasks; ++t)
-                        n += b->h_counts[dq.first_task + t];
-                hi.resize(n);
-        }
-        for (uint32_t t = 0; t < dq.ntasks; ++t) {
-                const uint32_t c = b->h_counts[dq.first_task + t];
-                if (!c)
-                        continue;
-                const uint64_t off = b->tasks[dq.first_task + t].out_off;
-                if (present)
-                        HIP_TRY(hipMemcpyAsync(present + w, b->d_rich_present + off, (size_t)c * 4, hipMemcpyDeviceToHost, dev->stream));
-                if (present64) { // the low words from where they always were; a wide-report query's high words from its slots of the second array
-                        HIP_TRY(hipMemcpyAsync(reinterpret_cast<uint32_t *>(present64 + w) + c, b->d_rich_present + off, (size_t)c * 4, hipMemcpyDeviceToHost, dev->stream));
-                        if (wide_q)
-                                HIP_TRY(hipMemcpyAsync(hi.data() + w, b->d_rich_present_hi + b->rich_wide[slot].slots + (off - dq.out_off), (size_t)c * 4, hipMemcpyDeviceToHost, dev->stream));
-                        segs.emplace_back(w, c);
-                }
-                if (freq && wide_q) { // rows `stride` cells apart on the device, nscore wide for the caller
-                        const DevRichWide &rw = b->rich_wide[slot];
-                        rows.resize((size_t)c * rw.stride);
-                        HIP_TRY(hipMemcpy(rows.data(), b->d_rich_freq_wide + rw.cells + (off - dq.out_off) * rw.stride, (size_t)c * 2 * rw.stride, hipMemcpyDeviceToHost));
-                        for (size_t i = 0; i < c; ++i)
-                                for (uint32_t k = 0; k < dq.nscore; ++k)
-                                        freq[(w + i) * dq.nscore + k] = rows[i * rw.stride + k];
-                } else if (freq) {
-                        if (b->rich_R == dq.nscore)
-                                HIP_TRY(hipMemcpyAsync(freq + w * dq.nscore, b->d_rich_freq + off * b->rich_R, (size_t)c * 2 * b->rich_R, hipMemcpyDeviceToHost, dev->stream));
-                        else {
-                                rows.resize((size_t)c * b->rich_R);
-                                HIP_TRY(hipMemcpy(rows.data(), b->d_rich_freq + off * b->rich_R, (size_t)c * 2 * b->rich_R, hipMemcpyDeviceToHost));
-                                for (size_t i = 0; i < c; ++i)
-                                        for (uint32_t k = 0; k < dq.nscore; ++k)
-                                                freq[(w + i) * dq.nscore + k] = rows[i * b->rich_R + k];
-                        }
-                }
-                w += c;
-        }
-        HIP_TRY(hipStreamSynchronize(dev->stream));
-        for (const auto &sg : segs) {
-                const uint32_t *lo = reinterpret_cast<const uint32_t *>(present64 + sg.first) + sg.second;
-                for (size_t i = 0; i < sg.second; ++i) {
-                        uint32_t l;
-                        memcpy(&l, lo + i, 4);
-                        present64[sg.first + i] = (uint64_t)l | (wide_q ? (uint64_t)hi[sg.first + i] << 32 : 0ull);
-                }
-        }
-        return TRI_OK;
-}
-
-extern "C" int tri_batch_matched_terms(tri_batch *b, size_t q, uint32_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos) {
-        return matched_terms_impl(b, q, present, nullptr, freq, positions, pos_cap, npos, false);
-}
-extern "C" int tri_batch_matched_terms_wide(tri_batch *b, size_t q, uint64_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos) {
-        return matched_terms_impl(b, q, nullptr, present, freq, positions, pos_cap, npos, true);
-}
-
-// the payloads of query q's hits, parallel to the positions tri_batch_matched_terms returns (same order, same count); for a wide-report query: to those of
-// tri_batch_matched_terms_wide
-extern "C" int tri_batch_matched_payloads(tri_batch *b, size_t q, uint8_t *lens, uint64_t *payloads, size_t cap, size_t *n) {
-        if (!b || !n || q >= b->nq)
-                return fail(TRI_ERR_INVALID, "bad argument");
-        if (!(b->flags & TRI_FLAG_MATCHED_TERMS) || !(b->flags & TRI_FLAG_HIT_PAYLOADS))
-                return fail(TRI_ERR_INVALID, "not a TRI_FLAG_MATCHED_TERMS | TRI_FLAG_HIT_PAYLOADS batch");
-        if (!b->synced)
-                return fail(TRI_ERR_INVALID, "tri_batch_sync first");
-        *n = 0;
-        const uint32_t slot = b->slot_of_query[q];
-        if (slot == UINT32_MAX)
-                return TRI_OK;
-        const DevQuery &dq = b->plan[slot];
-        const uint64_t p0 = b->h_task_pos_base[dq.first_task], p1 = b->h_task_pos_base[dq.first_task + dq.ntasks];
-        *n = (size_t)(p1 - p0);
-        if (!lens && !payloads)
-                return TRI_OK;
-        if (cap < *n)
-                return fail(TRI_ERR_INVALID, "payloads need %zu slots, %zu given", *n, cap);
-        HIP_TRY(hipSetDevice(b->ix->dev->device));
-        if (*n && lens)
-                HIP_TRY(hipMemcpy(lens, b->d_rich_plen + p0, *n, hipMemcpyDeviceToHost));
-        if (*n && payloads)
-                HIP_TRY(hipMemcpy(payloads, b->d_rich_payload + p0, *n * 8, hipMemcpyDeviceToHost));
-        return TRI_OK;
-}
-
 // tri_batch_set_ranker: which program tokens the default mode reports — every TERM token outside the excluded side of a NOT (the second operand's subtree)
 static void reportable_tokens(const uint32_t *prog, const uint32_t plen, std::vector<uint8_t> &rep) {
         rep.assign(plen, 1);
@@ -2446,278 +2290,31 @@ extern "C" int tri_batch_set_ranker(tri_batch *b, const tri_ranker *spec, const 
         return TRI_OK;
 }
 
-extern "C" int tri_batch_ranked(tri_batch *b, uint32_t *docids, double *scores, uint32_t *counts) {
-        if (!b || !docids || !scores || !counts)
-                return fail(TRI_ERR_INVALID, "tri_batch_ranked: null argument");
-        if (!b->rank_on)
-                return fail(TRI_ERR_INVALID, "tri_batch_ranked: no ranker is set (tri_batch_set_ranker)");
-        if (!b->synced || (!b->rank_done && !b->tasks.empty()))
-                return fail(TRI_ERR_INVALID, "tri_batch_ranked: tri_batch_sync first (a run that follows tri_batch_set_ranker)");
-        HIP_TRY(hipSetDevice(b->dev->device));
-        const size_t K = b->rank.topk;
-        HIP_TRY(hipMemcpy(docids, b->d_rank_docs, b->nq * K * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(scores, b->d_rank_scores, b->nq * K * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(counts, b->d_rank_counts, b->nq * 4, hipMemcpyDeviceToHost));
-        return TRI_OK;
-}
-
-extern "C" int tri_batch_get_info(const tri_batch *b, tri_batch_info *info) {
-        if (!b || !info)
-                return fail(TRI_ERR_INVALID, "null argument");
-        *info = b->info;
-        return TRI_OK;
-}
-
-extern "C" int tri_batch_query_status(const tri_batch *b, int32_t *status) {
-        if (!b || !status)
-                return fail(TRI_ERR_INVALID, "null argument");
-        for (size_t q = 0; q < b->nq; ++q)
-                status[q] = b->qstatus[q];
-        return TRI_OK;
-}
-
-extern "C" int tri_batch_match_counts(tri_batch *b, uint64_t *counts) {
-        if (!b || !counts)
-                return fail(TRI_ERR_INVALID, "null argument");
-        if (!b->synced)
-                return fail(TRI_ERR_INVALID, "tri_batch_sync first");
-        for (size_t q = 0; q < b->nq; ++q)
-                counts[q] = b->slot_of_query[q] == UINT32_MAX ? 0 : b->h_query_counts[b->slot_of_query[q]];
-        return TRI_OK;
-}
-
-extern "C" int tri_batch_docset(tri_batch *b, size_t q, uint32_t *out, size_t cap, size_t *n) {
-        if (!b || !n || q >= b->nq)
-                return fail(TRI_ERR_INVALID, "bad argument");
-        if (!b->synced)
-                return fail(TRI_ERR_INVALID, "tri_batch_sync first");
-        const uint32_t slot = b->slot_of_query[q];
-        *n = slot == UINT32_MAX ? 0 : b->h_query_counts[slot];
-        if (!*n || !out)
-                return TRI_OK;
-        if (b->plan[slot].ntasks && !b->plan[slot].out_cap && task_onepass(b->tasks[b->plan[slot].first_task].kind))
-                return fail(TRI_ERR_INVALID, "query %zu ran through the one-pass scored kernel: an AccumulatedScore top-K batch keeps top-K lists and match counts, not docID sets (use topk == 0 or DocumentsOnly)", q);
-        if (cap < *n)
-                return fail(TRI_ERR_INVALID, "docset needs %zu slots, %zu given", *n, cap);
-        HIP_TRY(hipSetDevice(b->ix->dev->device));
-        // the docID set is the in-order concatenation of the query's task segments
-        const DevQuery &dq = b->plan[slot];
-        if (dq.form == RESULT_BITMAP) { // one bit per document (dev_structs.hpp): the region's words come over as they are, the docIDs are written out here
-                const uint32_t w_lo = b->tasks[dq.first_task].tile_begin, w_hi = b->tasks[dq.first_task + dq.ntasks - 1].tile_end;
-                std::vector<uint32_t> words((size_t)(w_hi - w_lo) * SPAN_WORDS);
-                HIP_TRY(hipMemcpy(words.data(), b->d_out + dq.out_off, words.size() * 4, hipMemcpyDeviceToHost));
-                size_t w = 0;
-                for (size_t i = 0; i < words.size(); ++i)
-                        for (uint32_t m = words[i]; m; m &= m - 1u) {
-                                if (w == *n)
-                                        return fail(TRI_ERR_INTERNAL, "query %zu: its bitmap holds more documents than its tasks counted", q);
-                                out[w++] = (uint32_t)(((size_t)w_lo * SPAN_WORDS + i) * 32u + (uint32_t)__builtin_ctz(m));
-                        }
-                if (w != *n)
-                        return fail(TRI_ERR_INTERNAL, "query %zu: its bitmap holds %zu documents, its tasks counted %zu", q, w, *n);
-                return TRI_OK;
+// a collection batch (tri_cbatch_create ... below: "collections of segments"; here, because its result calls are read_side.hpp's too)
+struct tri_cbatch {
+        std::vector<tri_batch *> parts;
+        std::vector<uint32_t *> d_slots; // per part: caller query -> plan slot
+        DevSource *d_src = nullptr;
+        uint32_t *d_top_docs = nullptr, *d_top_counts = nullptr;
+        float *d_top_scores = nullptr;
+        uint64_t *d_counts = nullptr;
+        bool ran = false, synced = false;
+        ~tri_cbatch() {
+                if (!parts.empty())
+                        hipSetDevice(parts[0]->ix->dev->device);
+                for (auto p : d_slots)
+                        hipFree(p);
+                hipFree(d_src);
+                hipFree(d_top_docs);
+                hipFree(d_top_counts);
+                hipFree(d_top_scores);
+                hipFree(d_counts);
         }
-        // (the batch is synced: its results are complete — the copies go on the read-back stream and wait for nothing queued behind the batch)
-        DevLock g(b->ix->dev->mu);
-        size_t w = 0;
-        for (uint32_t t = 0; t < dq.ntasks; ++t) {
-                const uint32_t c = b->h_counts[dq.first_task + t];
-                if (!c)
-                        continue;
-                const uint32_t *src = b->d_out + b->tasks[dq.first_task + t].out_off;
-                HIP_TRY(hipMemcpyAsync(out + w, src, (size_t)c * 4, hipMemcpyDeviceToHost, b->ix->dev->stream_rb));
-                w += c;
-        }
-        HIP_TRY(hipStreamSynchronize(b->ix->dev->stream_rb));
-        return TRI_OK;
-}
+};
 
-// The docID set of query q as the engine holds it when the planner chose the bitmap form for it (dev_structs.hpp RESULT_BITMAP: DocumentsOnly
-// unions / conjunctions of head terms): *first_doc = the docID of bit 0 of words[0] (a multiple of 32), *nwords = the words that follow — bit j of
-// word i: document *first_doc + 32 i + j matches.  words == NULL: only *form (0 docIDs: use tri_batch_docset; 1 bitmap), *first_doc, *nwords.
-extern "C" int tri_batch_docset_bitmap(tri_batch *b, size_t q, int *form, uint32_t *words, size_t cap, uint32_t *first_doc, size_t *nwords) {
-        if (!b || !form || !first_doc || !nwords || q >= b->nq)
-                return fail(TRI_ERR_INVALID, "bad argument");
-        if (!b->synced)
-                return fail(TRI_ERR_INVALID, "tri_batch_sync first");
-        const uint32_t slot = b->slot_of_query[q];
-        *form = 0, *first_doc = 0, *nwords = 0;
-        if (slot == UINT32_MAX || b->plan[slot].form != RESULT_BITMAP)
-                return TRI_OK;
-        const DevQuery &dq = b->plan[slot];
-        const uint32_t w_lo = b->tasks[dq.first_task].tile_begin, w_hi = b->tasks[dq.first_task + dq.ntasks - 1].tile_end;
-        *form = 1;
-        *first_doc = w_lo * SPAN_BITS;
-        *nwords = (size_t)(w_hi - w_lo) * SPAN_WORDS;
-        if (!words)
-                return TRI_OK;
-        if (cap < *nwords)
-                return fail(TRI_ERR_INVALID, "bitmap needs %zu words, %zu given", *nwords, cap);
-        HIP_TRY(hipSetDevice(b->ix->dev->device));
-        HIP_TRY(hipMemcpy(words, b->d_out + dq.out_off, *nwords * 4, hipMemcpyDeviceToHost));
-        return TRI_OK;
-}
-
-extern "C" int tri_batch_docset_hashes(tri_batch *b, uint64_t *hashes) {
-        if (!b || !hashes)
-                return fail(TRI_ERR_INVALID, "null argument");
-        if (!b->synced)
-                return fail(TRI_ERR_INVALID, "tri_batch_sync first");
-        tri_dev *dev = b->ix->dev;
-        HIP_TRY(hipSetDevice(dev->device));
-        const uint32_t n = (uint32_t)b->plan.size();
-        if ((b->n_fused + b->n_fused16 + b->n_fusedgen + b->n_planes + b->n_planes8) && (b->flags & TRI_FLAG_ACCUMULATED_SCORE)) // (DocumentsOnly: the one-pass kernel's tasks wrote their matches)
-                return fail(TRI_ERR_INVALID, "the batch holds queries that ran through the one-pass scored kernel: their docID sets are not materialised");
-        std::vector<uint64_t> h(n);
-        if (n) {
-                if (!b->d_hashes)
-                        HIP_TRY(hipMalloc((void **)&b->d_hashes, (size_t)n * 8));
-                DevLock g(dev->mu);
-                hipLaunchKernelGGL(k_hash_docsets, dim3((n + 63) / 64), dim3(64), 0, dev->stream_rb, b->dev_at(b->plan), b->dev_at(b->tasks), b->d_counts, n, b->d_out,
-                                   b->d_hashes);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipStreamSynchronize(dev->stream_rb));
-                HIP_TRY(hipMemcpy(h.data(), b->d_hashes, (size_t)n * 8, hipMemcpyDeviceToHost));
-        }
-        for (size_t q = 0; q < b->nq; ++q)
-                hashes[q] = b->slot_of_query[q] == UINT32_MAX ? 1469598103934665603ull : h[b->slot_of_query[q]];
-        return TRI_OK;
-}
-
-extern "C" int tri_batch_topk(tri_batch *b, uint32_t *docids, float *scores, uint32_t *counts) {
-        if (!b || !docids || !scores || !counts)
-                return fail(TRI_ERR_INVALID, "null argument");
-        if (!(b->flags & TRI_FLAG_ACCUMULATED_SCORE))
-                return fail(TRI_ERR_INVALID, "batch was not created with TRI_FLAG_ACCUMULATED_SCORE");
-        if (!b->synced)
-                return fail(TRI_ERR_INVALID, "tri_batch_sync first");
-        HIP_TRY(hipSetDevice(b->ix->dev->device));
-        HIP_TRY(hipMemcpy(docids, b->d_top_docs, b->nq * b->topk * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(scores, b->d_top_scores, b->nq * b->topk * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(counts, b->d_top_counts, b->nq * 4, hipMemcpyDeviceToHost));
-        return TRI_OK;
-}
-
-extern "C" int tri_batch_scores(tri_batch *b, size_t q, double *out, size_t cap, size_t *n) {
-        if (!b || !n || q >= b->nq)
-                return fail(TRI_ERR_INVALID, "bad argument");
-        if (!(b->flags & TRI_FLAG_ACCUMULATED_SCORE) || b->topk)
-                return fail(TRI_ERR_INVALID, "per-match scores are kept only for AccumulatedScoreScheme batches created with topk == 0");
-        if (!b->synced)
-                return fail(TRI_ERR_INVALID, "tri_batch_sync first");
-        const uint32_t slot = b->slot_of_query[q];
-        *n = slot == UINT32_MAX ? 0 : b->h_query_counts[slot];
-        if (!*n || !out)
-                return TRI_OK;
-        if (cap < *n)
-                return fail(TRI_ERR_INVALID, "scores need %zu slots, %zu given", *n, cap);
-        HIP_TRY(hipSetDevice(b->ix->dev->device));
-        const DevQuery &dq = b->plan[slot];
-        DevLock g(b->ix->dev->mu);
-        size_t w = 0;
-        for (uint32_t t = 0; t < dq.ntasks; ++t) {
-                const uint32_t c = b->h_counts[dq.first_task + t];
-                if (!c)
-                        continue;
-                HIP_TRY(hipMemcpyAsync(out + w, b->d_all_scores + b->tasks[dq.first_task + t].out_off, (size_t)c * 8, hipMemcpyDeviceToHost, b->ix->dev->stream_rb));
-                w += c;
-        }
-        HIP_TRY(hipStreamSynchronize(b->ix->dev->stream_rb));
-        return TRI_OK;
-}
-
-// (forms == nullptr: every set as ascending docIDs — tri_batch_docsets; else tri_batch_docsets_mixed: a RESULT_BITMAP query's region goes out as its words)
-static int docsets_deliver(tri_batch *b, uint32_t *out, size_t cap, uint64_t *offsets, uint32_t *forms, const char *fn) {
-        if (!b || !offsets)
-                return fail(TRI_ERR_INVALID, "%s: null argument", fn);
-        if (!b->synced)
-                return fail(TRI_ERR_INVALID, "tri_batch_sync first");
-        tri_dev *dev = b->ix->dev;
-        const size_t nslots = b->plan.size();
-        std::vector<uint64_t> slot_off(nslots + 1, 0);
-        uint64_t total = 0;
-        for (size_t q = 0; q < b->nq; ++q) {
-                const uint32_t slot = b->slot_of_query[q];
-                offsets[q] = total;
-                if (forms)
-                        forms[q] = RESULT_DOCIDS;
-                if (slot == UINT32_MAX)
-                        continue;
-                const DevQuery &dq = b->plan[slot];
-                if (dq.ntasks && !dq.out_cap && task_onepass(b->tasks[dq.first_task].kind) && b->h_query_counts[slot])
-                        return fail(TRI_ERR_INVALID, "query %zu ran through the one-pass scored kernel: an AccumulatedScore top-K batch keeps top-K lists and match counts, not docID sets", q);
-                slot_off[slot] = total;
-                if (forms && dq.form == RESULT_BITMAP) {
-                        forms[q] = RESULT_BITMAP;
-                        total += dq.out_cap; // (the region's words: one bit per document of the query's docID range, from document 0)
-                } else
-                        total += b->h_query_counts[slot];
-        }
-        offsets[b->nq] = total;
-        if (!out || !total)
-                return TRI_OK;
-        if (cap < total)
-                return fail(TRI_ERR_INVALID, "the docID sets need %llu slots, %zu given", (unsigned long long)total, cap);
-        HIP_TRY(hipSetDevice(dev->device));
-        uint32_t *d_flat = nullptr;
-        uint64_t *d_slot_off = nullptr;
-        hipError_t e;
-        {
-                // (the device lock covers the pool and the enqueues; the WAIT for the copy stands outside it: a thread that compiles the next batch, or runs
-                //  one, is not held up by the seconds a large delivery spends on PCIe — the read-back stream's work overlaps the engine stream's)
-                DevLock g(dev->mu);
-                HIP_TRY(pool_alloc(dev, (void **)&d_flat, (total + 64) * 4));
-                e = pool_alloc(dev, (void **)&d_slot_off, (nslots + 1) * 8 + POOL_MIN_BYTES);
-                if (e == hipSuccess)
-                        e = hipMemcpyAsync(d_slot_off, slot_off.data(), (nslots + 1) * 8, hipMemcpyHostToDevice, dev->stream_rb); // (pageable source: staged before the call returns)
-                if (e == hipSuccess) {
-                        hipLaunchKernelGGL(k_deliver_docsets, dim3((uint32_t)b->tasks.size()), dim3(256), 0, dev->stream_rb, (const DevQuery *)b->dev_at(b->plan), (const DevTask *)b->dev_at(b->tasks),
-                                           (const uint32_t *)b->d_counts, (const uint32_t *)b->d_out, (const uint64_t *)d_slot_off, d_flat, forms ? 1u : 0u);
-                        e = hipGetLastError();
-                }
-                if (e == hipSuccess)
-                        e = hipMemcpyAsync(out, d_flat, total * 4, hipMemcpyDeviceToHost, dev->stream_rb);
-        }
-        if (e == hipSuccess)
-                e = hipStreamSynchronize(dev->stream_rb);
-        pool_free(dev, d_flat);
-        pool_free(dev, d_slot_off);
-        HIP_TRY(e);
-        return TRI_OK;
-}
-
-// ---- every query's docID set in ONE call: what a caller that replays MatchedIndexDocumentsFilter::consider(const docid_t *, size_t) (matches.h:161-165)
-//      per query needs on the host.  out[offsets[q] .. offsets[q + 1]) = query q's ascending docIDs, queries in the caller's order; the sets are
-//      gathered on the device into one contiguous buffer (k_deliver_docsets: the tasks' segments in order, bitmap-form results expanded) and come
-//      over in a single copy — at a pinned `out` that is PCIe's rate, not a copy and a synchronisation per task segment
-extern "C" int tri_batch_docsets(tri_batch *b, uint32_t *out, size_t cap, uint64_t *offsets) { return docsets_deliver(b, out, cap, offsets, nullptr, "tri_batch_docsets"); }
-
-// ... and each set in the FORM THE ENGINE HOLDS IT: forms[q] = RESULT_DOCIDS: ascending docIDs as above; RESULT_BITMAP (a union / conjunction of head terms that matches one
-// document in 32 or more): out[offsets[q] .. offsets[q + 1]) = the words of a bitmap over the query's docID range — bit j of word i = document 32 i + j matches.  A dense set
-// crosses PCIe as a bit per document instead of four bytes per match (and is not expanded on the device first); the consumer expands it, or hands the bitmap on
-extern "C" int tri_batch_docsets_mixed(tri_batch *b, uint32_t *out, size_t cap, uint64_t *offsets, uint32_t *forms) {
-        if (!forms)
-                return fail(TRI_ERR_INVALID, "tri_batch_docsets_mixed: null forms");
-        return docsets_deliver(b, out, cap, offsets, forms, "tri_batch_docsets_mixed");
-}
-
-extern "C" int tri_batch_counts_device(tri_batch *b, void **counts) {
-        if (!b || !counts)
-                return fail(TRI_ERR_INVALID, "null argument");
-        *counts = b->d_qcounts;
-        return TRI_OK;
-}
-
-extern "C" int tri_batch_topk_device(tri_batch *b, void **docids, void **scores, void **counts) {
-        if (!b || !docids || !scores || !counts)
-                return fail(TRI_ERR_INVALID, "null argument");
-        if (!(b->flags & TRI_FLAG_ACCUMULATED_SCORE))
-                return fail(TRI_ERR_INVALID, "batch was not created with TRI_FLAG_ACCUMULATED_SCORE");
-        *docids = b->d_top_docs;
-        *scores = b->d_top_scores;
-        *counts = b->d_top_counts;
-        return TRI_OK;
-}
+// ------------------------------------------------------------------------------------------ read side
+// every result call of a batch and of a collection batch: one query view, one segment walk, one read-back rule
+#include "read_side.hpp"
 
 // ------------------------------------------------------------------------------------------ per-query document filters
 // IndexDocumentsFilter (matches.h:190-201; exec.cpp:1133-1150: tested where the masked documents are, before consider()) as a device bitmap per filter and a
@@ -2807,10 +2404,9 @@ extern "C" int tri_filter_from_docset(tri_batch *b, size_t q, int mode, tri_filt
         if (slot != UINT32_MAX && b->plan[slot].ntasks) { // (else: a query that can never match — the empty set)
                 const DevQuery &dq = b->plan[slot];
                 uint32_t most = 0; // the longest task segment: docIDs, or the words of its docID windows
-                for (uint32_t t = 0; t < dq.ntasks; ++t) {
-                        const DevTask &task = b->tasks[dq.first_task + t];
-                        most = std::max(most, dq.form == RESULT_BITMAP ? (task.tile_end - task.tile_begin) * SPAN_WORDS : b->h_counts[dq.first_task + t]);
-                }
+                for_each_segment(b, dq, [&](size_t, const uint32_t t, uint64_t, const uint32_t c) {
+                        most = std::max(most, dq.form == RESULT_BITMAP ? (b->tasks[t].tile_end - b->tasks[t].tile_begin) * SPAN_WORDS : c);
+                });
                 if (dq.ntasks > 65535u) // (gridDim.y; a query is cut into a few hundred tasks at the most)
                         return fail(TRI_ERR_UNSUPPORTED, "tri_filter_from_docset: query %zu has more than 65535 tasks", q);
                 if (most) {
@@ -2892,27 +2488,6 @@ extern "C" int tri_batch_set_filters(tri_batch *b, tri_filter *const *filters, s
 // newer ones update (tri_index_set_masked), and the application's filter sees the matches of all of them (exec_query per source,
 // exec.h:57-62).  A tri_cbatch borrows one tri_batch per source — the same queries, term indices resolved per source — runs them back
 // to back on the engine stream and merges on the device: match counts add up, top-K lists merge K-way from the parts' partial lists.
-struct tri_cbatch {
-        std::vector<tri_batch *> parts;
-        std::vector<uint32_t *> d_slots; // per part: caller query -> plan slot
-        DevSource *d_src = nullptr;
-        uint32_t *d_top_docs = nullptr, *d_top_counts = nullptr;
-        float *d_top_scores = nullptr;
-        uint64_t *d_counts = nullptr;
-        bool ran = false, synced = false;
-        ~tri_cbatch() {
-                if (!parts.empty())
-                        hipSetDevice(parts[0]->ix->dev->device);
-                for (auto p : d_slots)
-                        hipFree(p);
-                hipFree(d_src);
-                hipFree(d_top_docs);
-                hipFree(d_top_counts);
-                hipFree(d_top_scores);
-                hipFree(d_counts);
-        }
-};
-
 extern "C" int tri_cbatch_create(tri_batch *const *parts, size_t n, tri_cbatch **out) {
         if (!parts || !n || !out)
                 return fail(TRI_ERR_INVALID, "tri_cbatch_create: null argument");
@@ -2994,60 +2569,6 @@ extern "C" int tri_cbatch_sync(tri_cbatch *c) {
                         return rc;
         HIP_TRY(hipStreamSynchronize(c->parts[0]->ix->dev->stream));
         c->synced = true;
-        return TRI_OK;
-}
-
-extern "C" int tri_cbatch_match_counts(tri_cbatch *c, uint64_t *counts) {
-        if (!c || !counts)
-                return fail(TRI_ERR_INVALID, "null argument");
-        if (!c->synced)
-                return fail(TRI_ERR_INVALID, "tri_cbatch_sync first");
-        HIP_TRY(hipSetDevice(c->parts[0]->ix->dev->device));
-        HIP_TRY(hipMemcpy(counts, c->d_counts, c->parts[0]->nq * 8, hipMemcpyDeviceToHost));
-        return TRI_OK;
-}
-
-extern "C" int tri_cbatch_topk(tri_cbatch *c, uint32_t *docids, float *scores, uint32_t *counts) {
-        if (!c || !docids || !scores || !counts)
-                return fail(TRI_ERR_INVALID, "null argument");
-        if (!c->d_top_docs)
-                return fail(TRI_ERR_INVALID, "the parts were not created with TRI_FLAG_ACCUMULATED_SCORE and topk >= 1");
-        if (!c->synced)
-                return fail(TRI_ERR_INVALID, "tri_cbatch_sync first");
-        const size_t nq = c->parts[0]->nq, k = c->parts[0]->topk;
-        HIP_TRY(hipSetDevice(c->parts[0]->ix->dev->device));
-        HIP_TRY(hipMemcpy(docids, c->d_top_docs, nq * k * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(scores, c->d_top_scores, nq * k * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(counts, c->d_top_counts, nq * 4, hipMemcpyDeviceToHost));
-        return TRI_OK;
-}
-
-// the docID set of query q over the collection: the sources' sets one after the other (each ascending; the sources are disjoint where
-// the newer ones mask the older) — the order exec_query delivers them in when it is called source after source
-extern "C" int tri_cbatch_docset(tri_cbatch *c, size_t q, uint32_t *out, size_t cap, size_t *n) {
-        if (!c || !n)
-                return fail(TRI_ERR_INVALID, "null argument");
-        if (!c->synced)
-                return fail(TRI_ERR_INVALID, "tri_cbatch_sync first");
-        size_t total = 0;
-        for (tri_batch *p : c->parts) {
-                size_t m = 0;
-                if (int rc = tri_batch_docset(p, q, nullptr, 0, &m))
-                        return rc;
-                total += m;
-        }
-        *n = total;
-        if (!out)
-                return TRI_OK;
-        if (cap < total)
-                return fail(TRI_ERR_INVALID, "docset needs %zu slots, %zu given", total, cap);
-        size_t w = 0;
-        for (tri_batch *p : c->parts) {
-                size_t m = 0;
-                if (int rc = tri_batch_docset(p, q, out + w, cap - w, &m))
-                        return rc;
-                w += m;
-        }
         return TRI_OK;
 }
 
