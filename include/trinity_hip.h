@@ -34,7 +34,8 @@ extern "C" {
                                 within 9: options tree_max_nodes / tree_wide_min_nodes (query trees of up to 1024 nodes; no new export, no struct grew);
                                 within 9: option rich_max_terms, tri_batch_query_terms_wide / tri_batch_matched_terms_wide (the default mode reports up to 64 matched terms per query; no struct grew);
                                 within 9: tri_decode_hits / tri_decode_hits_at (the codec seam's materialize_hits: the hits of whole lists and of chosen documents; no struct grew);
-                                within 9: tri_batch_set_ranker / tri_batch_ranked (the default mode ranks its matches on the device: a proximity score, top-K per query; no struct grew) */
+                                within 9: tri_batch_set_ranker / tri_batch_ranked (the default mode ranks its matches on the device: a proximity score, top-K per query; no struct grew),
+                                tri_cbatch_ranked / tri_cbatch_matched_terms[_wide] / tri_cbatch_matched_payloads (the default mode over a collection) */
 
 /* status codes */
 #define TRI_OK 0
@@ -419,7 +420,7 @@ int tri_batch_matched_payloads(tri_batch *, size_t q, uint8_t *lens, uint64_t *p
  * query the planner left out (tri_batch_query_status) has count 0.  TRI_ERR_INVALID when no ranker is set or the batch has not been synced since it was.
  * tri_batch_matched_terms*, tri_batch_docset and the rest keep working on a ranked batch; a caller that wants only the ranking does not call them, and then
  * nothing but the top-K block is copied.  (tri_dev_get_option "rich_write_last_us" / "rank_last_us", read-only: the device time of the last ranked batch's
- * WRITE pass and rank pass.)  Not ranked: the collections of tri_cbatch_*, tri_gather_results. */
+ * WRITE pass and rank pass.)  A collection's parts merge their ranked lists on the device: tri_cbatch_ranked.  Not ranked: tri_gather_results. */
 #define TRI_RANK_PROXIMITY 1u
 typedef struct tri_ranker {
         uint32_t kind;     /* TRI_RANK_PROXIMITY */
@@ -446,7 +447,23 @@ int tri_batch_docset_hashes(tri_batch *, uint64_t *hashes /* [nq] */);
  * term table; per-token weights when the scores of the sources must share their statistics), same flags and topk, all on one device,
  * oldest source first, each index carrying its masked set (tri_index_set_masked).  The collection batch borrows them: run = the parts
  * back to back on the engine stream + a device merge — match counts add up, top-K lists merge K-way from the parts' partial lists
- * (score descending, docID ascending, as one application heap would hold them); docID sets concatenate source after source. */
+ * (score descending, docID ascending, as one application heap would hold them); docID sets concatenate source after source.
+ *
+ * The default mode (TRI_FLAG_MATCHED_TERMS parts) over a collection.  tri_cbatch_ranked: after tri_cbatch_sync, blocks laid out as tri_batch_ranked's — query q's
+ * list is the best topk (docID, score) pairs over all parts, counts[q] = min(sum of the parts' ranked counts, topk), rows past counts[q] zero on every run.
+ * Order: score descending, then docID ascending, then source index ascending — a STABLE sort by (-score, docID) of the parts' lists concatenated source after
+ * source: where no masks are installed and two sources hold the same docID at the same score, both entries stay, the older source's first (both matches reach
+ * consider() in the reference).  A merged score is bit for bit one part's score.  The collection "is ranked" for a run when at that tri_cbatch_run every part
+ * carried a ranker (tri_batch_set_ranker) and all the parts' tri_ranker structs are bytewise equal; the weights are each part's own.  Otherwise run and sync
+ * behave as they always did — nothing more is refused, allocated or launched — and tri_cbatch_ranked answers TRI_ERR_INVALID, names the reason ("no ranker on
+ * part i", "part i's ranker differs from part 0's in <field>") and writes nothing; so it does before a sync and on a NULL argument.  (tri_dev_get_option
+ * "crank_merge_last_us", read-only: the device time of the last ranked collection's merge kernel.)  A query the planner left
+ * out of a part contributes nothing from that part, as with tri_cbatch_topk (tri_cbatch_query_status tells).
+ * tri_cbatch_matched_terms[_wide] / tri_cbatch_matched_payloads: the rows of query q parallel to tri_cbatch_docset — each part's rows source after source, with
+ * the conventions of the tri_batch_* calls (the sizing call with NULLs, dense [n * nterms] frequencies, positions match-major then term-minor) and their
+ * refusals (a narrow call on a query of more than 16 terms, the wrong mode, a too-small cap).  Column k must mean the same slot in every part: when the parts
+ * that report the query disagree in tri_batch_query_terms_wide's nterms (two of its terms unknown to one source and resolved to the same id), the call answers
+ * TRI_ERR_INVALID, names both counts and writes nothing — the caller reads that query part by part. */
 typedef struct tri_cbatch tri_cbatch;
 int tri_cbatch_create(tri_batch *const *parts, size_t n, tri_cbatch **out);
 void tri_cbatch_destroy(tri_cbatch *);
@@ -458,6 +475,10 @@ int tri_cbatch_sync(tri_cbatch *);
 int tri_cbatch_match_counts(tri_cbatch *, uint64_t *counts /* [nq] */);
 int tri_cbatch_topk(tri_cbatch *, uint32_t *docids, float *scores, uint32_t *counts);
 int tri_cbatch_docset(tri_cbatch *, size_t q, uint32_t *out, size_t cap, size_t *n);
+int tri_cbatch_ranked(tri_cbatch *, uint32_t *docids /* [nq][topk] */, double *scores /* [nq][topk] */, uint32_t *counts /* [nq] */);
+int tri_cbatch_matched_terms(tri_cbatch *, size_t q, uint32_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos);
+int tri_cbatch_matched_terms_wide(tri_cbatch *, size_t q, uint64_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos);
+int tri_cbatch_matched_payloads(tri_cbatch *, size_t q, uint8_t *lens, uint64_t *payloads, size_t cap, size_t *n);
 
 /* ---- multi-GPU result gather (RCCL over xGMI) -------------------------------------------------------
  * exec_query_par gives every source / shard its own result object and the caller combines them (exec.h:132-176).  One process per GPU,

@@ -136,9 +136,24 @@ def build_mirror_rank_test(force=False):
     return MIRROR_RANK_BIN
 
 
+MIRROR_COLLECTION_SRC = os.path.join(ROOT, "tests", "cpp", "host_mirror_collection_test.cpp")
+MIRROR_COLLECTION_BIN = os.path.join(ROOT, "tests", "cpp", "host_mirror_collection_test")
+
+
+def build_mirror_collection_test(force=False):
+    """IndexSourcesCollection, exec_query's collection form and ProximityRanker::blend (csrc/host/trinity_gpu.hpp) compiled into their driver; in-tree, so that it
+    travels to the GPU box, where tests/test_host_mirror_collection.py runs it."""
+    deps = [MIRROR_COLLECTION_SRC, os.path.join(PKG, "csrc", "host", "trinity_gpu.hpp"), os.path.join(PKG, "csrc", "host", "google_encoder.hpp"), os.path.join(ROOT, "include", "trinity_hip.h")]
+    if force or _newer(MIRROR_COLLECTION_BIN, deps):
+        build_hip()
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", MIRROR_COLLECTION_BIN, MIRROR_COLLECTION_SRC, "-L" + PKG, "-ltrinity_hip", "-Wl,-rpath,$ORIGIN/../../trinity_amd"]
+        subprocess.run(cmd, check=True)
+    return MIRROR_COLLECTION_BIN
+
+
 def build_all(force=False):
     return (build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force), build_mirror_wide_terms_test(force),
-            build_mirror_hits_test(force), build_mirror_rank_test(force))
+            build_mirror_hits_test(force), build_mirror_rank_test(force), build_mirror_collection_test(force))
 
 
 def kernels_stamp():

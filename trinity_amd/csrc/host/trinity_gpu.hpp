@@ -516,6 +516,20 @@ namespace trinity_amd {
                         std::sort(out.begin(), out.end(), better);
                         return out;
                 }
+                // The lists of a collection's sources (exec_query's collection form, oldest source first) blended into one: the best K under score descending, docID
+                // ascending, source ascending — a stable sort of the lists one after the other, so where two sources hold the same docID at the same score (no
+                // masks installed) both entries stay, the older source's first.  The host form of tri_cbatch_ranked's device merge (k_rank_merge_sources).
+                static std::vector<std::pair<docid_t, double>> blend(const std::vector<std::unique_ptr<ProximityRanker>> &parts, const size_t K) {
+                        std::vector<std::pair<docid_t, double>> out;
+                        for (const auto &p : parts) {
+                                const auto l = p->ranked();
+                                out.insert(out.end(), l.begin(), l.end());
+                        }
+                        std::stable_sort(out.begin(), out.end(), better);
+                        if (out.size() > K)
+                                out.resize(K);
+                        return out;
+                }
         };
 
         struct IndexDocumentsFilter { // matches.h:198-201: return true to disregard the document
@@ -1069,6 +1083,48 @@ namespace trinity_amd {
                 } catch (const aborted_search_exception &) {
                         // search was aborted by the application's filter
                 }
+        }
+
+        // index_source.cpp:3-30 IndexSourcesCollection: the sources of an index, oldest first, each with the documents it updates or deletes in the older ones.
+        // scanner_registry_for(i) is the registry exec_query runs source i under: the union of the lists of the sources newer than i.  (The reference's commit()
+        // collects the lists from the sources; here the caller hands each list over with its source.  The sources are borrowed.)
+        class IndexSourcesCollection final {
+                std::vector<updated_documents> all; // per source, in the order of sources[]
+
+              public:
+                std::vector<IndexSource *> sources;
+
+                void insert(IndexSource *is, updated_documents updates = {}) {
+                        std::sort(updates.ids.begin(), updates.ids.end());
+                        sources.push_back(is);
+                        all.push_back(std::move(updates));
+                }
+                std::unique_ptr<masked_documents_registry> scanner_registry_for(const std::size_t idx) const {
+                        if (idx >= all.size())
+                                throw invalid_argument("IndexSourcesCollection::scanner_registry_for: no such source");
+                        return masked_documents_registry::make(all.data() + idx + 1, all.size() - idx - 1);
+                }
+        };
+
+        // exec.h:63-81: the query over every source of the collection in sequence, each under its registry, one T per source — "you are expected to
+        // merge/reduce/blend them" (ProximityRanker::blend).  roots: the query lowered against each source (roots[i] from sources[i]'s own iterators: term
+        // ids are per source).  Every IndexSource holds its own device handle, so the sources' batches are independent, as the reference's executions are.
+        template <typename T, typename... Arg>
+        std::vector<std::unique_ptr<T>> exec_query(const std::vector<DocsSetIterators::Iterator *> &roots, IndexSourcesCollection *collection, IndexDocumentsFilter *f, const uint32_t flags,
+                                                   const Arg &... args) {
+                static_assert(std::is_base_of<MatchedIndexDocumentsFilter, T>::value, "expected a MatchedIndexDocumentsFilter subclass");
+                validate_flags(flags);
+                const std::size_t n = collection->sources.size();
+                if (roots.size() != n)
+                        throw invalid_argument("exec_query: one lowered query per source of the collection");
+                std::vector<std::unique_ptr<T>> out;
+                for (std::size_t i = 0; i < n; ++i) {
+                        const auto scanner = collection->scanner_registry_for(i);
+                        auto filter = std::make_unique<T>(args...);
+                        exec_query(roots[i], collection->sources[i], scanner.get(), filter.get(), f, flags);
+                        out.push_back(std::move(filter));
+                }
+                return out;
         }
 
         // The batched sibling of exec_query_par (exec.h:87-177): all queries in ONE engine batch; DocumentsOnly results

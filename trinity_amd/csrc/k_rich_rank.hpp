@@ -254,3 +254,73 @@ __global__ __launch_bounds__(AND_WG) void k_rank_merge(const DevQuery *__restric
                 __syncthreads();
         }
 }
+
+// tri_cbatch_ranked: the ranked lists of a collection's parts merged per query.  Each part's [nq][k] list is sorted already (k_rank_merge: score descending,
+// docID ascending), and a query holds at most nsrc * 256 entries: they are not pushed through the LDS top-K again — every entry's final rank is COUNTED.
+// One lane per entry (q, s, i).  A live entry (i < count_s[q]) stands at rank i + sum over the other sources j of #{ live entries of j that precede it }, where
+// "precede" is (score descending, docID ascending, source ascending): the stable sort by (-score, docID) of the parts' lists concatenated source after source
+// — the older source first where two sources hold the same docID at the same score (a collection without masks).  Those that precede form a prefix of j's
+// list, so the count is one lower-bound search — taken in a fixed number of steps (the bits of k's highest power of two: wave-uniform, no lane waits for
+// another's longer search).  rank < k: the pair is stored at out[q][rank].  The ranks of a query's live entries are a permutation of 0 .. sum(count) - 1, and
+// the lanes of source 0 zero the positions from min(sum(count), k) on: every output word is written exactly once a run — no LDS, no barrier, no atomics.
+// Scores are compared as doubles with > and ==: -0.0 and 0.0 tie and the docID decides; the score stored is the part's own 64 bits.
+struct DevRankSource {
+        const uint32_t *docs;   // [nq][k]
+        const double *scores;   // [nq][k]
+        const uint32_t *counts; // [nq]
+};
+
+__global__ __launch_bounds__(AND_WG) void k_rank_merge_sources(const DevRankSource *__restrict__ src, const uint32_t nsrc, const uint32_t nq, const uint32_t k,
+                                                               uint32_t *__restrict__ top_docs, double *__restrict__ top_scores, uint32_t *__restrict__ top_counts) {
+        const uint64_t e = (uint64_t)blockIdx.x * AND_WG + threadIdx.x;
+        const uint64_t per_q = (uint64_t)nsrc * k;
+        if (e >= per_q * nq)
+                return;
+        const uint32_t q = (uint32_t)(e / per_q);
+        const uint32_t r = (uint32_t)(e - (uint64_t)q * per_q);
+        const uint32_t s = r / k, i = r - s * k;
+        const uint64_t row = (uint64_t)q * k;
+        uint32_t total = 0, mine = 0;
+        for (uint32_t j = 0; j < nsrc; ++j) {
+                const uint32_t c = min(src[j].counts[q], k);
+                total += c;
+                mine = j == s ? c : mine;
+        }
+        const uint32_t n = min(total, k);
+        if (s == 0) {
+                if (i >= n) {
+                        top_docs[row + i] = 0u;
+                        top_scores[row + i] = 0.0;
+                }
+                if (i == 0)
+                        top_counts[q] = n;
+        }
+        if (i >= mine)
+                return;
+        const double sc = src[s].scores[row + i];
+        const uint32_t doc = src[s].docs[row + i];
+        const uint32_t top_step = 1u << (31 - __builtin_clz(k)); // (2 * top_step - 1 >= k: the steps reach every count up to k)
+        uint32_t rank = i;
+        for (uint32_t j = 0; j < nsrc; ++j) {
+                if (j == s)
+                        continue;
+                const uint32_t c = min(src[j].counts[q], k);
+                const double *js = src[j].scores + row;
+                const uint32_t *jd = src[j].docs + row;
+                uint32_t lo = 0; // entries of j known to precede
+                for (uint32_t step = top_step; step; step >>= 1) {
+                        const uint32_t at = lo + step;
+                        if (at <= c) {
+                                const double x = js[at - 1];
+                                const uint32_t d = jd[at - 1];
+                                if (x > sc || (x == sc && (d < doc || (d == doc && j < s))))
+                                        lo = at;
+                        }
+                }
+                rank += lo;
+        }
+        if (rank < k) {
+                top_docs[row + rank] = doc;
+                top_scores[row + rank] = sc;
+        }
+}

@@ -207,6 +207,59 @@ namespace {
                         return fail(TRI_ERR_INVALID, "%s: tri_cbatch_sync first", fn);
                 return TRI_OK;
         }
+
+        // the default mode's rows over a collection: column k must mean the same slot in every part that reports the query at all (a part that left it out, or
+        // to which all of its terms are unknown, reports no terms and holds no row)
+        int cbatch_query_width(tri_cbatch *c, const size_t q, const char *fn, uint32_t &nterms) {
+                uint32_t terms[RICH_WIDE_TERMS];
+                nterms = 0;
+                for (size_t i = 0; i < c->parts.size(); ++i) {
+                        uint32_t nt = 0;
+                        if (const int rc = tri_batch_query_terms_wide(c->parts[i], q, terms, &nt))
+                                return rc;
+                        if (nt && nterms && nt != nterms)
+                                return fail(TRI_ERR_INVALID, "%s: query %zu reports %u terms in part %zu and %u in an older part (terms unknown to a source that resolve to one id?): read it part by part", fn,
+                                            q, nt, i, nterms);
+                        if (nt)
+                                nterms = nt;
+                }
+                return TRI_OK;
+        }
+
+        // tri_cbatch_matched_terms[_wide]: the parts' own calls source after source — a sizing pass first (it also takes every refusal before anything is written)
+        int cbatch_matched_terms(tri_cbatch *c, const size_t q, uint32_t *present, uint64_t *present64, uint16_t *freq, uint16_t *positions, const size_t pos_cap, size_t *npos,
+                                 const bool wide_call, const char *fn) {
+                if (const int rc = cbatch_check(c, npos != nullptr, fn))
+                        return rc;
+                auto part_call = [&](tri_batch *p, uint32_t *pr, uint64_t *pr64, uint16_t *f, uint16_t *pos, const size_t cap, size_t *np) {
+                        return wide_call ? tri_batch_matched_terms_wide(p, q, pr64, f, pos, cap, np) : tri_batch_matched_terms(p, q, pr, f, pos, cap, np);
+                };
+                size_t total = 0;
+                for (tri_batch *p : c->parts) {
+                        size_t np = 0;
+                        if (const int rc = part_call(p, nullptr, nullptr, nullptr, nullptr, 0, &np))
+                                return rc;
+                        total += np;
+                }
+                uint32_t nterms = 0;
+                if (const int rc = cbatch_query_width(c, q, fn, nterms))
+                        return rc;
+                *npos = total;
+                if (positions && pos_cap < total)
+                        return fail(TRI_ERR_INVALID, "%s: positions need %zu slots, %zu given", fn, total, pos_cap);
+                size_t m = 0, w = 0;
+                for (tri_batch *p : c->parts) {
+                        size_t n = 0, np = 0;
+                        if (const int rc = tri_batch_docset(p, q, nullptr, 0, &n))
+                                return rc;
+                        if (const int rc = part_call(p, present ? present + m : nullptr, present64 ? present64 + m : nullptr, freq ? freq + m * nterms : nullptr,
+                                                     positions ? positions + w : nullptr, total - w, &np))
+                                return rc;
+                        m += n;
+                        w += np;
+                }
+                return TRI_OK;
+        }
 } // namespace
 
 extern "C" int tri_batch_query_terms(tri_batch *b, size_t q, uint32_t *terms, uint32_t *nterms) { return query_terms(b, q, terms, nterms, RICH_NARROW_TERMS, __func__); }
@@ -423,6 +476,49 @@ extern "C" int tri_cbatch_docset(tri_cbatch *c, size_t q, uint32_t *out, size_t 
         for (tri_batch *p : c->parts) {
                 size_t m = 0;
                 if (int rc = tri_batch_docset(p, q, out + w, cap - w, &m))
+                        return rc;
+                w += m;
+        }
+        return TRI_OK;
+}
+
+// a collection's ranked list (k_rank_merge_sources, queued by tri_cbatch_sync): the best topk (docID, score) pairs of every query over all parts
+extern "C" int tri_cbatch_ranked(tri_cbatch *c, uint32_t *docids, double *scores, uint32_t *counts) {
+        if (const int rc = cbatch_check(c, docids && scores && counts, __func__))
+                return rc;
+        if (!c->ranked)
+                return fail(TRI_ERR_INVALID, "%s: the collection is not ranked: %s", __func__, c->rank_why.c_str());
+        const size_t nq = c->parts[0]->nq, k = c->rank_k;
+        return ReadBack(c->parts[0]->dev).copy(docids, c->d_rank_docs, nq * k * 4).copy(scores, c->d_rank_scores, nq * k * 8).copy(counts, c->d_rank_counts, nq * 4).done();
+}
+
+// the default mode's rows of query q over the collection, parallel to tri_cbatch_docset: each part's rows source after source (host walks over the parts' calls)
+extern "C" int tri_cbatch_matched_terms(tri_cbatch *c, size_t q, uint32_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos) {
+        return cbatch_matched_terms(c, q, present, nullptr, freq, positions, pos_cap, npos, false, __func__);
+}
+extern "C" int tri_cbatch_matched_terms_wide(tri_cbatch *c, size_t q, uint64_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos) {
+        return cbatch_matched_terms(c, q, nullptr, present, freq, positions, pos_cap, npos, true, __func__);
+}
+
+extern "C" int tri_cbatch_matched_payloads(tri_cbatch *c, size_t q, uint8_t *lens, uint64_t *payloads, size_t cap, size_t *n) {
+        if (const int rc = cbatch_check(c, n != nullptr, __func__))
+                return rc;
+        size_t total = 0;
+        for (tri_batch *p : c->parts) {
+                size_t m = 0;
+                if (const int rc = tri_batch_matched_payloads(p, q, nullptr, nullptr, 0, &m))
+                        return rc;
+                total += m;
+        }
+        *n = total;
+        if (!lens && !payloads)
+                return TRI_OK;
+        if (cap < total)
+                return fail(TRI_ERR_INVALID, "%s: payloads need %zu slots, %zu given", __func__, total, cap);
+        size_t w = 0;
+        for (tri_batch *p : c->parts) {
+                size_t m = 0;
+                if (const int rc = tri_batch_matched_payloads(p, q, lens ? lens + w : nullptr, payloads ? payloads + w : nullptr, total - w, &m))
                         return rc;
                 w += m;
         }

@@ -74,6 +74,7 @@ struct tri_dev {
         int cus;
         tri_options opt;
         uint64_t rich_write_last_us = 0, rank_last_us = 0; // the last ranked batch's WRITE pass and rank pass (tri_dev_get_option, read-only)
+        uint64_t crank_merge_last_us = 0;                  // the last ranked collection's merge of its parts' lists (k_rank_merge_sources)
         int refs = 0;         // indexes and batches alive on this handle ...
         bool closing = false; // ... tri_dev_close with some left: the handle goes with the last of them
         // The large buffers of a batch (output regions, score streams, term planes, decoded lists) and its plan arena are recycled from
@@ -622,6 +623,10 @@ extern "C" int tri_dev_get_option(tri_dev *d, const char *name, uint64_t *value)
         // (read-only: the device time of the last ranked batch's WRITE pass and rank pass — HIP events around them, tri_batch_sync)
         if (!strcmp(name, "rich_write_last_us") || !strcmp(name, "rank_last_us")) {
                 *value = !strcmp(name, "rich_write_last_us") ? d->rich_write_last_us : d->rank_last_us;
+                return TRI_OK;
+        }
+        if (!strcmp(name, "crank_merge_last_us")) { // (... and of the last ranked collection's merge kernel, tri_cbatch_sync)
+                *value = d->crank_merge_last_us;
                 return TRI_OK;
         }
         const uint64_t *slot = option_slot(d->opt, name);
@@ -2298,6 +2303,17 @@ struct tri_cbatch {
         uint32_t *d_top_docs = nullptr, *d_top_counts = nullptr;
         float *d_top_scores = nullptr;
         uint64_t *d_counts = nullptr;
+        // tri_cbatch_ranked (k_rank_merge_sources): the merged [nq][rank_k] blocks and the parts' {docs, scores, counts} table — allocated by the first run that finds
+        // the collection ranked (every part carries a ranker, all tri_ranker structs bytewise equal), re-sized when topk changed; rank_why: why a run was not ranked
+        bool ranked = false;
+        uint32_t rank_k = 0;
+        uint32_t *d_rank_docs = nullptr, *d_rank_counts = nullptr;
+        double *d_rank_scores = nullptr;
+        DevRankSource *d_rank_src = nullptr;
+        std::vector<DevRankSource> rank_src;
+        std::string rank_why;
+        hipEvent_t rank_ev[2] = {}; // around the merge kernel (option crank_merge_last_us)
+        bool rank_timed = false;
         bool ran = false, synced = false;
         ~tri_cbatch() {
                 if (!parts.empty())
@@ -2309,6 +2325,13 @@ struct tri_cbatch {
                 hipFree(d_top_counts);
                 hipFree(d_top_scores);
                 hipFree(d_counts);
+                hipFree(d_rank_docs);
+                hipFree(d_rank_scores);
+                hipFree(d_rank_counts);
+                hipFree(d_rank_src);
+                for (hipEvent_t e : rank_ev)
+                        if (e)
+                                hipEventDestroy(e);
         }
 };
 
@@ -2542,6 +2565,91 @@ extern "C" int tri_cbatch_query_status(const tri_cbatch *c, int32_t *status) {
         return TRI_OK;
 }
 
+// tri_cbatch_ranked, at tri_cbatch_run: is the collection ranked for this run?  Every part carries a ranker and the tri_ranker structs are bytewise equal (the
+// weights are each part's own).  If so the merged blocks exist at the rankers' topk and the parts' table — a part's ranker block moves when its ranker is
+// replaced — goes to the device on the engine stream, ahead of the merge tri_cbatch_sync queues.  If not, nothing is allocated, copied or launched.
+static int cbatch_rank_prepare(tri_cbatch *c) {
+        c->ranked = false;
+        const tri_batch *p0 = c->parts[0];
+        char why[160];
+        for (size_t i = 0; i < c->parts.size(); ++i) {
+                const tri_batch *p = c->parts[i];
+                const char *field = nullptr;
+                if (!p->rank_on) {
+                        snprintf(why, sizeof why, "no ranker on part %zu (tri_batch_set_ranker)", i);
+                        c->rank_why = why;
+                        return TRI_OK;
+                }
+                if (p->rank.kind != p0->rank.kind)
+                        field = "kind";
+                else if (p->rank.topk != p0->rank.topk)
+                        field = "topk";
+                else if (p->rank.freq_cap != p0->rank.freq_cap)
+                        field = "freq_cap";
+                else if (p->rank.reserved != p0->rank.reserved)
+                        field = "reserved";
+                else if (memcmp(&p->rank.adjacency, &p0->rank.adjacency, sizeof(double)))
+                        field = "adjacency";
+                if (field) {
+                        snprintf(why, sizeof why, "part %zu's ranker differs from part 0's in %s", i, field);
+                        c->rank_why = why;
+                        return TRI_OK;
+                }
+        }
+        tri_dev *dev = p0->ix->dev;
+        const size_t nq = p0->nq, n = c->parts.size(), k = p0->rank.topk;
+        DevLock dev_lock(dev->mu);
+        HIP_TRY(hipSetDevice(dev->device));
+        if (c->rank_k != k) { // (no merge of an earlier run is in flight: tri_cbatch_sync waits for the one it queues)
+                hipFree(c->d_rank_docs);
+                hipFree(c->d_rank_scores);
+                hipFree(c->d_rank_counts);
+                c->d_rank_docs = c->d_rank_counts = nullptr, c->d_rank_scores = nullptr, c->rank_k = 0;
+                HIP_TRY(hipMalloc((void **)&c->d_rank_docs, (nq * k + 1) * 4));
+                HIP_TRY(hipMalloc((void **)&c->d_rank_scores, (nq * k + 1) * 8));
+                HIP_TRY(hipMalloc((void **)&c->d_rank_counts, (nq + 1) * 4));
+                c->rank_k = (uint32_t)k;
+        }
+        if (!c->d_rank_src)
+                HIP_TRY(hipMalloc((void **)&c->d_rank_src, n * sizeof(DevRankSource)));
+        c->rank_src.resize(n);
+        for (size_t i = 0; i < n; ++i)
+                c->rank_src[i] = {c->parts[i]->d_rank_docs, c->parts[i]->d_rank_scores, c->parts[i]->d_rank_counts};
+        HIP_TRY(hipMemcpyAsync(c->d_rank_src, c->rank_src.data(), n * sizeof(DevRankSource), hipMemcpyHostToDevice, dev->stream));
+        c->ranked = true;
+        return TRI_OK;
+}
+
+// ... and at tri_cbatch_sync, behind the last part's own sync: one lane per (query, source, rank) entry
+static int cbatch_rank_merge(tri_cbatch *c) {
+        if (!c->ranked)
+                return TRI_OK;
+        for (size_t i = 0; i < c->parts.size(); ++i) { // (a ranker replaced or removed between the run and the sync: the part ranked nothing under the table's block)
+                const tri_batch *p = c->parts[i];
+                if (!p->rank_on || p->d_rank_docs != c->rank_src[i].docs || (!p->rank_done && !p->tasks.empty())) {
+                        c->ranked = false;
+                        c->rank_why = "part " + std::to_string(i) + "'s ranker was replaced after tri_cbatch_run";
+                        return TRI_OK;
+                }
+        }
+        tri_dev *dev = c->parts[0]->ix->dev;
+        const uint64_t lanes = (uint64_t)c->parts[0]->nq * c->parts.size() * c->rank_k;
+        if (!lanes)
+                return TRI_OK;
+        DevLock dev_lock(dev->mu);
+        HIP_TRY(hipSetDevice(dev->device));
+        for (hipEvent_t &e : c->rank_ev)
+                if (!e)
+                        HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(c->rank_ev[0], dev->stream));
+        hipLaunchKernelGGL(k_rank_merge_sources, dim3((uint32_t)((lanes + AND_WG - 1) / AND_WG)), dim3(AND_WG), 0, dev->stream, (const DevRankSource *)c->d_rank_src,
+                           (uint32_t)c->parts.size(), (uint32_t)c->parts[0]->nq, c->rank_k, c->d_rank_docs, c->d_rank_scores, c->d_rank_counts);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(c->rank_ev[1], dev->stream));
+        c->rank_timed = true;
+        return TRI_OK;
+}
+
 extern "C" int tri_cbatch_run(tri_cbatch *c) {
         if (!c)
                 return fail(TRI_ERR_INVALID, "null collection batch");
@@ -2558,7 +2666,7 @@ extern "C" int tri_cbatch_run(tri_cbatch *c) {
         }
         c->ran = true;
         c->synced = false;
-        return TRI_OK;
+        return cbatch_rank_prepare(c);
 }
 
 extern "C" int tri_cbatch_sync(tri_cbatch *c) {
@@ -2567,7 +2675,15 @@ extern "C" int tri_cbatch_sync(tri_cbatch *c) {
         for (tri_batch *p : c->parts)
                 if (int rc = tri_batch_sync(p))
                         return rc;
+        if (int rc = cbatch_rank_merge(c)) // (a part's list stands once its own sync has run the WRITE and rank passes: behind the last of them)
+                return rc;
         HIP_TRY(hipStreamSynchronize(c->parts[0]->ix->dev->stream));
+        if (c->rank_timed) {
+                float ms = 0;
+                HIP_TRY(hipEventElapsedTime(&ms, c->rank_ev[0], c->rank_ev[1]));
+                c->parts[0]->ix->dev->crank_merge_last_us = (uint64_t)(ms * 1000.0f);
+                c->rank_timed = false;
+        }
         c->synced = true;
         return TRI_OK;
 }

@@ -114,7 +114,7 @@ ABI_SYMBOLS = [
     "tri_index_upload", "tri_index_destroy", "tri_index_get_info", "tri_index_term_docbytes", "tri_index_set_masked", "tri_decode_terms", "tri_decode_hits", "tri_decode_hits_at",
     "tri_batch_create", "tri_batch_query_status", "tri_batch_destroy", "tri_batch_run", "tri_batch_sync", "tri_batch_get_info",
     "tri_batch_match_counts", "tri_batch_docset", "tri_batch_docset_bitmap", "tri_batch_docsets", "tri_batch_docsets_mixed", "tri_batch_scores", "tri_batch_query_terms", "tri_batch_matched_terms", "tri_batch_query_terms_wide", "tri_batch_matched_terms_wide", "tri_batch_matched_payloads", "tri_batch_set_ranker", "tri_batch_ranked", "tri_batch_topk", "tri_batch_topk_device", "tri_batch_counts_device", "tri_batch_docset_hashes",
-    "tri_cbatch_create", "tri_cbatch_destroy", "tri_cbatch_query_status", "tri_cbatch_run", "tri_cbatch_sync", "tri_cbatch_match_counts", "tri_cbatch_topk", "tri_cbatch_docset", "tri_encode_google", "tri_encode_google_payloads", "tri_commit_google", "tri_commit_lucene", "tri_merge_google", "tri_merge_lucene", "tri_encode_lucene",
+    "tri_cbatch_create", "tri_cbatch_destroy", "tri_cbatch_query_status", "tri_cbatch_run", "tri_cbatch_sync", "tri_cbatch_match_counts", "tri_cbatch_topk", "tri_cbatch_docset", "tri_cbatch_ranked", "tri_cbatch_matched_terms", "tri_cbatch_matched_terms_wide", "tri_cbatch_matched_payloads", "tri_encode_google", "tri_encode_google_payloads", "tri_commit_google", "tri_commit_lucene", "tri_merge_google", "tri_merge_lucene", "tri_encode_lucene",
     "tri_comm_unique_id", "tri_comm_create", "tri_comm_create_custom", "tri_comm_destroy", "tri_gather_results",
     "tri_filter_create", "tri_filter_from_docset", "tri_filter_destroy", "tri_batch_set_filters",
 ]  # fmt: skip
@@ -179,6 +179,10 @@ def hip_lib():
     L.tri_cbatch_match_counts.argtypes = [vp, vp]
     L.tri_cbatch_topk.argtypes = [vp, vp, vp, vp]
     L.tri_cbatch_docset.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.tri_cbatch_ranked.argtypes = [vp, vp, vp, vp]
+    L.tri_cbatch_matched_terms.argtypes = [vp, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.tri_cbatch_matched_terms_wide.argtypes = L.tri_cbatch_matched_terms.argtypes
+    L.tri_cbatch_matched_payloads.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.tri_encode_google.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
     L.tri_encode_google_payloads.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
     L.tri_encode_lucene.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
@@ -845,6 +849,57 @@ class CollectionBatch:
         got = C.c_size_t()
         _check(hip_lib().tri_cbatch_docset(self.h, q, out.ctypes.data, n, C.byref(got)))
         return out[: got.value]
+
+    def ranked(self):
+        """After sync(), every part carrying the same ranker (Batch.set_ranker): (docids u32[nq, topk], scores f64[nq, topk], counts u32[nq]) — per query the
+        best topk documents over all parts, score descending, docID ascending, older source first; rows past counts[q] are zero (tri_cbatch_ranked)."""
+        k = max(1, max(getattr(b, "rank_topk", 0) for b in self.parts))
+        d = np.zeros((self.nq, k), dtype=np.uint32)
+        s = np.zeros((self.nq, k), dtype=np.float64)
+        c = np.zeros(self.nq, dtype=np.uint32)
+        _check(hip_lib().tri_cbatch_ranked(self.h, d.ctypes.data, s.ctypes.data, c.ctypes.data))
+        return d, s, c
+
+    def _query_width(self, q):
+        """(terms, nterms) of query q: those of the first part that reports it (the parts agree, or the row calls refuse)."""
+        terms = np.zeros(64, dtype=np.uint32)
+        for b in self.parts:
+            nt = C.c_uint32()
+            _check(hip_lib().tri_batch_query_terms_wide(b.h, q, terms.ctypes.data, C.byref(nt)))
+            if nt.value:
+                return terms, nt.value
+        return terms, 0
+
+    def _matched(self, q, n, wide):
+        L = hip_lib()
+        matched = L.tri_cbatch_matched_terms_wide if wide else L.tri_cbatch_matched_terms
+        terms, nt = self._query_width(q)
+        npos = C.c_size_t()
+        _check(matched(self.h, q, None, None, None, 0, C.byref(npos)))
+        present = np.zeros(n, dtype=np.uint64 if wide else np.uint32)
+        freq = np.zeros((n, max(nt, 1)), dtype=np.uint16)
+        pos = np.zeros(max(1, npos.value), dtype=np.uint16)
+        _check(matched(self.h, q, present.ctypes.data, freq.ctypes.data, pos.ctypes.data, pos.size, C.byref(npos)))
+        return terms[:nt], present, freq[:, :nt], pos[: npos.value]
+
+    def matched_terms(self, q, n):
+        """FLAG_MATCHED_TERMS parts: what Batch.matched_terms returns, for the n matches docset(q, n) returns — the parts' rows source after source; the terms
+        are the first reporting part's (the parts' term ids are their own)."""
+        return self._matched(q, n, self._query_width(q)[1] > 16)
+
+    def matched_terms_wide(self, q, n):
+        """... through the _wide call whatever the query's width: present as u64[n]."""
+        return self._matched(q, n, True)
+
+    def matched_payloads(self, q):
+        """FLAG_MATCHED_TERMS | FLAG_HIT_PAYLOADS parts: (lens u8[npos], payloads u64[npos]) parallel to matched_terms()'s positions."""
+        L = hip_lib()
+        n = C.c_size_t()
+        _check(L.tri_cbatch_matched_payloads(self.h, q, None, None, 0, C.byref(n)))
+        lens = np.zeros(max(1, n.value), dtype=np.uint8)
+        pl = np.zeros(max(1, n.value), dtype=np.uint64)
+        _check(L.tri_cbatch_matched_payloads(self.h, q, lens.ctypes.data, pl.ctypes.data, n.value, C.byref(n)))
+        return lens[: n.value], pl[: n.value]
 
     def close(self):
         if self.h:
