@@ -35,7 +35,9 @@ extern "C" {
                                 within 9: option rich_max_terms, tri_batch_query_terms_wide / tri_batch_matched_terms_wide (the default mode reports up to 64 matched terms per query; no struct grew);
                                 within 9: tri_decode_hits / tri_decode_hits_at (the codec seam's materialize_hits: the hits of whole lists and of chosen documents; no struct grew);
                                 within 9: tri_batch_set_ranker / tri_batch_ranked (the default mode ranks its matches on the device: a proximity score, top-K per query; no struct grew),
-                                tri_cbatch_ranked / tri_cbatch_matched_terms[_wide] / tri_cbatch_matched_payloads (the default mode over a collection) */
+                                tri_cbatch_ranked / tri_cbatch_matched_terms[_wide] / tri_cbatch_matched_payloads (the default mode over a collection);
+                                within 9: tri_isect_run / _status / _results / _histogram / _get_info / _destroy, options isect_max_bytes / isect_max_masks / isect_max_runs
+                                (Trinity::intersect: token-set co-occurrence counts; no existing struct grew) */
 
 /* status codes */
 #define TRI_OK 0
@@ -313,6 +315,70 @@ int tri_decode_hits(tri_index *, const uint32_t *terms, size_t n, uint16_t *posi
                     uint64_t *out_offsets /* [n + 1] */);
 int tri_decode_hits_at(tri_index *, const uint32_t *terms, const uint32_t *docids, size_t n, uint32_t *freqs /* [n] */, uint16_t *positions, uint8_t *payload_lens,
                        uint64_t *payloads, size_t cap /* hits */, uint64_t *out_offsets /* [n + 1] */);
+
+/* ---- token-set co-occurrence (Trinity::intersect) ----------------------------------------------------
+ * Trinity::intersect_impl (intersect.h:25-37, intersect.cpp:5-170) — the engine behind intersection_alternatives' "drop a word" suggestions — for a BATCH of
+ * requests over one index, synchronous like tri_decode_hits.  A request is a list of 1 .. 64 token GROUPS, each a set of synonymous terms (the reference's
+ * std::vector<std::unordered_set<str8_t>>); bit i of a document's mask is set when the document holds a term of group i.  Request r's groups follow request
+ * r - 1's: with G = the sum of all ngroups, group g's term ids are terms[group_first[g] .. group_first[g + 1]) (group_first[G + 1], ascending, an empty group is
+ * legal).  A term id of 0xffffffff, or a term without documents, is an UNKNOWN token (intersect.cpp:27-43: term_ctx().documents == 0).  origMask = the groups
+ * with a known term, forced to 0 when any term of the request is unknown (:33, :50-51).  A document is CONSIDERED when its mask is not origMask (:138), the
+ * stop-word test passes, and the index's masked set as it stands at the call (tri_index_set_masked) does not hold it (:140); the considered masks, in docID
+ * order, go through ctx::consider (:64-91) and finalize (:93-99).  A request without any known term is legal and yields empty lists (:47-48).
+ *
+ * Two things are consciously NOT copied.  (1) Stop words: the reference tests `first` / `last`, slot indices of its remaining[] array, not token indices
+ * (:112-131, :139) — they equal the mask's lowest / highest set bit only while every group has one term and no list has ended.  The engine implements what
+ * intersect.h:15-18 documents: a document is ignored when the LOWEST or the HIGHEST set bit of its mask is in stopwords_mask.  Parity with the reference's
+ * code is claimed for stopwords_mask == 0 only — the value intersection_alternatives passes (:276).  (2) ctx::indexPrev is a uint8_t and wraps once the
+ * antichain holds more than 255 entries; the engine's replay uses a full-width index.
+ *
+ * tri_isect_run (intersect.cpp:5-170): builds one docID bitmap row per distinct known term of the call in a scratch block of the call (the index's plane cache
+ * is not touched), runs the two passes of csrc/k_isect.hpp and the replay of csrc/host/isect_rows.hpp, and returns a handle that holds every request's answer.
+ * TRI_ERR_UNSUPPORTED for the whole call, *out untouched: the call's scratch would exceed option isect_max_bytes; an index whose docIDs reach 2^31.
+ * tri_isect_status (no counterpart: the reference's vector grows without bound, intersect.cpp:89): status[r] = TRI_OK, or TRI_ERR_UNSUPPORTED when one of the request's tables overflowed (options isect_max_masks / isect_max_runs): the caller
+ * keeps its CPU path for that request, as with tri_batch_query_status; the other requests of the call are unaffected.
+ * tri_isect_results (intersect.cpp:160-169): request r's list as intersect_impl appends it — (mask, count) pairs in finalize's order, popcount descending, then
+ * count descending; the reference's std::sort leaves ties unspecified, here they are broken by ascending mask.  masks == NULL: *n only.
+ * tri_isect_histogram: table H, the exact order-free product — every distinct mask the merge loop builds (intersect.cpp:111-131) on a document that passes
+ * :138-142, with its documents and its first docID, ascending mask.
+ * masks == NULL: *n only.  Both fail with TRI_ERR_UNSUPPORTED on a request whose status is that.
+ * tri_isect_get_info (the reference's only account of a run is its trace line, intersect.cpp:162-163): the kernels' constants and what the call used (the
+ * per-request arrays belong to the handle).  tri_isect_destroy: the handle and every list in it (intersect.cpp:165-169 appends to the caller's vector instead).
+ * TRI_ERR_INVALID, nothing written: a null argument, more than 65535 requests, ngroups of 0 or above 64, a non-zero `reserved`, a group_first that does not
+ * ascend, a term id >= the index's terms that is not 0xffffffff, r >= the call's requests, a cap smaller than the list.
+ * Options (tri_dev_set_option, read by tri_isect_run).  "isect_max_bytes": the scratch budget of a CALL — its rows (4 bytes per 32 docIDs and distinct known term:
+ * 1.3 MB a term at 10 M documents), its requests' tables and 8 bytes per request and span of 4096 documents; default 2 GiB, a ceiling: the scratch is taken from the
+ * handle's buffer pool for the call and goes back to it.  A call that would exceed it is TRI_ERR_UNSUPPORTED as a whole (split it).  "isect_max_masks": the most slots
+ * of a request's table H (default 262144; 16 bytes each + 4 for the thresholds).  H is sized by the call's WIDEST request — g groups make fewer than 2^g masks: 2 x 2^g
+ * slots, at least 64 — up to the option, the same for every request of the call.  "isect_max_runs": the most slots of a request's table C (default 524288; 12 bytes each).
+ * C is keyed by (mask, epoch), so the group count does not bound it; it is sized AFTER pass 1 from H, which gives an exact upper bound — every mask that has a strict
+ * superset adds one key per epoch from its threshold's on — twice the largest request's bound, at least 64, up to the option: a request whose runs fit the option is
+ * never refused for them.  tri_isect_info.max_masks / max_runs: the slots the call used (max_runs 0: pass 2 was not needed). */
+typedef struct tri_isect tri_isect;
+typedef struct tri_isect_request {
+        uint32_t ngroups;        /* 1 .. 64 */
+        uint32_t reserved;       /* 0 */
+        uint64_t stopwords_mask; /* bit i: group i is a stop word (intersect.h:15-18) */
+} tri_isect_request;
+typedef struct tri_isect_info {
+        uint32_t span_docs;       /* documents a wave takes (k_isect.hpp ISECT_SPAN) */
+        uint32_t lds_slots;       /* keys of a wave's LDS table (ISECT_LDS_SLOTS) */
+        uint32_t nreq, nspans;
+        uint32_t rows;            /* plane-0 rows built: the distinct known terms of the call */
+        uint32_t max_masks, max_runs; /* the table sizes the call ran with */
+        uint32_t passes;          /* kernels passes run: 0 (no known term), 1 (no mask has a strict superset: nothing to credit) or 2 */
+        uint64_t row_bytes;       /* bytes of one row */
+        uint64_t scratch_bytes;   /* rows + tables + per-span words: what counted against isect_max_bytes */
+        const uint32_t *h_size;   /* [nreq] entries of H */
+        const uint32_t *c_size;   /* [nreq] entries of C */
+        const uint32_t *lds_spills; /* [nreq] (mask, step) groups that found their wave's LDS table full and went to the global one */
+} tri_isect_info;
+int tri_isect_run(tri_index *, const tri_isect_request *reqs, size_t nreq, const uint32_t *terms, const uint32_t *group_first, tri_isect **out);
+int tri_isect_status(const tri_isect *, int32_t *status /* [nreq] */);
+int tri_isect_results(const tri_isect *, size_t r, uint64_t *masks, uint32_t *counts, size_t cap, size_t *n);
+int tri_isect_histogram(const tri_isect *, size_t r, uint64_t *masks, uint32_t *counts, uint32_t *first_docs, size_t cap, size_t *n);
+int tri_isect_get_info(const tri_isect *, tri_isect_info *);
+void tri_isect_destroy(tri_isect *);
 
 /* ---- batched query execution (span seam) -----------------------------------------------------------
  * Replaces, for a whole batch of queries at once: queryexec_ctx::build_iterator + build_span

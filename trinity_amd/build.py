@@ -34,7 +34,7 @@ def hipcc():
 
 
 def build_hip(force=False):
-    if force or _newer(LIB_HIP, _deps(HIP_SRCS) + [os.path.join(PKG, "csrc", "host", "result_rows.hpp")]):  # (read_side.hpp's host transforms)
+    if force or _newer(LIB_HIP, _deps(HIP_SRCS) + [os.path.join(PKG, "csrc", "host", n) for n in ("result_rows.hpp", "isect_rows.hpp")]):  # (read_side.hpp's host transforms, isect_side.hpp's replay)
         cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-o", LIB_HIP] + HIP_SRCS + ["-ldl"]
         subprocess.run(cmd, check=True)
     return LIB_HIP
@@ -151,9 +151,24 @@ def build_mirror_collection_test(force=False):
     return MIRROR_COLLECTION_BIN
 
 
+MIRROR_ISECT_SRC = os.path.join(ROOT, "tests", "cpp", "host_mirror_isect_test.cpp")
+MIRROR_ISECT_BIN = os.path.join(ROOT, "tests", "cpp", "host_mirror_isect_test")
+
+
+def build_mirror_isect_test(force=False):
+    """Trinity::intersect on the operator surface (csrc/host/trinity_gpu.hpp: intersect_impl / intersect over a source and over a collection, through tri_isect_run)
+    compiled into its driver; in-tree, so that it travels to the GPU box, where tests/test_host_mirror_isect.py runs it."""
+    deps = [MIRROR_ISECT_SRC, os.path.join(PKG, "csrc", "host", "trinity_gpu.hpp"), os.path.join(PKG, "csrc", "host", "google_encoder.hpp"), os.path.join(ROOT, "include", "trinity_hip.h")]
+    if force or _newer(MIRROR_ISECT_BIN, deps):
+        build_hip()
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", MIRROR_ISECT_BIN, MIRROR_ISECT_SRC, "-L" + PKG, "-ltrinity_hip", "-Wl,-rpath,$ORIGIN/../../trinity_amd"]
+        subprocess.run(cmd, check=True)
+    return MIRROR_ISECT_BIN
+
+
 def build_all(force=False):
     return (build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force), build_mirror_wide_terms_test(force),
-            build_mirror_hits_test(force), build_mirror_rank_test(force), build_mirror_collection_test(force))
+            build_mirror_hits_test(force), build_mirror_rank_test(force), build_mirror_collection_test(force), build_mirror_isect_test(force))
 
 
 def kernels_stamp():

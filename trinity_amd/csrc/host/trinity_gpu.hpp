@@ -24,6 +24,7 @@
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <utility>
 #include <vector>
 
@@ -1125,6 +1126,92 @@ namespace trinity_amd {
                         out.push_back(std::move(filter));
                 }
                 return out;
+        }
+
+        // ---- intersect.h:25-47, intersect.cpp:5-217: which subsets of a query's token groups co-occur in documents, and in how many — the engine behind
+        // intersection_alternatives' suggestions, on the device (tri_isect_run).  tokens: per query token the set of its synonymous terms, at most 64 sets; a
+        // term the source does not know is an unknown token (intersect.cpp:38-43).  The registry becomes the source's masked set for the call, as in exec_query.
+        // What differs from the reference's code, on purpose: the stop-word rule is the documented one (the lowest or the highest set bit of a document's mask
+        // is in stopwordsMask, intersect.h:15-18 — the same as the reference's only for stopwordsMask == 0), ties of the final order are broken by ascending
+        // mask, and a request that overflows the engine's tables (options isect_max_masks / isect_max_runs) throws invalid_argument: the caller keeps its own path.
+        // intersection_alternatives (intersect.cpp:219-327) needs the query rewriter (queries_rewrite.h) and is not mirrored.
+        inline void intersect_impl(const uint64_t stopwordsMask, const std::vector<std::unordered_set<std::string>> &tokens, IndexSource *const src,
+                                   masked_documents_registry *const maskedDocumentsRegistry, std::vector<std::pair<uint64_t, uint32_t>> *const out) {
+                if (tokens.empty() || tokens.size() > 64 || !out || !src)
+                        throw invalid_argument("intersect_impl: 1 .. 64 token sets, a source and an output vector"); // intersect.cpp:18-19
+                struct Restore {
+                        IndexSource *src;
+                        std::vector<docid_t> before;
+                        ~Restore() {
+                                try {
+                                        src->set_masked_documents(before);
+                                } catch (...) {
+                                }
+                        }
+                } restore{src, src->masked_documents()};
+                src->set_masked_documents(maskedDocumentsRegistry ? maskedDocumentsRegistry->ids : std::vector<docid_t>{});
+                std::vector<uint32_t> terms, first{0};
+                for (const auto &set : tokens) {
+                        for (const auto &token : set) {
+                                const uint32_t id = src->term_id(token);
+                                terms.push_back(id == 0x0fffffffu ? 0xffffffffu : id); // (term_id's "no such term" -> tri_isect_run's unknown token)
+                        }
+                        first.push_back((uint32_t)terms.size());
+                }
+                terms.push_back(0); // (never null)
+                const tri_isect_request req{(uint32_t)tokens.size(), 0, stopwordsMask};
+                tri_isect *h = nullptr;
+                check(tri_isect_run(src->handle(), &req, 1, terms.data(), first.data(), &h));
+                struct Free {
+                        tri_isect *h;
+                        ~Free() { tri_isect_destroy(h); }
+                } free_{h};
+                size_t n = 0;
+                check(tri_isect_results(h, 0, nullptr, nullptr, 0, &n));
+                std::vector<uint64_t> masks(n + 1);
+                std::vector<uint32_t> counts(n + 1);
+                check(tri_isect_results(h, 0, masks.data(), counts.data(), n, &n));
+                for (size_t i = 0; i < n; ++i)
+                        out->push_back({masks[i], counts[i]}); // intersect.cpp:165-169
+        }
+        inline std::vector<std::pair<uint64_t, uint32_t>> intersect(const uint64_t stopwordsMask, const std::vector<std::unordered_set<std::string>> &tokens, IndexSource *src,
+                                                                    masked_documents_registry *reg) { // intersect.h:27-32
+                std::vector<std::pair<uint64_t, uint32_t>> res;
+                intersect_impl(stopwordsMask, tokens, src, reg, &res);
+                return res;
+        }
+        // intersect.cpp:172-201: one run per source under that source's registry (origMask is per source: a token one source does not know is unknown there
+        // only), then the lists sorted by mask and equal masks summed
+        inline std::vector<std::pair<uint64_t, uint32_t>> intersect(const uint64_t stopwordsMask, const std::vector<std::unordered_set<std::string>> &tokens,
+                                                                    IndexSourcesCollection *collection) {
+                std::vector<std::pair<uint64_t, uint32_t>> out;
+                for (std::size_t i = 0; i != collection->sources.size(); ++i) {
+                        const auto scanner = collection->scanner_registry_for(i);
+                        intersect_impl(stopwordsMask, tokens, collection->sources[i], scanner.get(), &out);
+                }
+                std::stable_sort(out.begin(), out.end(), [](const auto &a, const auto &b) noexcept { return a.first < b.first; }); // :184
+                std::size_t o = 0;
+                for (std::size_t p = 0; p != out.size();) { // :187-197
+                        const auto mask = out[p].first;
+                        auto cnt = out[p].second;
+                        for (++p; p != out.size() && out[p].first == mask; ++p)
+                                cnt += out[p].second;
+                        out[o++] = {mask, cnt};
+                }
+                out.resize(o);
+                return out;
+        }
+        // intersect.cpp:203-217: the indices of a mask's set bits, ascending; returns how many
+        inline uint8_t intersection_indices(uint64_t mask, uint8_t *const out) {
+                uint8_t collected = 0;
+                for (; mask; mask &= mask - 1)
+                        out[collected++] = (uint8_t)__builtin_ctzll(mask);
+                return collected;
+        }
+        // intersect.h:42-47
+        static inline bool sort_intersections(const std::pair<uint64_t, uint32_t> &a, const std::pair<uint64_t, uint32_t> &b) noexcept {
+                const auto ca = __builtin_popcountll(a.first), cb = __builtin_popcountll(b.first);
+                return cb < ca || (cb == ca && b.second < a.second);
         }
 
         // The batched sibling of exec_query_par (exec.h:87-177): all queries in ONE engine batch; DocumentsOnly results

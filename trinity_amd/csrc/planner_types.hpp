@@ -66,6 +66,11 @@ struct tri_options {
         uint64_t rich_max_terms = 16;          // default mode: a query of more reportable terms than this is left out (TRI_ERR_UNSUPPORTED per query).  16 (RICH_NARROW_TERMS) .. 64
                                                // (RICH_WIDE_TERMS: one 64-bit mask, and what the CPU oracle holds); any other value fails tri_batch_create.  Off by default because
                                                // of what a wide-report query reserves: 2 x stride bytes of frequency row + 8 bytes of masks per OUTPUT SLOT (its tree's upper bound)
+        uint64_t isect_max_bytes = 2ull << 30; // tri_isect_run (isect_side.hpp): scratch budget of a call — plane-0 rows (one per distinct known term), the requests' tables, the per-span words;
+                                               // beyond it the call is TRI_ERR_UNSUPPORTED
+        uint64_t isect_max_masks = 262144;     // ... most slots of a request's table H (distinct considered masks; 16 + 4 bytes each): sized by the call's widest request (2 x 2^groups) up to this
+        uint64_t isect_max_runs = 524288;      // ... of its table C ((mask, epoch) run credits; 12 bytes each): sized after pass 1 from H's exact bound, up to this.  A request that
+                                               // overflows either table answers TRI_ERR_UNSUPPORTED
         uint64_t probe_max_blocks = 0;         // > 0: a lead list of at most this many blocks against lists that all have planes runs in k_probe (a wave per task) instead of
                                                // k_and's candidate tiles.  Off by default — measured at cfg2 (step ms / k_probe / k_and): 0: 2.14 / - / 0.78; 64: 2.25 / 0.15 / 0.75;
                                                // 256: 2.26 / 0.22 / 0.70; 1024: 2.35 / 0.41 / 0.59; all: 2.55 / 0.82 / 0.41 — k_and's time is its tail, not its task count

@@ -42,6 +42,16 @@ class TriRanker(C.Structure):
 RANK_PROXIMITY = 1
 
 
+class TriIsectRequest(C.Structure):
+    _fields_ = [("ngroups", C.c_uint32), ("reserved", C.c_uint32), ("stopwords_mask", C.c_uint64)]
+
+
+class TriIsectInfo(C.Structure):
+    _fields_ = [("span_docs", C.c_uint32), ("lds_slots", C.c_uint32), ("nreq", C.c_uint32), ("nspans", C.c_uint32), ("rows", C.c_uint32), ("max_masks", C.c_uint32),
+                ("max_runs", C.c_uint32), ("passes", C.c_uint32), ("row_bytes", C.c_uint64), ("scratch_bytes", C.c_uint64), ("h_size", C.POINTER(C.c_uint32)),
+                ("c_size", C.POINTER(C.c_uint32)), ("lds_spills", C.POINTER(C.c_uint32))]  # fmt: skip
+
+
 class TriIndexInfo(C.Structure):
     _fields_ = [
         ("index_bytes", C.c_uint64),
@@ -117,6 +127,7 @@ ABI_SYMBOLS = [
     "tri_cbatch_create", "tri_cbatch_destroy", "tri_cbatch_query_status", "tri_cbatch_run", "tri_cbatch_sync", "tri_cbatch_match_counts", "tri_cbatch_topk", "tri_cbatch_docset", "tri_cbatch_ranked", "tri_cbatch_matched_terms", "tri_cbatch_matched_terms_wide", "tri_cbatch_matched_payloads", "tri_encode_google", "tri_encode_google_payloads", "tri_commit_google", "tri_commit_lucene", "tri_merge_google", "tri_merge_lucene", "tri_encode_lucene",
     "tri_comm_unique_id", "tri_comm_create", "tri_comm_create_custom", "tri_comm_destroy", "tri_gather_results",
     "tri_filter_create", "tri_filter_from_docset", "tri_filter_destroy", "tri_batch_set_filters",
+    "tri_isect_run", "tri_isect_status", "tri_isect_results", "tri_isect_histogram", "tri_isect_get_info", "tri_isect_destroy",
 ]  # fmt: skip
 
 _hip = None
@@ -202,6 +213,13 @@ def hip_lib():
     L.tri_filter_destroy.restype = None
     L.tri_batch_set_filters.argtypes = [vp, vp, C.c_size_t, vp]
     L.tri_batch_set_ranker.argtypes = [vp, vp, vp]
+    L.tri_isect_run.argtypes = [vp, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
+    L.tri_isect_status.argtypes = [vp, vp]
+    L.tri_isect_results.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.tri_isect_histogram.argtypes = [vp, C.c_size_t, vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.tri_isect_get_info.argtypes = [vp, C.POINTER(TriIsectInfo)]
+    L.tri_isect_destroy.argtypes = [vp]
+    L.tri_isect_destroy.restype = None
     L.tri_batch_ranked.argtypes = [vp, vp, vp, vp]
     _hip = L
     return L
@@ -451,6 +469,47 @@ class Device:
             self.h = C.c_void_p()
 
 
+class Intersection:
+    """The answers of one tri_isect_run call."""
+
+    def __init__(self, h, nreq):
+        self.h, self.nreq = h, nreq
+
+    def status(self):
+        st = np.zeros(max(1, self.nreq), dtype=np.int32)
+        _check(hip_lib().tri_isect_status(self.h, st.ctypes.data))
+        return st[: self.nreq].tolist()
+
+    def results(self, r):
+        """request r's list as intersect_impl appends it: [(mask, count)] in finalize's order (ties by ascending mask)"""
+        n = C.c_size_t()
+        _check(hip_lib().tri_isect_results(self.h, r, None, None, 0, C.byref(n)))
+        m, c = np.zeros(max(1, n.value), dtype=np.uint64), np.zeros(max(1, n.value), dtype=np.uint32)
+        _check(hip_lib().tri_isect_results(self.h, r, m.ctypes.data, c.ctypes.data, n.value, C.byref(n)))
+        return list(zip(m[: n.value].tolist(), c[: n.value].tolist()))
+
+    def histogram(self, r):
+        """table H of request r: [(mask, documents, first docID)], ascending mask"""
+        n = C.c_size_t()
+        _check(hip_lib().tri_isect_histogram(self.h, r, None, None, None, 0, C.byref(n)))
+        m, c, f = np.zeros(max(1, n.value), dtype=np.uint64), np.zeros(max(1, n.value), dtype=np.uint32), np.zeros(max(1, n.value), dtype=np.uint32)
+        _check(hip_lib().tri_isect_histogram(self.h, r, m.ctypes.data, c.ctypes.data, f.ctypes.data, n.value, C.byref(n)))
+        return list(zip(m[: n.value].tolist(), c[: n.value].tolist(), f[: n.value].tolist()))
+
+    def info(self):
+        i = TriIsectInfo()
+        _check(hip_lib().tri_isect_get_info(self.h, C.byref(i)))
+        out = {k: getattr(i, k) for k, _ in TriIsectInfo._fields_[:10]}
+        for k in ("h_size", "c_size", "lds_spills"):
+            out[k] = [getattr(i, k)[r] for r in range(self.nreq)]
+        return out
+
+    def close(self):
+        if self.h:
+            hip_lib().tri_isect_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 def host_encode_google(docs, freqs, positions, term_first, payload_lens=None, payloads=None):
     """The HOST encoder (csrc/host/google_encoder.hpp: byte-identical to the reference's) over the same arguments: tests' checker of
     Device.encode_google."""
@@ -511,6 +570,22 @@ class Index:
         _check(hip_lib().tri_decode_terms(self.h, t.ctypes.data, t.size, docs.ctypes.data, freqs.ctypes.data if want_freqs else None, offs.ctypes.data))
         assert int(offs[-1]) == tot, (int(offs[-1]), tot)
         return docs, freqs, offs
+
+    def intersect(self, requests):
+        """Trinity::intersect for a batch of requests (tri_isect_run, intersect.cpp:5-170).  requests: [(groups, stopwords_mask)], groups = lists of term ids
+        (0xffffffff: a token the dictionary does not know).  -> Intersection; close() it."""
+        reqs = (TriIsectRequest * max(1, len(requests)))()
+        terms, first = [], [0]
+        for r, (groups, stop) in enumerate(requests):
+            reqs[r].ngroups, reqs[r].reserved, reqs[r].stopwords_mask = len(groups), 0, int(stop)
+            for g in groups:
+                terms += [int(t) for t in g]
+                first.append(len(terms))
+        t = np.array(terms + [0], dtype=np.uint32)
+        gf = np.array(first, dtype=np.uint32)
+        h = C.c_void_p()
+        _check(hip_lib().tri_isect_run(self.h, reqs, len(requests), t.ctypes.data, gf.ctypes.data, C.byref(h)))
+        return Intersection(h, len(requests))
 
     def decode_hits(self, terms, want_payloads=False):
         """The hits of whole postings lists (tri_decode_hits: materialize_hits for every document, in list order), sized then filled.
