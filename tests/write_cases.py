@@ -16,6 +16,7 @@ import os
 
 import numpy as np
 
+import pfor_cases
 from merge_restated import encoder_arrays, merge_term
 
 ENC_SCAN_CHUNK = 32768  # (k_encode.hpp; tests/test_write_cases.py::test_constants_mirror_the_headers parses the header)
@@ -352,11 +353,12 @@ def encoder_cases():
     out = {"google_varints": google_varints, "google_skip_cap": google_skip_cap, "lucene_blocks": lucene_blocks}
     out.update({f"google_skip_phases_r{r}": (lambda r=r: google_skip_phases(r)) for r in range(8)})
     out.update({f"scan_{n}": (lambda n=n: scan_sizes(n)) for n in SCAN_SIZES})
+    out.update({f"pfor_{w}": (lambda w=w: pfor_cases.EncoderCase(w)) for w in ("narrow", "wide")})  # the chosen PFOR128 group shapes (tests/pfor_cases.py)
     return out
 
 
 GOOGLE_ENCODER_CASES = ["google_varints"] + [f"google_skip_phases_r{r}" for r in range(8)] + [f"scan_{n}" for n in SCAN_SIZES] + ["google_skip_cap"]
-LUCENE_ENCODER_CASES = ["lucene_blocks"] + [f"scan_{n}" for n in SCAN_SIZES] + [f"google_skip_phases_r{r}" for r in (0, 5)]
+LUCENE_ENCODER_CASES = ["lucene_blocks"] + [f"scan_{n}" for n in SCAN_SIZES] + [f"google_skip_phases_r{r}" for r in (0, 5)] + ["pfor_narrow", "pfor_wide"]
 
 
 def oracle_read_back(name, arrays, index, terms):
