@@ -127,39 +127,34 @@ extern "C" int tri_isect_run(tri_index *ix, const tri_isect_request *reqs, size_
         if (!nrows || !nreq) // no known term anywhere: empty lists (intersect.cpp:47-48)
                 return finish();
 
-        struct Scratch { // a pooled block of this call
-                tri_dev *dev;
-                void *p = nullptr;
-                ~Scratch() { pool_free(dev, p); }
-                uint8_t *at(const uint64_t off) const { return static_cast<uint8_t *>(p) + off; }
-        } s1{dev}, s2{dev};
-        HIP_TRY(pool_alloc(dev, &s1.p, total1));
+        Pooled<uint8_t> s1, s2; // the pooled blocks of this call
+        HIP_TRY(s1.alloc(dev, total1));
         I.scratch_bytes = total1;
         hipStream_t st = dev->stream;
-        HIP_TRY(hipMemcpyAsync(s1.at(o_build), P.build.data(), P.build.size() * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(s1.at(o_rowtab), P.rowtab.data(), P.rowtab.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(s1.at(o_reqs), P.reqs.data(), nreq * sizeof(IsectReq), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(s1.at(o_hk), 0, o_hfirst - o_hk, st));
-        HIP_TRY(hipMemsetAsync(s1.at(o_hfirst), 0xff, h32_b, st));
+        HIP_TRY(hipMemcpyAsync(s1 + o_build, P.build.data(), P.build.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s1 + o_rowtab, P.rowtab.data(), P.rowtab.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s1 + o_reqs, P.reqs.data(), nreq * sizeof(IsectReq), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(s1 + o_hk, 0, o_hfirst - o_hk, st));
+        HIP_TRY(hipMemsetAsync(s1 + o_hfirst, 0xff, h32_b, st));
         IsectTables T{};
-        T.h_key = reinterpret_cast<unsigned long long *>(s1.at(o_hk));
-        T.h_cnt = reinterpret_cast<uint32_t *>(s1.at(o_hcnt));
-        T.h_first = reinterpret_cast<uint32_t *>(s1.at(o_hfirst));
-        T.flags = reinterpret_cast<uint32_t *>(s1.at(o_flags));
+        T.h_key = reinterpret_cast<unsigned long long *>(s1 + o_hk);
+        T.h_cnt = reinterpret_cast<uint32_t *>(s1 + o_hcnt);
+        T.h_first = reinterpret_cast<uint32_t *>(s1 + o_hfirst);
+        T.flags = reinterpret_cast<uint32_t *>(s1 + o_flags);
         T.spills = T.flags + nr;
         T.h_cap = h_cap;
         T.c_cap = 0;
-        const uint64_t *d_rows = reinterpret_cast<const uint64_t *>(s1.at(o_rows));
-        const uint2 *d_rowtab = reinterpret_cast<const uint2 *>(s1.at(o_rowtab));
-        const IsectReq *d_reqs = reinterpret_cast<const IsectReq *>(s1.at(o_reqs));
-        unsigned long long *d_span = reinterpret_cast<unsigned long long *>(s1.at(o_span));
+        const uint64_t *d_rows = reinterpret_cast<const uint64_t *>(s1 + o_rows);
+        const uint2 *d_rowtab = reinterpret_cast<const uint2 *>(s1 + o_rowtab);
+        const IsectReq *d_reqs = reinterpret_cast<const IsectReq *>(s1 + o_reqs);
+        unsigned long long *d_span = reinterpret_cast<unsigned long long *>(s1 + o_span);
 
         // ---- the rows: plane 0 of every distinct known term (k_term_plane0 writes every word of a row: no memset), the index's plane cache untouched
         const uint32_t nwin = plw / PL_WORDS;
         for (uint32_t y0 = 0; y0 < nrows; y0 += 65535u) {
                 const uint32_t ny = std::min(65535u, nrows - y0);
                 TRI_LAUNCH(k_term_plane0, ix->codec, dim3((nwin + P0_GROUP - 1) / P0_GROUP, ny), dim3(AND_WG), st, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec, ix->d_blk_doff, ix->d_win,
-                           ix->d_terms, reinterpret_cast<const uint32_t *>(s1.at(o_build)) + 2 * (size_t)y0, reinterpret_cast<uint32_t *>(s1.at(o_rows)), plw, (uint32_t *)nullptr);
+                           ix->d_terms, reinterpret_cast<const uint32_t *>(s1 + o_build) + 2 * (size_t)y0, reinterpret_cast<uint32_t *>(s1 + o_rows), plw, (uint32_t *)nullptr);
                 HIP_TRY(hipGetLastError());
         }
         // ---- pass 1
@@ -169,10 +164,10 @@ extern "C" int tri_isect_run(tri_index *ix, const tri_isect_request *reqs, size_
         I.passes = 1;
         std::vector<uint64_t> hk((size_t)nr * h_cap);
         std::vector<uint32_t> hcnt((size_t)nr * h_cap), hfirst((size_t)nr * h_cap), flags((size_t)nr * 2);
-        HIP_TRY(hipMemcpyAsync(hk.data(), s1.at(o_hk), hk_b, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(hcnt.data(), s1.at(o_hcnt), h32_b, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(hfirst.data(), s1.at(o_hfirst), h32_b, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(flags.data(), s1.at(o_flags), (size_t)nr * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(hk.data(), s1 + o_hk, hk_b, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(hcnt.data(), s1 + o_hcnt, h32_b, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(hfirst.data(), s1 + o_hfirst, h32_b, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(flags.data(), s1 + o_flags, (size_t)nr * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
 
         // ---- the host step: H by first docID, the thresholds (per slot of H), the epoch bounds, and what C can hold at most: a mask with a threshold adds one
@@ -227,24 +222,24 @@ extern "C" int tri_isect_run(tri_index *ix, const tri_isect_request *reqs, size_
                 if (total1 + total2 > dev->opt.isect_max_bytes)
                         return fail(TRI_ERR_UNSUPPORTED, "tri_isect_run: the run tables (%u requests of %u slots) bring the call's scratch to %llu bytes: above isect_max_bytes = %llu", nr, c_cap,
                                     (unsigned long long)(total1 + total2), (unsigned long long)dev->opt.isect_max_bytes);
-                HIP_TRY(pool_alloc(dev, &s2.p, total2));
+                HIP_TRY(s2.alloc(dev, total2));
                 I.scratch_bytes += total2;
-                T.c_key = reinterpret_cast<unsigned long long *>(s2.at(o_ck));
-                T.c_cnt = reinterpret_cast<uint32_t *>(s2.at(o_ccnt));
+                T.c_key = reinterpret_cast<unsigned long long *>(s2 + o_ck);
+                T.c_cnt = reinterpret_cast<uint32_t *>(s2 + o_ccnt);
                 T.c_cap = c_cap;
-                HIP_TRY(hipMemsetAsync(s2.at(o_ck), 0, o_thr - o_ck, st));
-                HIP_TRY(hipMemcpyAsync(s2.at(o_thr), thr.data(), h32_b, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(s2.at(o_bounds), bounds.data(), bounds.size() * 4, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(s1.at(o_reqs), P.reqs.data(), nreq * sizeof(IsectReq), hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemsetAsync(s2 + o_ck, 0, o_thr - o_ck, st));
+                HIP_TRY(hipMemcpyAsync(s2 + o_thr, thr.data(), h32_b, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(s2 + o_bounds, bounds.data(), bounds.size() * 4, hipMemcpyHostToDevice, st));
+                HIP_TRY(hipMemcpyAsync(s1 + o_reqs, P.reqs.data(), nreq * sizeof(IsectReq), hipMemcpyHostToDevice, st));
                 hipLaunchKernelGGL(k_isect_runs, dim3(nspans, nr), dim3(64), 0, st, d_rows, plw64, d_rowtab, d_reqs, (const uint32_t *)ix->d_masked, T, (const unsigned long long *)d_span, nspans,
-                                   reinterpret_cast<const uint32_t *>(s2.at(o_thr)), reinterpret_cast<const uint32_t *>(s2.at(o_bounds)));
+                                   reinterpret_cast<const uint32_t *>(s2 + o_thr), reinterpret_cast<const uint32_t *>(s2 + o_bounds));
                 HIP_TRY(hipGetLastError());
                 I.passes = 2;
                 ck.resize((size_t)nr * c_cap);
                 ccnt.resize((size_t)nr * c_cap);
-                HIP_TRY(hipMemcpyAsync(ck.data(), s2.at(o_ck), ck_b, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(ccnt.data(), s2.at(o_ccnt), c32_b, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(flags.data(), s1.at(o_flags), (size_t)nr * 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(ck.data(), s2 + o_ck, ck_b, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(ccnt.data(), s2 + o_ccnt, c32_b, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(flags.data(), s1 + o_flags, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipStreamSynchronize(st));
         }
 

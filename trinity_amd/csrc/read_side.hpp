@@ -178,13 +178,13 @@ namespace {
                 if (cap < total)
                         return fail(TRI_ERR_INVALID, "%s: the docID sets need %llu slots, %zu given", fn, (unsigned long long)total, cap);
                 // the sets are gathered on the device into one contiguous buffer and come over in a single copy (the lock covers the pool too)
-                uint32_t *d_flat = nullptr;
-                uint64_t *d_slot_off = nullptr;
+                Pooled<uint32_t> d_flat;
+                Pooled<uint64_t> d_slot_off;
                 ReadBack rb(dev);
                 rb.enqueue([&](hipStream_t s) {
-                        hipError_t e = pool_alloc(dev, (void **)&d_flat, (total + 64) * 4);
+                        hipError_t e = d_flat.alloc(dev, (total + 64) * 4);
                         if (e == hipSuccess)
-                                e = pool_alloc(dev, (void **)&d_slot_off, (nslots + 1) * 8 + POOL_MIN_BYTES);
+                                e = d_slot_off.alloc(dev, (nslots + 1) * 8 + POOL_MIN_BYTES);
                         if (e == hipSuccess)
                                 e = hipMemcpyAsync(d_slot_off, slot_off.data(), (nslots + 1) * 8, hipMemcpyHostToDevice, s); // (pageable source: staged before the call returns)
                         if (e != hipSuccess)
@@ -193,10 +193,7 @@ namespace {
                                            (const uint32_t *)b->d_counts, (const uint32_t *)b->d_out, (const uint64_t *)d_slot_off, d_flat, forms ? 1u : 0u);
                         return hipGetLastError();
                 });
-                const hipError_t e = rb.copy(out, d_flat, total * 4).wait();
-                pool_free(dev, d_flat);
-                pool_free(dev, d_slot_off);
-                HIP_TRY(e);
+                HIP_TRY(rb.copy(out, d_flat, total * 4).wait()); // (the wait comes first on every way out: the two buffers go back to the pool behind it)
                 return TRI_OK;
         }
 
@@ -380,7 +377,7 @@ extern "C" int tri_batch_docset_hashes(tri_batch *b, uint64_t *hashes) {
                 ReadBack rb(b->dev);
                 rb.enqueue([&](hipStream_t s) {
                         if (!b->d_hashes)
-                                if (const hipError_t e = hipMalloc((void **)&b->d_hashes, (size_t)n * 8))
+                                if (const hipError_t e = b->d_hashes.alloc((size_t)n * 8))
                                         return e;
                         hipLaunchKernelGGL(k_hash_docsets, dim3((n + 63) / 64), dim3(64), 0, s, b->dev_at(b->plan), b->dev_at(b->tasks), b->d_counts, n, b->d_out, b->d_hashes);
                         return hipGetLastError();

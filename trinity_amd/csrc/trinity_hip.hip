@@ -204,9 +204,7 @@ static hipError_t pool_alloc(tri_dev *dev, void **out, const size_t bytes) {
                 P.size_of[*out] = rounded;
         return e;
 }
-static void pool_free(tri_dev *dev, void *p) {
-        if (!p)
-                return;
+static void pool_free(tri_dev *dev, void *p) { // (p != nullptr: the owners' release, as pinned_free and event_put are)
         if (!dev) {
                 hipFree(p);
                 return;
@@ -231,12 +229,6 @@ static void pool_free(tri_dev *dev, void *p) {
                 P.idle.erase(P.idle.begin() + (ptrdiff_t)big);
         }
 }
-struct DevBuf { // a device allocation of one call (not pooled), released on every way out of it
-        void *p = nullptr;
-        ~DevBuf() { hipFree(p); }
-        template <class T>
-        T *as() const { return static_cast<T *>(p); }
-};
 // pinned host block of at least `bytes` (64-byte aligned: hipHostMalloc is page-aligned); *cap = its size
 static uint8_t *pinned_alloc(tri_dev *dev, const size_t bytes, size_t *cap) {
         DevLock g(dev->mu);
@@ -261,12 +253,6 @@ static uint8_t *pinned_alloc(tri_dev *dev, const size_t bytes, size_t *cap) {
         return static_cast<uint8_t *>(p);
 }
 static void pinned_free(tri_dev *dev, void *p, const size_t cap) {
-        if (!p)
-                return;
-        if (!dev) {
-                hipHostFree(p);
-                return;
-        }
         DevLock g(dev->mu);
         if (dev->pinned_idle.size() >= PINNED_IDLE_MAX) { // full: the block idle for longest goes, the one just released stays — the list follows the
                 hipHostFree(dev->pinned_idle.front().second); // caller's CURRENT batches (a list full of another workload's block sizes made every create
@@ -275,8 +261,6 @@ static void pinned_free(tri_dev *dev, void *p, const size_t cap) {
         dev->pinned_idle.emplace_back(cap, p);
 }
 static void event_put(tri_dev *dev, hipEvent_t e) {
-        if (!e)
-                return;
         DevLock g(dev->mu);
         dev->events_idle.push_back(e);
 }
@@ -290,29 +274,46 @@ static hipError_t event_get(tri_dev *dev, hipEvent_t *e) {
         return hipEventCreate(e);
 }
 
+// the owning handles over the calls above: DevMem, Pooled, Pinned, PooledEvent, DevRef
+#include "owners.hpp"
+
+// An arena's sections, each named ONCE: carve(view, bytes) points `view` at the next section and moves on by `bytes`, rounded up to `align`.  Without a base
+// (the sizing pass) no view is touched and only `at` advances; `have` == false: the object lacks the section — a null view, no room taken.
+struct Carver {
+        uint8_t *base;
+        size_t at = 0, align = 256;
+        template <class T>
+        void operator()(T *&view, const size_t bytes, const bool have = true) {
+                if (base)
+                        view = have ? reinterpret_cast<T *>(base + at) : nullptr;
+                if (have)
+                        at += (bytes + align - 1) & ~(align - 1);
+        }
+};
+
 // the uploaded segment: what the walk derived (HostIndex; the planner reads terms / blk_last / docbytes / hitbytes / win / the df order)
 // plus its device copies
 struct tri_index : HostIndex {
-        tri_dev *dev = nullptr;
-        uint8_t *d_index = nullptr, *d_hits = nullptr;
-        uint32_t *d_blk_last = nullptr, *d_blk_off = nullptr, *d_win = nullptr;
-        uint32_t *d_blk_hits = nullptr, *d_hdir = nullptr; // where a directory row's hits start — LUCENE + hits.data: hit ordinal within the term
+        DevRef dev; // FIRST: members go in reverse order of declaration, so the handle is let go of after every buffer and event below went back to it
+        DevMem<uint8_t> d_index, d_hits;
+        DevMem<uint32_t> d_blk_last, d_blk_off, d_win;
+        DevMem<uint32_t> d_blk_hits, d_hdir; // where a directory row's hits start — LUCENE + hits.data: hit ordinal within the term
                                                            // (+ hdir: the 128-hit blocks of hits.data); GOOGLE: byte offset into index[]
         // GOOGLE: the document deltas of every block re-laid out as one contiguous stream per term ([n][n-1 prefix varints] per
         // block, bytes exactly as in the chunk) with its own offset column.  In the chunk a block's deltas are followed by its
         // freqs and hits, so a DocumentsOnly scan of a head term drags ~3x the bytes it decodes through HBM; the matching kernels
         // (k_and_dense, k_and) read this stream instead.  Scoring and phrases keep reading the chunk itself.
-        uint8_t *d_dstream = nullptr;
-        uint32_t *d_blk_doff = nullptr;
+        DevMem<uint8_t> d_dstream;
+        DevMem<uint32_t> d_blk_doff;
         // LUCENE: one 16-byte record per directory row (a quarter of a 128-document block, or a run of the varbyte tail) with all a lane
         // needs to address the row's payload in ONE load: {offset of the deltas group (tail: of the pairs), exception index, header word of
         // the deltas group, header word of the freqs group}.  Exception index = where THIS quarter's exceptions sit in the two groups'
         // lists: e0_deltas | cnt_deltas << 8 | e0_freqs << 16 | cnt_freqs << 24 (a lane patches its quarter without scanning the other
         // three's).  Header word = the group's first payload word (width | nexc << 8 | excwidth << 16), or bit 31 | value for an
         // all-equal group (k_fused.hpp PfRegs)
-        uint4 *d_blk_rec = nullptr;
-        uint32_t *d_masked = nullptr; // bitmap over docIDs of the masked documents (nullptr: none); max_doc / 32 + 2 words
-        DevTerm *d_terms = nullptr;
+        DevMem<uint4> d_blk_rec;
+        DevMem<uint32_t> d_masked; // bitmap over docIDs of the masked documents (nullptr: none); max_doc / 32 + 2 words
+        DevMem<DevTerm> d_terms;
         // ---- the term planes live with the index (they are a function of its lists alone): row r = the planes of the term of df rank r, built
         //      by k_term_planes the first time a batch's run wants them and kept — a caller that compiles a batch per step does not decode the
         //      same head terms step after step.  Two regions, built BY NEED (dev_structs.hpp: PL_HI): d_pcache holds every row's PLANE 0 (plw
@@ -321,51 +322,26 @@ struct tri_index : HostIndex {
         //      rows + one all-zero row (index pc_cap) in each region; pc_built[r]: bit 0 plane 0, bit 1 the high part, bit 2 the rank records — the build has been
         //      enqueued on the engine stream (every later kernel of the stream sees it).  Grown (rows moved on the upload stream) when a batch is
         //      planned with more eligible terms than it holds.
-        uint32_t *d_pcache = nullptr, *d_pcache_hi = nullptr;
+        Pooled<uint32_t> d_pcache, d_pcache_hi; // (pooled, like the four below: tri_batch_create grows them without a device-wide synchronisation)
         uint32_t pc_cap = 0, pc_plw = 0;
         std::vector<uint8_t> pc_built;
         // ... and what k_phrase needs to find a head term's hits WITHOUT walking its blocks (round 5): per row a RANK DIRECTORY over plane 0 — a 64-byte record per docID group g of 256 documents at d_prank[(row * (plw / 8) + g) * 16]:
         // the posting index of the group's first document and the group's eight plane-0 words, filled by k_term_planes —, and per posting the hits locator and frequency entry
         // phrase_locate_block would compute (d_phs[hs_off[row] + posting]; k_term_hits; GOOGLE, lists of full blocks).  d_term_row[term] = its row once both are there
-        uint32_t *d_prank = nullptr, *d_term_row = nullptr;
-        unsigned long long *d_phs = nullptr;
-        uint64_t *d_hs_off = nullptr;
-        uint32_t *d_ph_pairs = nullptr;   // (term, row) pairs of the rows whose hits entries were built, appended run after run (a row is built once: 2 * pc_cap words)
+        Pooled<uint32_t> d_prank;
+        DevMem<uint32_t> d_term_row;
+        Pooled<unsigned long long> d_phs;
+        Pooled<uint64_t> d_hs_off;
+        Pooled<uint32_t> d_ph_pairs;      // (term, row) pairs of the rows whose hits entries were built, appended run after run (a row is built once: 2 * pc_cap words)
         size_t ph_pairs_n = 0;
         std::vector<uint64_t> hs_off;     // [pc_cap + 1]: prefix sums of the rows' document counts (row = df rank)
         std::vector<uint8_t> ph_built;    // [pc_cap]: the row's hits entries have been enqueued
         std::vector<uint32_t> rank_term;  // [pc_cap]: the term of df rank r
-        hipEvent_t ev_pc_ready = nullptr;                       // the last growth's move of the rows (upload stream): every run waits for it
-        std::vector<std::pair<void *, hipEvent_t>> pc_retired; // outgrown row buffers and the engine-stream point their last readers precede
-        ~tri_index() { // also runs when tri_index_upload fails half-way
+        PooledEvent ev_pc_ready;                                // the last growth's move of the rows (upload stream): every run waits for it
+        std::vector<std::pair<Pooled<void>, PooledEvent>> pc_retired; // outgrown row buffers and the upload-stream point their last readers precede
+        ~tri_index() { // also runs when tri_index_upload fails half-way; the members release themselves behind it
                 if (dev)
                         hipSetDevice(dev->device);
-                hipFree(d_index);
-                hipFree(d_hits);
-                hipFree(d_blk_hits);
-                hipFree(d_hdir);
-                hipFree(d_dstream);
-                hipFree(d_blk_doff);
-                hipFree(d_blk_rec);
-                hipFree(d_masked);
-                hipFree(d_blk_last);
-                hipFree(d_blk_off);
-                hipFree(d_win);
-                hipFree(d_terms);
-                pool_free(dev, d_pcache); // (pooled: tri_batch_create grows it without a device-wide synchronisation)
-                pool_free(dev, d_pcache_hi);
-                pool_free(dev, d_prank);
-                pool_free(dev, d_phs);
-                pool_free(dev, d_hs_off);
-                pool_free(dev, d_ph_pairs);
-                hipFree(d_term_row);
-                for (auto &r : pc_retired) {
-                        pool_free(dev, r.first);
-                        hipEventDestroy(r.second);
-                }
-                if (ev_pc_ready)
-                        hipEventDestroy(ev_pc_ready);
-                dev_release(dev);
         }
 };
 
@@ -373,15 +349,13 @@ struct tri_index : HostIndex {
 // extent of d_masked (filter_words).  It belongs to its index — destroyed before it, like a batch — and is only read by the batches that name it
 // (tri_batch_set_filters): their runs OR it with the mask of the moment into a row of their own (k_filter.hpp)
 struct tri_filter {
+        DevRef dev; // (first: released last)
         tri_index *ix = nullptr;
-        tri_dev *dev = nullptr;
-        uint32_t *d_bits = nullptr;
+        Pooled<uint32_t> d_bits;
         size_t words = 0;
         ~tri_filter() {
                 if (dev)
                         hipSetDevice(dev->device);
-                pool_free(dev, d_bits);
-                dev_release(dev);
         }
 };
 // whole docID windows (the bitmap kernels read a window's worth of words at a time), one spare window: the extent of d_masked and of every filter
@@ -394,13 +368,44 @@ enum BatchEvent { EV_UP, EV_START, EV_PLANE_ROWS, EV_DENSE, EV_PSET, EV_PROBE, E
 // a compiled batch: the plan (BatchPlan: the host block with every array the kernels read, laid out by the planner) and its device side —
 // ONE arena that holds the block's copy followed by the batch's small device-only arrays, plus the large pooled buffers
 struct tri_batch : BatchPlan {
+        DevRef dev; // FIRST: members go in reverse order of declaration, so the handle is let go of after every buffer and event below went back to it
         tri_index *ix = nullptr;
-        tri_dev *dev = nullptr;
         uint32_t flags, topk;
         int similarity = TRI_SIM_BM25;
         size_t nq;
-        size_t block_cap = 0;       // size of the pinned host block (BatchPlan::block) as the pool knows it
-        uint8_t *d_arena = nullptr; // [copy of block][counts][ticket][qthr][part_counts][task_hits][task_pos_base] [zeroed at creation: qcounts, top_counts, top_docs, top_scores]
+        // ---- what the batch OWNS: each member releases itself (owners.hpp), behind ~tri_batch's waits
+        Pinned<uint8_t> pinned;   // the pinned host block BatchPlan::block points at
+        Pooled<uint8_t> d_arena;  // [copy of block], then batch_arena()'s sections: the run's small arrays, and last the ones zeroed at creation
+        PooledEvent ev[EV_COUNT]; // (owned by the batch: two batches in flight on one device keep their own timings)
+        Pooled<uint32_t> d_sparse; // k_planes: per resident workgroup, the lists of a task's decoded (non-plane) slots
+        Pooled<uint32_t> d_out;
+        Pooled<uint32_t> d_rich_allow; // default mode, batches that hold general trees: per match the reportable terms the tree sits on
+        DevMem<uint64_t> d_hashes;
+        // AccumulatedScoreScheme
+        Pooled<uint32_t> d_part_docs;
+        Pooled<double> d_part_scores, d_all_scores; // (d_all_scores: topk == 0, one double per out[] slot)
+        // TRI_FLAG_MATCHED_TERMS (k_rich.hpp): sterms[] holds every query's reportable terms; R = the widest query's count
+        Pooled<uint32_t> d_rich_present;
+        Pooled<uint16_t> d_rich_freq;
+        // ... with wide-report queries (option rich_max_terms; BatchPlan::rich_wide says where a query's share of each lies): their frequency rows, and the high
+        // halves of their matches' present / allow masks — d_rich_present / d_rich_allow keep the low halves of every query, laid out as ever
+        Pooled<uint16_t> d_rich_freq_wide;
+        Pooled<uint32_t> d_rich_present_hi, d_rich_allow_hi;
+        DevMem<uint16_t> d_rich_pool;
+        DevMem<uint8_t> d_rich_plen;     // TRI_FLAG_HIT_PAYLOADS: per hit of the pool, term_hit::payloadLen ...
+        DevMem<uint64_t> d_rich_payload; // ... and term_hit::payload
+        Pooled<double> d_pscore; // phrases, per out[] slot: sum of the phrase scores of the match (scored mode)
+        // TASK_TREE (k_tree.hpp): one scratch block — [tree rows: a PL_PLANES-plane row per distinct term leaf][phrase rows: a plane per hidden phrase query]
+        // [a match bitmap per tree query][per query and chunk: matches][(term, row) pairs for k_term_planes]
+        Pooled<uint32_t> d_tree_scratch;
+        Pooled<double> d_tree_scores; // scored top-K batches: the tree queries' score stream (topk == 0: d_all_scores holds it)
+        Pooled<uint32_t> d_scat_docs; // PSET_UNIT_SCATTER unions: the list k_psets_prep makes (k_psets.hpp)
+        // per-query filters (tri_batch_set_filters; stored by reference): filter_rows[r - 1] = the filter behind row id r — the filters at least one query
+        // names —, d_filter_tab = [row id per plan slot][the rows' source pointers], d_filter_rows = the rows every run rebuilds (filter | mask)
+        Pooled<uint8_t> d_filter_tab;
+        Pooled<uint32_t> d_filter_rows;
+        Pooled<uint8_t> d_rank_block; // tri_batch_set_ranker (k_rich_rank.hpp): ONE block, rank_block()'s sections
+        // ---- VIEWS: plain pointers into the buffers above, released with them
         // a section of the plan (a Span of BatchPlan: planner_types.hpp, for_each_section) on the device — the block's copy opens the arena
         template <class T>
         T *dev_at(const Span<T> &s) const {
@@ -410,102 +415,50 @@ struct tri_batch : BatchPlan {
         T *dev_opt(const Span<T> &s) const { // ... one that a batch may lack (qplane, splane): nullptr tells the kernels so
                 return s.empty() ? nullptr : dev_at(s);
         }
+        // into d_arena (batch_arena)
+        uint32_t *d_counts = nullptr; // per task, indexed first_task + i in query order
+        uint32_t *d_ticket = nullptr;
         uint32_t *d_build = nullptr; // (term, row) pairs of the plane rows a run has to build first
         unsigned long long *d_qthr = nullptr; // k_planes: per query, the best k-th score any of its tasks has seen (cleared at every run)
-        uint32_t *d_sparse = nullptr;      // k_planes: per resident workgroup, the lists of a task's decoded (non-plane) slots
-        hipEvent_t ev[EV_COUNT] = {}; // (owned by the batch: two batches in flight on one device keep their own timings)
-        // TASK_TREE (k_tree.hpp): one scratch block — [tree rows: a PL_PLANES-plane row per distinct term leaf][phrase rows: a plane per hidden phrase query]
-        // [a match bitmap per tree query][per query and chunk: matches][(term, row) pairs for k_term_planes]
-        uint32_t *d_tree_scratch = nullptr, *d_tree_rows = nullptr, *d_tree_prows = nullptr, *d_tree_qbits = nullptr, *d_tree_cc = nullptr, *d_tree_build = nullptr;
-        double *d_tree_scores = nullptr; // scored top-K batches: the tree queries' score stream (topk == 0: d_all_scores holds it)
+        uint32_t *d_part_counts = nullptr;
         uint32_t *d_score_order = nullptr; // AccumulatedScore: the tasks k_score runs, heaviest first by their match counts (k_score_order)
+        uint32_t *d_task_hits = nullptr;
+        uint64_t *d_task_pos_base = nullptr;
+        uint32_t *d_scat_off = nullptr, *d_scat_cnt = nullptr; // PSET_UNIT_SCATTER unions: per task its slice of d_scat_docs
         uint32_t *d_scat_list = nullptr; // ... the scatter queries' first units (k_psets_prep_list)
-        uint32_t *d_scat_off = nullptr, *d_scat_cnt = nullptr, *d_scat_docs = nullptr; // PSET_UNIT_SCATTER unions: per task its slice of the list k_psets_prep makes (k_psets.hpp)
+        uint64_t *d_qcounts = nullptr; // per caller query: matches of the last run (device copy for the result gather)
+        uint32_t *d_top_counts = nullptr, *d_top_docs = nullptr;
+        float *d_top_scores = nullptr;
+        // into d_tree_scratch (tree_scratch)
+        uint32_t *d_tree_rows = nullptr, *d_tree_prows = nullptr, *d_tree_qbits = nullptr, *d_tree_cc = nullptr, *d_tree_build = nullptr;
+        // into d_rank_block (rank_block): [a weight per sterms[] entry][the tasks' partial lists][the queries' ranked lists]
+        double *d_rank_w = nullptr, *d_rank_part_scores = nullptr, *d_rank_scores = nullptr;
+        uint32_t *d_rank_part_docs = nullptr, *d_rank_part_counts = nullptr, *d_rank_docs = nullptr, *d_rank_counts = nullptr;
+        // ---- host state
         uint32_t scat_cap = 0;
         bool ran = false;
         bool planes_hi = false; // the batch reads the HIGH parts of its plane rows (k_planes, k_score's level words): its run builds them where they are missing
-        uint32_t *d_out = nullptr;
-        uint32_t *d_counts = nullptr; // per task, indexed first_task + i in query order
-        uint32_t *d_ticket = nullptr;
-        uint32_t *d_rich_allow = nullptr; // default mode, batches that hold general trees: per match the reportable terms the tree sits on
-        uint64_t *d_hashes = nullptr;
-        uint64_t *d_qcounts = nullptr; // per caller query: matches of the last run (device copy for the result gather)
-        // AccumulatedScoreScheme
-        uint32_t *d_part_docs = nullptr, *d_part_counts = nullptr, *d_top_docs = nullptr, *d_top_counts = nullptr;
-        double *d_part_scores = nullptr;
-        float *d_top_scores = nullptr;
-        double *d_all_scores = nullptr; // topk == 0: one double per out[] slot
-        // TRI_FLAG_MATCHED_TERMS (k_rich.hpp): sterms[] holds every query's reportable terms; R = the widest query's count
-        uint32_t *d_rich_present = nullptr, *d_task_hits = nullptr;
-        uint16_t *d_rich_freq = nullptr, *d_rich_pool = nullptr;
-        // ... with wide-report queries (option rich_max_terms; BatchPlan::rich_wide says where a query's share of each lies): their frequency rows, and the high
-        // halves of their matches' present / allow masks — d_rich_present / d_rich_allow keep the low halves of every query, laid out as ever
-        uint16_t *d_rich_freq_wide = nullptr;
-        uint32_t *d_rich_present_hi = nullptr, *d_rich_allow_hi = nullptr;
-        uint8_t *d_rich_plen = nullptr;     // TRI_FLAG_HIT_PAYLOADS: per hit of the pool, term_hit::payloadLen ...
-        uint64_t *d_rich_payload = nullptr; // ... and term_hit::payload
-        uint64_t *d_task_pos_base = nullptr;
         std::vector<uint64_t> h_task_pos_base; // per task; [ntasks] = the pool's size
         size_t rich_pool_cap = 0;
-        // phrases
-        double *d_pscore = nullptr; // per out[] slot: sum of the phrase scores of the match (scored mode)
         std::vector<uint32_t> h_counts;       // per task
         std::vector<uint64_t> h_query_counts; // per plan slot
         bool synced = false;
-        // per-query filters (tri_batch_set_filters; stored by reference): filter_rows[r - 1] = the filter behind row id r — the filters at least one query
-        // names —, d_filter_tab = [row id per plan slot][the rows' source pointers], d_filter_rows = the rows every run rebuilds (filter | mask)
         std::vector<const tri_filter *> filter_rows;
-        uint8_t *d_filter_tab = nullptr;
-        uint32_t *d_filter_rows = nullptr;
         size_t filter_rows_cap = 0; // rows d_filter_rows holds
-        // tri_batch_set_ranker (k_rich_rank.hpp): the spec, ONE pooled block — [a weight per sterms[] entry][the tasks' partial lists][the queries' ranked lists] —
-        // and the caller's program (kept by default-mode batches: the ranker's weights come one per program token)
+        // tri_batch_set_ranker: the spec, and the caller's program (kept by default-mode batches: the ranker's weights come one per program token)
         bool rank_on = false, rank_done = false;
         tri_ranker rank{};
-        uint8_t *d_rank_block = nullptr;
-        double *d_rank_w = nullptr, *d_rank_part_scores = nullptr, *d_rank_scores = nullptr;
-        uint32_t *d_rank_part_docs = nullptr, *d_rank_part_counts = nullptr, *d_rank_docs = nullptr, *d_rank_counts = nullptr;
         std::vector<uint32_t> h_prog;
         std::vector<tri_query> h_queries;
         tri_batch_info info{};
-        ~tri_batch() { // also runs when tri_batch_create fails half-way: nothing allocated so far is leaked
-                if (dev) {
-                        hipSetDevice(dev->device);
-                        if (ran && !synced) // (its large buffers go back to the device's pool: nothing of this batch may still be running on them)
-                                hipStreamSynchronize(dev->stream);
-                        if (ev[EV_UP])
-                                hipEventSynchronize(ev[EV_UP]); // (the pinned block goes back to the pool: its copy must have left)
-                }
-                for (hipEvent_t e : ev)
-                        if (dev)
-                                event_put(dev, e);
-                        else if (e)
-                                hipEventDestroy(e);
-                pinned_free(dev, block, block_cap);
-                pool_free(dev, d_arena);
-                pool_free(dev, d_sparse);
-                pool_free(dev, d_out);
-                pool_free(dev, d_rich_allow);
-                hipFree(d_hashes);
-                pool_free(dev, d_part_docs);
-                pool_free(dev, d_part_scores);
-                pool_free(dev, d_all_scores);
-                pool_free(dev, d_rich_present);
-                pool_free(dev, d_rich_freq);
-                pool_free(dev, d_rich_freq_wide);
-                pool_free(dev, d_rich_present_hi);
-                pool_free(dev, d_rich_allow_hi);
-                hipFree(d_rich_pool);
-                hipFree(d_rich_plen);
-                hipFree(d_rich_payload);
-                pool_free(dev, d_pscore);
-                pool_free(dev, d_tree_scratch);
-                pool_free(dev, d_tree_scores);
-                pool_free(dev, d_scat_docs);
-                pool_free(dev, d_filter_tab);
-                pool_free(dev, d_filter_rows);
-                pool_free(dev, d_rank_block);
-                dev_release(dev);
+        ~tri_batch() { // also runs when tri_batch_create fails half-way.  Only the waits stand here: they come before any member is released
+                if (!dev)
+                        return;
+                hipSetDevice(dev->device);
+                if (ran && !synced) // (its large buffers go back to the device's pool: nothing of this batch may still be running on them)
+                        hipStreamSynchronize(dev->stream);
+                if (ev[EV_UP])
+                        hipEventSynchronize(ev[EV_UP]); // (the pinned block goes back to the pool: its copy must have left)
         }
 };
 
@@ -531,13 +484,14 @@ struct tri_batch : BatchPlan {
 #include "filtered_kernels.hpp"
 
 // launch the instantiation of a codec-templated kernel that matches the uploaded segment: `pick` maps the codec (a std::integral_constant: the
-// kernel template's first argument) to the kernel, and chooses the template's other arguments, if it has any
+// kernel template's first argument) to the kernel, and chooses the template's other arguments, if it has any.  The arguments are forwarded: an owner
+// (owners.hpp) becomes the kernel's pointer at the kernel call
 template <class Pick, class... Args>
-static void tri_launch(const int codec, Pick pick, const dim3 grid, const dim3 block, const hipStream_t stream, Args... args) {
+static void tri_launch(const int codec, Pick pick, const dim3 grid, const dim3 block, const hipStream_t stream, Args &&...args) {
         if (codec == TRI_CODEC_LUCENE)
-                hipLaunchKernelGGL(pick(std::integral_constant<int, CODEC_LUCENE>()), grid, block, 0, stream, args...);
+                hipLaunchKernelGGL(pick(std::integral_constant<int, CODEC_LUCENE>()), grid, block, 0, stream, std::forward<Args>(args)...);
         else
-                hipLaunchKernelGGL(pick(std::integral_constant<int, CODEC_GOOGLE>()), grid, block, 0, stream, args...);
+                hipLaunchKernelGGL(pick(std::integral_constant<int, CODEC_GOOGLE>()), grid, block, 0, stream, std::forward<Args>(args)...);
 }
 // ... of a kernel whose only template argument is the codec
 #define TRI_LAUNCH(K, codec, grid, block, stream, ...) tri_launch(codec, [](auto c_) { return K<c_.value>; }, grid, block, stream, __VA_ARGS__)
@@ -670,10 +624,10 @@ extern "C" void *tri_dev_stream(tri_dev *d) { return d ? (void *)d->stream : nul
 // ------------------------------------------------------------------------------------------ host: upload
 namespace {
         template <class T>
-        int dev_upload(T **dst, const std::vector<T> &src, size_t extra = 0) {
-                HIP_TRY(hipMalloc((void **)dst, (src.size() + extra) * sizeof(T) + 16));
+        int dev_upload(DevMem<T> &dst, const std::vector<T> &src, size_t extra = 0) {
+                HIP_TRY(dst.alloc((src.size() + extra) * sizeof(T) + 16));
                 if (!src.empty())
-                        HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+                        HIP_TRY(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
                 return TRI_OK;
         }
 } // namespace
@@ -691,8 +645,7 @@ extern "C" int tri_index_upload(tri_dev *dev, const uint8_t *index, size_t len, 
                 if (const int rc = build_host_index(index, len, hits, hits_len, codec, terms, nterms, docs_cnt, *ix, err))
                         return fail(rc, "%s", err.c_str());
         }
-        ix->dev = dev;
-        dev_retain(dev);
+        ix->dev.retain(dev);
         if (!ix->dev_index.empty()) { // a LUCENE segment with FastPFor<4> payload words: the device gets its PFOR128 transcription (index_host.hpp)
                 index = ix->dev_index.data();
                 len = ix->dev_index.size();
@@ -701,33 +654,33 @@ extern "C" int tri_index_upload(tri_dev *dev, const uint8_t *index, size_t len, 
         }
         // device copies
         int rc;
-        if ((rc = dev_upload(&ix->d_win, ix->win, 3 * CELLS_PER_SPAN + 8))) // (lanes of terms without a row read entries 0, CELLS_PER_SPAN, 2 * CELLS_PER_SPAN and drop them)
+        if ((rc = dev_upload(ix->d_win, ix->win, 3 * CELLS_PER_SPAN + 8))) // (lanes of terms without a row read entries 0, CELLS_PER_SPAN, 2 * CELLS_PER_SPAN and drop them)
                 return rc;
         HIP_TRY(hipMemset(ix->d_win + ix->win.size(), 0, (3 * CELLS_PER_SPAN + 8) * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void **)&ix->d_index, len + 256)); // over-read slack: the byte streams keep several qwords in flight past the cursor
+        HIP_TRY(ix->d_index.alloc(len + 256)); // over-read slack: the byte streams keep several qwords in flight past the cursor
         HIP_TRY(hipMemset(ix->d_index, 0, len + 256));
         if (len)
                 HIP_TRY(hipMemcpy(ix->d_index, index, len, hipMemcpyHostToDevice));
-        if ((rc = dev_upload(&ix->d_blk_last, ix->blk_last)) || (rc = dev_upload(&ix->d_blk_off, ix->blk_off)) || (rc = dev_upload(&ix->d_terms, ix->terms)))
+        if ((rc = dev_upload(ix->d_blk_last, ix->blk_last)) || (rc = dev_upload(ix->d_blk_off, ix->blk_off)) || (rc = dev_upload(ix->d_terms, ix->terms)))
                 return rc;
         if (codec == TRI_CODEC_GOOGLE) {
                 ix->blk_doff.push_back((uint32_t)ix->dstream.size() + 1); // (sentinel: block b's delta bytes = blk_doff[b + 1] - blk_doff[b] - 1 for the last block too)
                 ix->dstream.resize(ix->dstream.size() + 256, 0); // over-read slack, like index[]
-                if ((rc = dev_upload(&ix->d_dstream, ix->dstream)) || (rc = dev_upload(&ix->d_blk_doff, ix->blk_doff)))
+                if ((rc = dev_upload(ix->d_dstream, ix->dstream)) || (rc = dev_upload(ix->d_blk_doff, ix->blk_doff)))
                         return rc;
         }
         if (hits_len) { // LUCENE: hits.data (positions) resident next to the index
-                HIP_TRY(hipMalloc((void **)&ix->d_hits, hits_len + 256));
+                HIP_TRY(ix->d_hits.alloc(hits_len + 256));
                 HIP_TRY(hipMemset(ix->d_hits, 0, hits_len + 256));
                 HIP_TRY(hipMemcpy(ix->d_hits, hits, hits_len, hipMemcpyHostToDevice));
-                if (ix->has_hdir && ((rc = dev_upload(&ix->d_blk_hits, ix->blk_hits)) || (rc = dev_upload(&ix->d_hdir, ix->hdir))))
+                if (ix->has_hdir && ((rc = dev_upload(ix->d_blk_hits, ix->blk_hits)) || (rc = dev_upload(ix->d_hdir, ix->hdir))))
                         return rc;
         }
-        if (codec == TRI_CODEC_GOOGLE && (rc = dev_upload(&ix->d_blk_hits, ix->blk_hits)))
+        if (codec == TRI_CODEC_GOOGLE && (rc = dev_upload(ix->d_blk_hits, ix->blk_hits)))
                 return rc;
         if (codec == TRI_CODEC_LUCENE) {
                 static_assert(sizeof(RowRec) == sizeof(uint4), "row records are read as uint4");
-                HIP_TRY(hipMalloc((void **)&ix->d_blk_rec, ix->blk_rec.size() * sizeof(uint4) + 16));
+                HIP_TRY(ix->d_blk_rec.alloc(ix->blk_rec.size() * sizeof(uint4) + 16));
                 if (!ix->blk_rec.empty())
                         HIP_TRY(hipMemcpy(ix->d_blk_rec, ix->blk_rec.data(), ix->blk_rec.size() * sizeof(uint4), hipMemcpyHostToDevice));
         }
@@ -743,8 +696,7 @@ extern "C" int tri_index_set_masked(tri_index *ix, const uint32_t *docids, size_
         HIP_TRY(hipSetDevice(ix->dev->device));
         HIP_TRY(hipStreamSynchronize(ix->dev->stream)); // no batch of this device is reading the old bitmap
         if (!n) {
-                hipFree(ix->d_masked);
-                ix->d_masked = nullptr;
+                ix->d_masked.reset();
                 return TRI_OK;
         }
         // whole docID windows (the bitmap kernel reads a window's worth of words at a time), one spare window
@@ -754,13 +706,13 @@ extern "C" int tri_index_set_masked(tri_index *ix, const uint32_t *docids, size_
                 if (docids[i] <= ix->max_doc) // a document this segment does not hold cannot match anyway
                         bm[docids[i] >> 5] |= 1u << (docids[i] & 31);
         if (!ix->d_masked)
-                HIP_TRY(hipMalloc((void **)&ix->d_masked, words * 4));
+                HIP_TRY(ix->d_masked.alloc(words * 4));
         HIP_TRY(hipMemcpy(ix->d_masked, bm.data(), words * 4, hipMemcpyHostToDevice));
         return TRI_OK;
 }
 
 extern "C" void tri_index_destroy(tri_index *ix) {
-        delete ix; // ~tri_index releases the device buffers
+        delete ix; // its members release the device buffers
 }
 
 extern "C" int tri_index_get_info(const tri_index *ix, tri_index_info *info) {
@@ -800,14 +752,13 @@ extern "C" int tri_decode_terms(tri_index *ix, const uint32_t *terms, size_t n, 
         out_offsets[n] = tot;
         if (!tot || !docs)
                 return TRI_OK;
-        DevBuf jobs_buf, docs_buf, freqs_buf;
-        HIP_TRY(hipMalloc(&jobs_buf.p, n * sizeof(DecodeJob)));
-        HIP_TRY(hipMemcpyAsync(jobs_buf.p, jobs.data(), n * sizeof(DecodeJob), hipMemcpyHostToDevice, dev->stream));
-        HIP_TRY(hipMalloc(&docs_buf.p, padded * 4));
+        DevMem<DecodeJob> d_jobs; // (of this call: not pooled)
+        DevMem<uint32_t> d_docs, d_freqs;
+        HIP_TRY(d_jobs.alloc(n * sizeof(DecodeJob)));
+        HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), n * sizeof(DecodeJob), hipMemcpyHostToDevice, dev->stream));
+        HIP_TRY(d_docs.alloc(padded * 4));
         if (freqs)
-                HIP_TRY(hipMalloc(&freqs_buf.p, padded * 4));
-        DecodeJob *d_jobs = jobs_buf.as<DecodeJob>();
-        uint32_t *d_docs = docs_buf.as<uint32_t>(), *d_freqs = freqs_buf.as<uint32_t>();
+                HIP_TRY(d_freqs.alloc(padded * 4));
         dim3 grid(std::min<uint32_t>((maxblocks + 255) / 256, 4096), (uint32_t)n);
         TRI_LAUNCH(k_decode_terms, ix->codec, grid, dim3(256), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_terms, d_jobs, d_docs,
                            d_freqs);
@@ -838,12 +789,12 @@ namespace {
                 return TRI_OK;
         }
         // the three output columns of `tot` hits on the device -> the caller's buffers
-        int decode_hits_fetch(tri_dev *dev, const uint64_t tot, const DevBuf &d_pos, const DevBuf &d_len, const DevBuf &d_pay, uint16_t *positions, uint8_t *payload_lens, uint64_t *payloads) {
+        int decode_hits_fetch(tri_dev *dev, const uint64_t tot, const uint16_t *d_pos, const uint8_t *d_len, const uint64_t *d_pay, uint16_t *positions, uint8_t *payload_lens, uint64_t *payloads) {
                 HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(positions, d_pos.p, tot * 2, hipMemcpyDeviceToHost, dev->stream));
+                HIP_TRY(hipMemcpyAsync(positions, d_pos, tot * 2, hipMemcpyDeviceToHost, dev->stream));
                 if (payload_lens) {
-                        HIP_TRY(hipMemcpyAsync(payload_lens, d_len.p, tot, hipMemcpyDeviceToHost, dev->stream));
-                        HIP_TRY(hipMemcpyAsync(payloads, d_pay.p, tot * 8, hipMemcpyDeviceToHost, dev->stream));
+                        HIP_TRY(hipMemcpyAsync(payload_lens, d_len, tot, hipMemcpyDeviceToHost, dev->stream));
+                        HIP_TRY(hipMemcpyAsync(payloads, d_pay, tot * 8, hipMemcpyDeviceToHost, dev->stream));
                 }
                 HIP_TRY(hipStreamSynchronize(dev->stream));
                 return TRI_OK;
@@ -870,23 +821,26 @@ extern "C" int tri_decode_hits(tri_index *ix, const uint32_t *terms, size_t n, u
                 maxblocks = std::max(maxblocks, t.nblocks);
         }
         const bool google = ix->codec == TRI_CODEC_GOOGLE;
-        DevBuf d_jobs, d_totals, d_cnt, d_pos, d_len, d_pay;
+        DevMem<HitsJob> d_jobs;
+        DevMem<uint64_t> d_totals, d_cnt, d_pay;
+        DevMem<uint16_t> d_pos;
+        DevMem<uint8_t> d_len;
         const uint32_t nj = (uint32_t)n, gy = std::min<uint32_t>(nj, 32768), gx = std::min<uint32_t>((maxblocks + 255) / 256, 4096);
         if (nblk) {
                 // pass 1: hits per block (GOOGLE) and per job
-                HIP_TRY(hipMalloc(&d_jobs.p, n * sizeof(HitsJob)));
-                HIP_TRY(hipMalloc(&d_totals.p, n * 8));
-                HIP_TRY(hipMemcpyAsync(d_jobs.p, jobs.data(), n * sizeof(HitsJob), hipMemcpyHostToDevice, dev->stream));
-                HIP_TRY(hipMemsetAsync(d_totals.p, 0, n * 8, dev->stream));
+                HIP_TRY(d_jobs.alloc(n * sizeof(HitsJob)));
+                HIP_TRY(d_totals.alloc(n * 8));
+                HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), n * sizeof(HitsJob), hipMemcpyHostToDevice, dev->stream));
+                HIP_TRY(hipMemsetAsync(d_totals, 0, n * 8, dev->stream));
                 if (google)
-                        HIP_TRY(hipMalloc(&d_cnt.p, nblk * 8));
+                        HIP_TRY(d_cnt.alloc(nblk * 8));
                 TRI_LAUNCH(k_hits_count, ix->codec, google ? dim3(gx, gy) : dim3(1, gy), dim3(google ? 256 : 64), dev->stream, (const uint8_t *)ix->d_index, (const uint32_t *)ix->d_blk_off,
-                           (const uint32_t *)ix->d_blk_hits, (const DevTerm *)ix->d_terms, (const HitsJob *)d_jobs.as<HitsJob>(), nj, d_cnt.as<uint64_t>(), d_totals.as<uint64_t>());
+                           (const uint32_t *)ix->d_blk_hits, (const DevTerm *)ix->d_terms, (const HitsJob *)d_jobs, nj, d_cnt, d_totals);
                 if (google)
-                        hipLaunchKernelGGL(k_hits_scan, dim3(std::min<uint32_t>(nj, 4096)), dim3(256), 0, dev->stream, (const DevTerm *)ix->d_terms, (const HitsJob *)d_jobs.as<HitsJob>(), nj,
-                                           d_cnt.as<uint64_t>(), d_totals.as<uint64_t>());
+                        hipLaunchKernelGGL(k_hits_scan, dim3(std::min<uint32_t>(nj, 4096)), dim3(256), 0, dev->stream, (const DevTerm *)ix->d_terms, (const HitsJob *)d_jobs, nj,
+                                           d_cnt, d_totals);
                 HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(totals.data(), d_totals.p, n * 8, hipMemcpyDeviceToHost, dev->stream));
+                HIP_TRY(hipMemcpyAsync(totals.data(), d_totals, n * 8, hipMemcpyDeviceToHost, dev->stream));
                 HIP_TRY(hipStreamSynchronize(dev->stream));
         }
         for (size_t i = 0; i < n; ++i) {
@@ -900,15 +854,15 @@ extern "C" int tri_decode_hits(tri_index *ix, const uint32_t *terms, size_t n, u
         if (!positions || !tot)
                 return TRI_OK;
         // pass 2: the hits
-        HIP_TRY(hipMemcpyAsync(d_jobs.p, jobs.data(), n * sizeof(HitsJob), hipMemcpyHostToDevice, dev->stream));
-        HIP_TRY(hipMalloc(&d_pos.p, tot * 2 + 64));
+        HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), n * sizeof(HitsJob), hipMemcpyHostToDevice, dev->stream));
+        HIP_TRY(d_pos.alloc(tot * 2 + 64));
         if (payload_lens) {
-                HIP_TRY(hipMalloc(&d_len.p, tot + 64));
-                HIP_TRY(hipMalloc(&d_pay.p, tot * 8 + 64));
+                HIP_TRY(d_len.alloc(tot + 64));
+                HIP_TRY(d_pay.alloc(tot * 8 + 64));
         }
         TRI_LAUNCH(k_decode_hits, ix->codec, dim3(gx, gy), dim3(256), dev->stream, (const uint8_t *)ix->d_index, (const uint8_t *)ix->d_hits, (const uint32_t *)ix->d_blk_off,
-                   (const uint32_t *)ix->d_blk_hits, (const uint32_t *)ix->d_hdir, (const DevTerm *)ix->d_terms, (const HitsJob *)d_jobs.as<HitsJob>(), nj,
-                   (const uint64_t *)d_cnt.as<uint64_t>(), d_pos.as<uint16_t>(), d_len.as<uint8_t>(), d_pay.as<uint64_t>());
+                   (const uint32_t *)ix->d_blk_hits, (const uint32_t *)ix->d_hdir, (const DevTerm *)ix->d_terms, (const HitsJob *)d_jobs, nj,
+                   (const uint64_t *)d_cnt, d_pos, d_len, d_pay);
         return decode_hits_fetch(dev, tot, d_pos, d_len, d_pay, positions, payload_lens, payloads);
 }
 
@@ -928,19 +882,22 @@ extern "C" int tri_decode_hits_at(tri_index *ix, const uint32_t *terms, const ui
         HIP_TRY(hipSetDevice(dev->device));
         const uint32_t np = (uint32_t)n;
         const dim3 grid((np + 255) / 256);
-        DevBuf d_terms, d_docs, d_freqs, d_loc, d_off, d_pos, d_len, d_pay;
-        HIP_TRY(hipMalloc(&d_terms.p, n * 4));
-        HIP_TRY(hipMalloc(&d_docs.p, n * 4));
-        HIP_TRY(hipMalloc(&d_freqs.p, n * 4));
-        HIP_TRY(hipMalloc(&d_loc.p, n * 12)); // block, slot, hits of the block before the document
-        HIP_TRY(hipMemcpyAsync(d_terms.p, terms, n * 4, hipMemcpyHostToDevice, dev->stream));
-        HIP_TRY(hipMemcpyAsync(d_docs.p, docids, n * 4, hipMemcpyHostToDevice, dev->stream));
-        uint32_t *at_block = d_loc.as<uint32_t>(), *at_slot = at_block + n, *at_before = at_slot + n;
+        DevMem<uint32_t> d_terms, d_docs, d_freqs, d_loc;
+        DevMem<uint64_t> d_off, d_pay;
+        DevMem<uint16_t> d_pos;
+        DevMem<uint8_t> d_len;
+        HIP_TRY(d_terms.alloc(n * 4));
+        HIP_TRY(d_docs.alloc(n * 4));
+        HIP_TRY(d_freqs.alloc(n * 4));
+        HIP_TRY(d_loc.alloc(n * 12)); // block, slot, hits of the block before the document
+        HIP_TRY(hipMemcpyAsync(d_terms, terms, n * 4, hipMemcpyHostToDevice, dev->stream));
+        HIP_TRY(hipMemcpyAsync(d_docs, docids, n * 4, hipMemcpyHostToDevice, dev->stream));
+        uint32_t *at_block = d_loc, *at_slot = at_block + n, *at_before = at_slot + n;
         TRI_LAUNCH(k_hits_at_freq, ix->codec, grid, dim3(256), dev->stream, (const uint8_t *)ix->d_index, (const uint32_t *)ix->d_blk_last, (const uint32_t *)ix->d_blk_off,
-                   (const DevTerm *)ix->d_terms, (const uint32_t *)d_terms.as<uint32_t>(), (const uint32_t *)d_docs.as<uint32_t>(), np, d_freqs.as<uint32_t>(), at_block, at_slot, at_before);
+                   (const DevTerm *)ix->d_terms, (const uint32_t *)d_terms, (const uint32_t *)d_docs, np, d_freqs, at_block, at_slot, at_before);
         HIP_TRY(hipGetLastError());
         std::vector<uint32_t> fr(n);
-        HIP_TRY(hipMemcpyAsync(fr.data(), d_freqs.p, n * 4, hipMemcpyDeviceToHost, dev->stream));
+        HIP_TRY(hipMemcpyAsync(fr.data(), d_freqs, n * 4, hipMemcpyDeviceToHost, dev->stream));
         HIP_TRY(hipStreamSynchronize(dev->stream));
         std::vector<uint64_t> offs(n + 1, 0);
         for (size_t i = 0; i < n; ++i)
@@ -952,17 +909,17 @@ extern "C" int tri_decode_hits_at(tri_index *ix, const uint32_t *terms, const ui
         std::copy(offs.begin(), offs.end(), out_offsets);
         if (!positions || !tot)
                 return TRI_OK;
-        HIP_TRY(hipMalloc(&d_off.p, n * 8));
-        HIP_TRY(hipMemcpyAsync(d_off.p, offs.data(), n * 8, hipMemcpyHostToDevice, dev->stream));
-        HIP_TRY(hipMalloc(&d_pos.p, tot * 2 + 64));
+        HIP_TRY(d_off.alloc(n * 8));
+        HIP_TRY(hipMemcpyAsync(d_off, offs.data(), n * 8, hipMemcpyHostToDevice, dev->stream));
+        HIP_TRY(d_pos.alloc(tot * 2 + 64));
         if (payload_lens) {
-                HIP_TRY(hipMalloc(&d_len.p, tot + 64));
-                HIP_TRY(hipMalloc(&d_pay.p, tot * 8 + 64));
+                HIP_TRY(d_len.alloc(tot + 64));
+                HIP_TRY(d_pay.alloc(tot * 8 + 64));
         }
         TRI_LAUNCH(k_hits_at_write, ix->codec, grid, dim3(256), dev->stream, (const uint8_t *)ix->d_index, (const uint8_t *)ix->d_hits, (const uint32_t *)ix->d_blk_off,
-                   (const uint32_t *)ix->d_blk_hits, (const uint32_t *)ix->d_hdir, (const DevTerm *)ix->d_terms, (const uint32_t *)d_terms.as<uint32_t>(), np,
-                   (const uint32_t *)d_freqs.as<uint32_t>(), (const uint32_t *)at_block, (const uint32_t *)at_slot, (const uint32_t *)at_before, (const uint64_t *)d_off.as<uint64_t>(),
-                   d_pos.as<uint16_t>(), d_len.as<uint8_t>(), d_pay.as<uint64_t>());
+                   (const uint32_t *)ix->d_blk_hits, (const uint32_t *)ix->d_hdir, (const DevTerm *)ix->d_terms, (const uint32_t *)d_terms, np,
+                   (const uint32_t *)d_freqs, (const uint32_t *)at_block, (const uint32_t *)at_slot, (const uint32_t *)at_before, (const uint64_t *)d_off,
+                   d_pos, d_len, d_pay);
         return decode_hits_fetch(dev, tot, d_pos, d_len, d_pay, positions, payload_lens, payloads);
 }
 
@@ -972,18 +929,17 @@ extern "C" int tri_decode_hits_at(tri_index *ix, const uint32_t *terms, const ui
 // it here: a stall in the serving loop whenever a batch was planned with more eligible terms): the rows move on the upload stream behind
 // everything the engine stream holds so far (runs that read or build the old rows), later runs wait for the move's event (tri_batch_run),
 // and the old buffers are retired — pooled again once that point has passed.  Everything a growth needs is taken before the index is
-// touched: when an allocation fails, what was taken goes back and the index is as it was.
+// touched, in local owners, and the index's members change hands behind the last call that can fail: an error anywhere leaves the index as it was and
+// hands back what was taken.
 static int fit_plane_cache(tri_batch *b, const bool planes_tasks) {
         tri_index *ix = b->ix;
         tri_dev *dev = b->dev;
         const uint32_t want = std::max<uint32_t>(1, b->plane_rows);
         // (rows whose readers are through go back to the pool: no call here waits for the device)
         for (size_t i = 0; i < ix->pc_retired.size();)
-                if (hipEventQuery(ix->pc_retired[i].second) == hipSuccess) {
-                        pool_free(dev, ix->pc_retired[i].first);
-                        event_put(dev, ix->pc_retired[i].second);
+                if (hipEventQuery(ix->pc_retired[i].second) == hipSuccess)
                         ix->pc_retired.erase(ix->pc_retired.begin() + (long)i);
-                } else
+                else
                         ++i;
         // (does this batch read the rows' HIGH parts — a scored batch whose one-pass kernel or scorers read planes?)
         b->planes_hi = planes_tasks || !b->splane.empty();
@@ -1006,102 +962,106 @@ static int fit_plane_cache(tri_batch *b, const bool planes_tasks) {
                 for (uint32_t r = 0; r < cap; ++r)
                         hs[r + 1] = hs[r] + (rt[r] != 0xffffffffu ? ix->terms[rt[r]].documents : 0u);
         }
-        // the buffers this growth replaces: retired on events recorded on the UPLOAD stream, behind the copies that read them — that point is past
-        // the engine stream's earlier readers too (stream_up waits for `drained`).  (Round 5 retired them on events of the engine stream recorded
-        // BEFORE the copies were enqueued: the next tri_batch_create could pool a buffer the copy had not read yet.)
-        std::vector<void *> outgrown;
-        if (resize && ix->d_prank) // (retired with the rows: same readers, and the copies below read them)
-                outgrown = {ix->d_prank, ix->d_phs, ix->d_hs_off, ix->d_ph_pairs};
-        if (resize && ix->d_pcache)
-                outgrown.push_back(ix->d_pcache);
-        if (new_hi && ix->d_pcache_hi)
-                outgrown.push_back(ix->d_pcache_hi);
+        // the buffers this growth replaces, each retired on an event of its own (the rank directories go with the rows: same readers, and the copies below read them)
+        const size_t n_outgrown = (resize && ix->d_prank ? 4 : 0) + (resize && ix->d_pcache ? 1 : 0) + (new_hi && ix->d_pcache_hi ? 1 : 0);
         // ---- take every buffer and event first
-        uint32_t *fresh = nullptr, *fresh_hi = nullptr, *pairs = nullptr, *prank = nullptr, *term_row = nullptr;
-        unsigned long long *phs = nullptr;
-        uint64_t *hso = nullptr;
-        hipEvent_t drained = nullptr, ready = nullptr;
-        std::vector<hipEvent_t> retire(outgrown.size(), nullptr);
+        Pooled<uint32_t> fresh, fresh_hi, pairs, prank;
+        Pooled<unsigned long long> phs;
+        Pooled<uint64_t> hso;
+        DevMem<uint32_t> term_row;
+        PooledEvent drained, ready;
+        std::vector<PooledEvent> retire(n_outgrown);
         hipError_t e = hipSuccess;
-        auto take = [&](auto **buf, const size_t bytes) { e = e == hipSuccess ? pool_alloc(dev, (void **)buf, bytes) : e; };
+        auto take = [&](auto &buf, const size_t bytes) { e = e == hipSuccess ? buf.alloc(dev, bytes) : e; };
         if (resize)
-                take(&fresh, ((size_t)cap + 1) * row + 64);
+                take(fresh, ((size_t)cap + 1) * row + 64);
         if (new_hi)
-                take(&fresh_hi, ((size_t)cap + 1) * row_hi + 64);
+                take(fresh_hi, ((size_t)cap + 1) * row_hi + 64);
         if (resize) {
-                take(&pairs, (size_t)cap * 8 + POOL_MIN_BYTES);
-                take(&prank, (size_t)cap * groups * PL_RANK_WORDS * 4 + 64);
-                take(&phs, (hs[cap] + 8) * 8);
-                take(&hso, ((size_t)cap + 1) * 8 + POOL_MIN_BYTES);
+                take(pairs, (size_t)cap * 8 + POOL_MIN_BYTES);
+                take(prank, (size_t)cap * groups * PL_RANK_WORDS * 4 + 64);
+                take(phs, (hs[cap] + 8) * 8);
+                take(hso, ((size_t)cap + 1) * 8 + POOL_MIN_BYTES);
                 if (e == hipSuccess && !ix->d_term_row)
-                        e = hipMalloc((void **)&term_row, (ix->terms.size() + 1) * 4);
+                        e = term_row.alloc((ix->terms.size() + 1) * 4);
         }
         if (e == hipSuccess)
-                e = event_get(dev, &drained);
+                e = drained.take(dev);
         if (e == hipSuccess && !ix->ev_pc_ready)
-                e = event_get(dev, &ready);
-        for (hipEvent_t &r : retire)
+                e = ready.take(dev);
+        for (PooledEvent &r : retire)
                 if (e == hipSuccess)
-                        e = event_get(dev, &r);
-        if (e != hipSuccess) {
-                for (void *p : {(void *)fresh, (void *)fresh_hi, (void *)pairs, (void *)prank, (void *)phs, (void *)hso})
-                        pool_free(dev, p);
-                hipFree(term_row);
-                event_put(dev, drained);
-                event_put(dev, ready);
-                for (hipEvent_t r : retire)
-                        event_put(dev, r);
+                        e = r.take(dev);
+        if (e != hipSuccess)
                 return fail(e == hipErrorOutOfMemory ? TRI_ERR_NOMEM : TRI_ERR_DEVICE, "tri_batch_create: growing the plane cache: %s", hipGetErrorString(e));
+        // ---- then the rows move: from the index's buffers, which stay in place, into the fresh ones
+        const hipEvent_t pc_ready = ready ? ready : ix->ev_pc_ready;
+        uint32_t *const d_term_row = term_row ? term_row : ix->d_term_row;
+        const int rc = [&]() -> int {
+                HIP_TRY(hipEventRecord(drained, dev->stream));
+                HIP_TRY(hipStreamWaitEvent(dev->stream_up, drained, 0));
+                if (fresh) {
+                        if (same_plw)
+                                HIP_TRY(hipMemcpyAsync(fresh, ix->d_pcache, (size_t)ix->pc_cap * row, hipMemcpyDeviceToDevice, dev->stream_up));
+                        HIP_TRY(hipMemsetAsync((uint8_t *)fresh.get() + (size_t)cap * row, 0, row + 64, dev->stream_up));
+                }
+                if (fresh_hi) {
+                        if (same_plw && ix->d_pcache_hi)
+                                HIP_TRY(hipMemcpyAsync(fresh_hi, ix->d_pcache_hi, (size_t)ix->pc_cap * row_hi, hipMemcpyDeviceToDevice, dev->stream_up));
+                        HIP_TRY(hipMemsetAsync((uint8_t *)fresh_hi.get() + (size_t)cap * row_hi, 0, row_hi + 64, dev->stream_up));
+                }
+                if (resize) {
+                        if (same_plw && ix->d_prank) {
+                                HIP_TRY(hipMemcpyAsync(pairs, ix->d_ph_pairs, ix->ph_pairs_n * 8, hipMemcpyDeviceToDevice, dev->stream_up));
+                                HIP_TRY(hipMemcpyAsync(prank, ix->d_prank, (size_t)ix->pc_cap * groups * PL_RANK_WORDS * 4, hipMemcpyDeviceToDevice, dev->stream_up));
+                                HIP_TRY(hipMemcpyAsync(phs, ix->d_phs, ix->hs_off[ix->pc_cap] * 8, hipMemcpyDeviceToDevice, dev->stream_up));
+                        }
+                        HIP_TRY(hipMemcpyAsync(hso, hs.data(), ((size_t)cap + 1) * 8, hipMemcpyHostToDevice, dev->stream_up)); // (hs outlives the copy: it becomes the member hs_off below)
+                        if (term_row || !same_plw)
+                                HIP_TRY(hipMemsetAsync(d_term_row, 0xff, (ix->terms.size() + 1) * 4, dev->stream_up));
+                }
+                HIP_TRY(hipEventRecord(pc_ready, dev->stream_up));
+                // the buffers this growth replaces are retired on events recorded on the UPLOAD stream, behind the copies that read them — that point is past
+                // the engine stream's earlier readers too (stream_up waits for `drained`).  (Round 5 retired them on events of the engine stream recorded
+                // BEFORE the copies were enqueued: the next tri_batch_create could pool a buffer the copy had not read yet.)
+                for (PooledEvent &r : retire)
+                        HIP_TRY(hipEventRecord(r, dev->stream_up));
+                return TRI_OK;
+        }();
+        if (rc) {
+                hipStreamSynchronize(dev->stream_up); // (the fresh buffers go back to the pool: no copy queued above may still be writing them)
+                return rc;
         }
-        // ---- then the rows move
-        if (ready)
-                ix->ev_pc_ready = ready;
-        HIP_TRY(hipEventRecord(drained, dev->stream));
-        HIP_TRY(hipStreamWaitEvent(dev->stream_up, drained, 0));
-        if (fresh) {
-                if (same_plw)
-                        HIP_TRY(hipMemcpyAsync(fresh, ix->d_pcache, (size_t)ix->pc_cap * row, hipMemcpyDeviceToDevice, dev->stream_up));
-                else
-                        ix->pc_built.clear();
-                HIP_TRY(hipMemsetAsync((uint8_t *)fresh + (size_t)cap * row, 0, row + 64, dev->stream_up));
-        }
-        if (fresh_hi) {
-                if (same_plw && ix->d_pcache_hi)
-                        HIP_TRY(hipMemcpyAsync(fresh_hi, ix->d_pcache_hi, (size_t)ix->pc_cap * row_hi, hipMemcpyDeviceToDevice, dev->stream_up));
-                else
-                        for (auto &bb : ix->pc_built)
-                                bb &= (uint8_t)~2u; // (no row has its high part yet)
-                HIP_TRY(hipMemsetAsync((uint8_t *)fresh_hi + (size_t)cap * row_hi, 0, row_hi + 64, dev->stream_up));
-        }
+        // ---- nothing below can fail: the index takes the fresh buffers, and what a member held is retired on the next event
+        size_t nret = 0;
+        auto swap_in = [&](auto &member, auto &with) {
+                if (member)
+                        ix->pc_retired.emplace_back(Pooled<void>(member.release(), FreePooled{dev}), std::move(retire[nret++]));
+                member = std::move(with);
+        };
         if (resize) {
-                if (same_plw && ix->d_prank) {
-                        HIP_TRY(hipMemcpyAsync(pairs, ix->d_ph_pairs, ix->ph_pairs_n * 8, hipMemcpyDeviceToDevice, dev->stream_up));
-                        HIP_TRY(hipMemcpyAsync(prank, ix->d_prank, (size_t)ix->pc_cap * groups * PL_RANK_WORDS * 4, hipMemcpyDeviceToDevice, dev->stream_up));
-                        HIP_TRY(hipMemcpyAsync(phs, ix->d_phs, ix->hs_off[ix->pc_cap] * 8, hipMemcpyDeviceToDevice, dev->stream_up));
-                } else {
+                if (!same_plw)
+                        ix->pc_built.clear();
+                if (!(same_plw && ix->d_prank)) { // (no rank directory was there to move)
                         ix->ph_built.clear();
                         ix->ph_pairs_n = 0;
                 }
                 ix->hs_off = std::move(hs); // (a row's offset depends on the rows before it alone: what was built stays where it was)
-                HIP_TRY(hipMemcpyAsync(hso, ix->hs_off.data(), ((size_t)cap + 1) * 8, hipMemcpyHostToDevice, dev->stream_up)); // (hs_off outlives the copy: a member)
+                swap_in(ix->d_prank, prank), swap_in(ix->d_phs, phs), swap_in(ix->d_hs_off, hso), swap_in(ix->d_ph_pairs, pairs);
+                swap_in(ix->d_pcache, fresh);
                 if (term_row)
-                        ix->d_term_row = term_row;
-                if (term_row || !same_plw)
-                        HIP_TRY(hipMemsetAsync(ix->d_term_row, 0xff, (ix->terms.size() + 1) * 4, dev->stream_up));
-                ix->d_prank = prank, ix->d_phs = phs, ix->d_hs_off = hso, ix->d_ph_pairs = pairs;
+                        ix->d_term_row = std::move(term_row);
                 ix->rank_term = std::move(rt);
                 ix->ph_built.resize(cap, 0);
         }
-        HIP_TRY(hipEventRecord(ix->ev_pc_ready, dev->stream_up));
-        for (size_t i = 0; i < outgrown.size(); ++i) {
-                HIP_TRY(hipEventRecord(retire[i], dev->stream_up));
-                ix->pc_retired.emplace_back(outgrown[i], retire[i]);
+        if (new_hi) {
+                if (!(same_plw && ix->d_pcache_hi))
+                        for (auto &bb : ix->pc_built)
+                                bb &= (uint8_t)~2u; // (no row has its high part yet)
+                swap_in(ix->d_pcache_hi, fresh_hi);
         }
-        event_put(dev, drained);
-        if (fresh)
-                ix->d_pcache = fresh;
-        if (fresh_hi)
-                ix->d_pcache_hi = fresh_hi;
+        if (ready)
+                ix->ev_pc_ready = std::move(ready);
         ix->pc_cap = cap;
         ix->pc_plw = b->plw;
         ix->pc_built.resize(cap, 0);
@@ -1112,213 +1072,210 @@ static int fit_plane_cache(tri_batch *b, const bool planes_tasks) {
 // host threads) + the plan's way to the device: ONE pinned block, ONE arena, ONE copy on the upload stream.  Everything a steady caller
 // needs per batch comes from the handle's pools (arena, pinned block, output regions, events): no hipMalloc, no hipFree, no device
 // synchronisation — the next batch is compiled and uploaded while the current one runs.
-extern "C" int tri_batch_create(tri_index *ix, const uint32_t *prog, size_t prog_len, const tri_query *queries, size_t nq, const double *weights,
-                                uint32_t flags, uint32_t topk, int similarity, tri_batch **out) {
+// ---- tri_batch_create's stages, in call order
+
+static int create_check_args(const tri_index *ix, const uint32_t *prog, const size_t prog_len, const tri_query *queries, const size_t nq, const uint32_t flags, const uint32_t topk,
+                             const int similarity, tri_batch *const *out) {
         if (!ix || !out || (!prog && prog_len) || (!queries && nq))
                 return fail(TRI_ERR_INVALID, "tri_batch_create: null argument");
         const uint32_t mode = flags & (TRI_FLAG_DOCUMENTS_ONLY | TRI_FLAG_ACCUMULATED_SCORE | TRI_FLAG_MATCHED_TERMS);
         if (mode != TRI_FLAG_DOCUMENTS_ONLY && mode != TRI_FLAG_ACCUMULATED_SCORE && mode != TRI_FLAG_MATCHED_TERMS)
                 return fail(TRI_ERR_INVALID, "exactly one of DocumentsOnly, AccumulatedScoreScheme, MatchedTerms (exec_query's default mode): the modes are mutually exclusive (exec.h:45-48)");
-        const bool scored = mode == TRI_FLAG_ACCUMULATED_SCORE;
-        const bool rich = mode == TRI_FLAG_MATCHED_TERMS;
-        if ((flags & TRI_FLAG_HIT_PAYLOADS) && !rich)
+        if ((flags & TRI_FLAG_HIT_PAYLOADS) && mode != TRI_FLAG_MATCHED_TERMS)
                 return fail(TRI_ERR_INVALID, "TRI_FLAG_HIT_PAYLOADS goes with TRI_FLAG_MATCHED_TERMS (the mode that delivers hits)");
-        if (scored && topk > TOPK_MAX)
+        if (mode == TRI_FLAG_ACCUMULATED_SCORE && topk > TOPK_MAX)
                 return fail(TRI_ERR_INVALID, "AccumulatedScoreScheme: topk <= %u (0 = keep every match's score instead of a top-K)", TOPK_MAX);
         if (similarity != TRI_SIM_BM25 && similarity != TRI_SIM_TFIDF && similarity != TRI_SIM_TRIVIAL)
                 return fail(TRI_ERR_INVALID, "unknown similarity %d", similarity);
-        tri_dev *dev = ix->dev;
-        HIP_TRY(hipSetDevice(dev->device));
-        const auto t_create = std::chrono::steady_clock::now();
-        auto b = std::make_unique<tri_batch>();
-        b->ix = ix;
-        b->dev = dev;
-        dev_retain(dev);
-        b->flags = flags;
-        b->topk = topk;
-        b->similarity = similarity;
-        b->nq = nq;
-        // ---- plan (host)
+        return TRI_OK;
+}
+// (the modes are mutually exclusive: create_check_args)
+static bool batch_scored(const tri_batch *b) { return b->flags & TRI_FLAG_ACCUMULATED_SCORE; }
+static bool batch_rich(const tri_batch *b) { return b->flags & TRI_FLAG_MATCHED_TERMS; }
+
+// plan on a free context (host; outside the handle's lock)
+static int create_plan(tri_batch *b, const PlanInput &in) {
+        tri_index *ix = b->ix;
+        tri_dev *dev = b->dev;
+        const size_t nq = in.nq;
         PlanEnv env;
         env.opt = dev->opt;
         env.cus = (uint32_t)dev->cus;
         env.fus_wgs_per_cu = FUS_WGS_PER_CU;
         env.plk_wgs_per_cu = PLK_WGS_PER_CU;
-        PlanInput in;
-        in.prog = prog;
-        in.prog_len = prog_len;
-        in.queries = queries;
-        in.nq = nq;
-        in.weights = weights;
-        in.flags = flags;
-        in.topk = topk;
-        in.similarity = similarity;
-        {
-                std::string err;
-                int rc;
-                try {
-                        // a free planner context (the first one when both are busy: creates from more threads than contexts plan one after the other)
-                        unsigned which = 0;
-                        std::unique_lock<std::mutex> plan_lock(dev->planners[0].mu, std::try_to_lock);
-                        for (unsigned k = 1; k < tri_dev::PLAN_CTXS && !plan_lock.owns_lock(); ++k) {
-                                plan_lock = std::unique_lock<std::mutex>(dev->planners[k].mu, std::try_to_lock);
-                                which = k;
-                        }
-                        if (!plan_lock.owns_lock()) {
-                                which = 0;
-                                plan_lock = std::unique_lock<std::mutex>(dev->planners[0].mu);
-                        }
-                        tri_dev::PlanCtx &pc = dev->planners[which];
-                        if (nq >= 1024 && !pc.pool) { // (batches below a thousand queries are planned on the calling thread)
-                                // (default: the handle's contexts share what the process may use — the affinity mask, capped by the cgroup's CPU quota — less six CPUs: the two
-                                //  compiling callers, the thread that runs and awaits batches, the runtime's own threads, and slack — a process that uses its whole quota is
-                                //  throttled at the first neighbour's burst: host_pool.hpp.  Under the GPU box's 16-CPU quota: 6 threads a context; measured there, 600 steps of cfg2
-                                //  with the kernels at 1.18 ms, 5 / 7 threads x 2 compilers: 1.185 ms per step either way, 8 x 1: 1.39 - 1.49 (the planner is the bound), 12 x 1: 1.18;
-                                //  at the round's end, kernels 1.11 ms, 100 steps, threads a context -> ms per step, a create's median / longest: 4 -> 1.29, 2.65 / 41;
-                                //  5 -> 1.121, 2.0 - 2.2 / 2.6 - 39; 6 -> 1.114, 1.58 / 1.97; 7 -> 1.117, 1.59 / 1.88; 8 -> 1.127, 1.56 / 44 — six: four CPUs of the quota stay free)
-                                const unsigned budget = host_cpu_budget();
-                                const unsigned fair = budget >= 10 ? std::min(16u, (budget - 4) / tri_dev::PLAN_CTXS) : budget >= 4 ? 2u : 1u;
-                                const unsigned want = dev->opt.plan_threads ? (unsigned)std::min<uint64_t>(dev->opt.plan_threads, 64) : fair;
-                                if (want > 1) {
-                                        try {
-                                                // (every pool of the handle counts its stretch of CPUs from the FIRST pool's anchor, not from its own creator's CPU;
-                                                //  under the handle's lock: two contexts starting their pools at once agree on it)
-                                                DevLock g(dev->mu);
-                                                pc.pool = std::make_unique<HostPool>(want, dev->opt.plan_pin != 0, (unsigned)dev->opt.plan_hot_us, which, tri_dev::PLAN_CTXS, dev->plan_anchor, dev->opt.plan_pin == 2);
-                                                if (dev->plan_anchor < 0)
-                                                        dev->plan_anchor = pc.pool->anchor();
-                                        } catch (...) { // (no threads to be had: the calling thread plans alone)
-                                        }
+        std::string err;
+        int rc;
+        try {
+                // a free planner context (the first one when both are busy: creates from more threads than contexts plan one after the other)
+                unsigned which = 0;
+                std::unique_lock<std::mutex> plan_lock(dev->planners[0].mu, std::try_to_lock);
+                for (unsigned k = 1; k < tri_dev::PLAN_CTXS && !plan_lock.owns_lock(); ++k) {
+                        plan_lock = std::unique_lock<std::mutex>(dev->planners[k].mu, std::try_to_lock);
+                        which = k;
+                }
+                if (!plan_lock.owns_lock()) {
+                        which = 0;
+                        plan_lock = std::unique_lock<std::mutex>(dev->planners[0].mu);
+                }
+                tri_dev::PlanCtx &pc = dev->planners[which];
+                if (nq >= 1024 && !pc.pool) { // (batches below a thousand queries are planned on the calling thread)
+                        // (default: the handle's contexts share what the process may use — the affinity mask, capped by the cgroup's CPU quota — less six CPUs: the two
+                        //  compiling callers, the thread that runs and awaits batches, the runtime's own threads, and slack — a process that uses its whole quota is
+                        //  throttled at the first neighbour's burst: host_pool.hpp.  Under the GPU box's 16-CPU quota: 6 threads a context; measured there, 600 steps of cfg2
+                        //  with the kernels at 1.18 ms, 5 / 7 threads x 2 compilers: 1.185 ms per step either way, 8 x 1: 1.39 - 1.49 (the planner is the bound), 12 x 1: 1.18;
+                        //  at the round's end, kernels 1.11 ms, 100 steps, threads a context -> ms per step, a create's median / longest: 4 -> 1.29, 2.65 / 41;
+                        //  5 -> 1.121, 2.0 - 2.2 / 2.6 - 39; 6 -> 1.114, 1.58 / 1.97; 7 -> 1.117, 1.59 / 1.88; 8 -> 1.127, 1.56 / 44 — six: four CPUs of the quota stay free)
+                        const unsigned budget = host_cpu_budget();
+                        const unsigned fair = budget >= 10 ? std::min(16u, (budget - 4) / tri_dev::PLAN_CTXS) : budget >= 4 ? 2u : 1u;
+                        const unsigned want = dev->opt.plan_threads ? (unsigned)std::min<uint64_t>(dev->opt.plan_threads, 64) : fair;
+                        if (want > 1) {
+                                try {
+                                        // (every pool of the handle counts its stretch of CPUs from the FIRST pool's anchor, not from its own creator's CPU;
+                                        //  under the handle's lock: two contexts starting their pools at once agree on it)
+                                        DevLock g(dev->mu);
+                                        pc.pool = std::make_unique<HostPool>(want, dev->opt.plan_pin != 0, (unsigned)dev->opt.plan_hot_us, which, tri_dev::PLAN_CTXS, dev->plan_anchor, dev->opt.plan_pin == 2);
+                                        if (dev->plan_anchor < 0)
+                                                dev->plan_anchor = pc.pool->anchor();
+                                } catch (...) { // (no threads to be had: the calling thread plans alone)
                                 }
                         }
-                        rc = plan_batch(*ix, env, in, pc.pool.get(), [&](size_t bytes) { return pinned_alloc(dev, bytes, &b->block_cap); }, *b, err, &pc.frag_cache);
-                } catch (const std::bad_alloc &) {
-                        return fail(TRI_ERR_NOMEM, "tri_batch_create: out of host memory");
                 }
-                if (rc != TRI_OK)
-                        return fail(rc, "%s", err.c_str());
-                if (!b->last_unsupported.empty())
-                        fail(TRI_ERR_UNSUPPORTED, "%s", b->last_unsupported.c_str()); // (tri_last_error() describes the last query that was left out; the call succeeds)
+                rc = plan_batch(*ix, env, in, pc.pool.get(), [&](size_t bytes) { return b->pinned.alloc(dev, bytes); }, *b, err, &pc.frag_cache);
+        } catch (const std::bad_alloc &) {
+                return fail(TRI_ERR_NOMEM, "tri_batch_create: out of host memory");
         }
-        const size_t nt = b->tasks.size(), np = b->plan.size();
-        const uint64_t off = b->out_capacity;
-        static const bool dbg_create = getenv("TRINITY_DEBUG_CREATE") != nullptr; // (stderr: where a create's time goes past the planner)
-        double dbg_t[6] = {0, 0, 0, 0, 0, 0};
-        auto dbg_lap = [&](int i) {
-                if (dbg_create)
-                        dbg_t[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count();
-        };
-        dbg_lap(0);
-        DevLock dev_lock(dev->mu); // (from here on: the device's pools, the index's plane cache, the streams — see tri_dev::mu)
-        // ---- the arena: the block's copy, then the batch's small device-only arrays; the part that must start out zero comes last
-        size_t a = b->block_bytes;
-        auto carve = [&](size_t bytes) {
-                const size_t at = a;
-                a += (bytes + 255) & ~(size_t)255;
-                return at;
-        };
-        const size_t a_counts = carve((nt + 1) * 4), a_ticket = carve(TICKET_BYTES), a_build = carve((b->plane_terms.size() + 1) * 8);
-        const bool planes_tasks = b->n_planes + b->n_planes8;
-        const size_t a_qthr = planes_tasks ? carve((np + 1) * 8) : 0;
-        const size_t a_part_counts = scored ? carve((nt + 1) * 4) : 0, a_score_order = scored ? carve((nt + 1) * 4) : 0;
-        const size_t a_task_hits = rich ? carve((nt + 1) * 4) : 0, a_task_pos = rich ? carve((nt + 1) * 8) : 0;
-        const size_t a_scat_off = b->pscatter_queries ? carve((nt + 1) * 4) : 0, a_scat_cnt = b->pscatter_queries ? carve((nt + 1) * 4) : 0;
-        const size_t a_scat_list = b->pscatter_queries ? carve((b->pscatter_queries + 1) * 4) : 0;
-        const size_t a_zero = a;
-        const size_t a_qcounts = carve((nq + 1) * 8); // queries that can never match keep count 0 ...
-        const size_t a_top_counts = scored ? carve((nq + 1) * 4) : 0;
-        const size_t a_top_docs = scored ? carve((nq * topk + 1) * 4) : 0; // ... and zeroed rows (k_topk_merge only writes the rows of queries that have a plan slot;
-        const size_t a_top_scores = scored ? carve((nq * topk + 1) * 4) : 0; // the blocks travel whole to the host and to the other ranks)
-        HIP_TRY(pool_alloc(dev, (void **)&b->d_arena, a + 256));
-        uint8_t *const A = b->d_arena;
-        b->d_counts = (uint32_t *)(A + a_counts);
-        b->d_ticket = (uint32_t *)(A + a_ticket);
-        b->d_build = (uint32_t *)(A + a_build);
-        b->d_qthr = planes_tasks ? (unsigned long long *)(A + a_qthr) : nullptr;
-        b->d_part_counts = scored ? (uint32_t *)(A + a_part_counts) : nullptr;
-        b->d_score_order = scored ? (uint32_t *)(A + a_score_order) : nullptr;
-        b->d_scat_off = b->pscatter_queries ? (uint32_t *)(A + a_scat_off) : nullptr;
-        b->d_scat_cnt = b->pscatter_queries ? (uint32_t *)(A + a_scat_cnt) : nullptr;
-        b->d_scat_list = b->pscatter_queries ? (uint32_t *)(A + a_scat_list) : nullptr;
+        if (rc != TRI_OK)
+                return fail(rc, "%s", err.c_str());
+        if (!b->last_unsupported.empty())
+                fail(TRI_ERR_UNSUPPORTED, "%s", b->last_unsupported.c_str()); // (tri_last_error() describes the last query that was left out; the call succeeds)
+        return TRI_OK;
+}
+
+// The arena's layout: the block's copy, then the batch's small device-only arrays; the part that must start out zero comes last (from *zero_from).  Every
+// section is named here and nowhere else: called without a base to size the arena, with the arena to point the batch's views into it
+static size_t batch_arena(tri_batch *b, uint8_t *base, size_t *zero_from) {
+        const size_t nt = b->tasks.size(), np = b->plan.size(), nq = b->nq, topk = b->topk;
+        const bool scored = batch_scored(b), rich = batch_rich(b), scatter = b->pscatter_queries;
+        Carver carve{base, b->block_bytes};
+        carve(b->d_counts, (nt + 1) * 4);
+        carve(b->d_ticket, TICKET_BYTES);
+        carve(b->d_build, (b->plane_terms.size() + 1) * 8);
+        carve(b->d_qthr, (np + 1) * 8, b->n_planes + b->n_planes8 != 0);
+        carve(b->d_part_counts, (nt + 1) * 4, scored);
+        carve(b->d_score_order, (nt + 1) * 4, scored);
+        carve(b->d_task_hits, (nt + 1) * 4, rich);
+        carve(b->d_task_pos_base, (nt + 1) * 8, rich);
+        carve(b->d_scat_off, (nt + 1) * 4, scatter);
+        carve(b->d_scat_cnt, (nt + 1) * 4, scatter);
+        carve(b->d_scat_list, (b->pscatter_queries + 1) * 4, scatter);
+        *zero_from = carve.at;
+        carve(b->d_qcounts, (nq + 1) * 8); // queries that can never match keep count 0 ...
+        carve(b->d_top_counts, (nq + 1) * 4, scored);
+        carve(b->d_top_docs, (nq * topk + 1) * 4, scored); // ... and zeroed rows (k_topk_merge only writes the rows of queries that have a plan slot;
+        carve(b->d_top_scores, (nq * topk + 1) * 4, scored); // the blocks travel whole to the host and to the other ranks)
+        return carve.at;
+}
+
+// the arena, the scatter list its sections index, the batch's events, and the plan's copy on its way
+static int create_arena(tri_batch *b) {
+        tri_dev *dev = b->dev;
+        size_t a_zero = 0;
+        const size_t a = batch_arena(b, nullptr, &a_zero);
+        HIP_TRY(b->d_arena.alloc(dev, a + 256));
+        batch_arena(b, b->d_arena, &a_zero);
         if (b->pscatter_queries) {
                 if (b->pscatter_docs + 64 > 0xffffffffull)
                         return fail(TRI_ERR_UNSUPPORTED, "tri_batch_create: the unions' terms without a plane hold more than 2^32 documents");
                 b->scat_cap = (uint32_t)b->pscatter_docs;
-                HIP_TRY(pool_alloc(dev, (void **)&b->d_scat_docs, ((size_t)b->scat_cap + 64) * 4));
+                HIP_TRY(b->d_scat_docs.alloc(dev, ((size_t)b->scat_cap + 64) * 4));
         }
-        b->d_task_hits = rich ? (uint32_t *)(A + a_task_hits) : nullptr;
-        b->d_task_pos_base = rich ? (uint64_t *)(A + a_task_pos) : nullptr;
-        b->d_qcounts = (uint64_t *)(A + a_qcounts);
-        b->d_top_counts = scored ? (uint32_t *)(A + a_top_counts) : nullptr;
-        b->d_top_docs = scored ? (uint32_t *)(A + a_top_docs) : nullptr;
-        b->d_top_scores = scored ? (float *)(A + a_top_scores) : nullptr;
-        for (hipEvent_t &e : b->ev)
-                HIP_TRY(event_get(dev, &e));
+        for (PooledEvent &e : b->ev)
+                HIP_TRY(e.take(dev));
         if (b->block_bytes)
-                HIP_TRY(hipMemcpyAsync(A, b->block, b->block_bytes, hipMemcpyHostToDevice, dev->stream_up));
-        HIP_TRY(hipMemsetAsync(A + a_zero, 0, a - a_zero, dev->stream_up));
-        dbg_lap(1);
-        // ---- the large buffers (the device handle's pool)
+                HIP_TRY(hipMemcpyAsync(b->d_arena, b->block, b->block_bytes, hipMemcpyHostToDevice, dev->stream_up));
+        HIP_TRY(hipMemsetAsync(b->d_arena + a_zero, 0, a - a_zero, dev->stream_up));
+        return TRI_OK;
+}
+
+// the trees' scratch block, its sections in words one after the other (tri_batch::d_tree_scratch), 64 spare words behind the last
+static size_t tree_scratch(tri_batch *b, uint32_t *base) {
+        const size_t plw = b->plw, nterms = b->tree_terms.size(), nhid = b->tree_hidden.size(), nchunks = (plw + TREE_CHUNK_WORDS - 1) / TREE_CHUNK_WORDS;
+        Carver carve{reinterpret_cast<uint8_t *>(base), 0, 4};
+        carve(b->d_tree_rows, nterms * PL_PLANES * plw * 4);
+        carve(b->d_tree_prows, nhid * plw * 4);
+        carve(b->d_tree_qbits, (size_t)b->n_tree * plw * 4);
+        carve(b->d_tree_cc, ((size_t)b->n_tree * nchunks + 64) * 4);
+        carve(b->d_tree_build, 2 * nterms * 4);
+        return carve.at + 64 * 4;
+}
+
+// the large buffers (the device handle's pool): what every mode takes, then the default mode's, AccumulatedScore's, the trees'
+template <class Lap>
+static int create_buffers(tri_batch *b, const PlanInput &in, Lap &&lap) {
+        tri_dev *dev = b->dev;
+        const uint64_t off = b->out_capacity;
+        const bool planes_tasks = b->n_planes + b->n_planes8 != 0, scored = batch_scored(b);
         if (!b->plane_terms.empty() || planes_tasks)
-                if (const int rc = fit_plane_cache(b.get(), planes_tasks))
+                if (const int rc = fit_plane_cache(b, planes_tasks))
                         return rc;
         if (planes_tasks) {
                 const uint64_t wgs = std::min<uint64_t>(std::max(b->n_planes, b->n_planes8), (uint64_t)dev->cus * PLK_WGS_PER_CU);
-                HIP_TRY(pool_alloc(dev, (void **)&b->d_sparse, (2 * wgs * b->sparse_cap + 64) * 4)); // (per workgroup: the lists' entries, then their frequencies)
+                HIP_TRY(b->d_sparse.alloc(dev, (2 * wgs * b->sparse_cap + 64) * 4)); // (per workgroup: the lists' entries, then their frequencies)
         }
-        dbg_lap(2);
-        HIP_TRY(pool_alloc(dev, (void **)&b->d_out, (off + 64) * 4));
-        dbg_lap(3);
+        lap(2);
+        HIP_TRY(b->d_out.alloc(dev, (off + 64) * 4));
+        lap(3);
         if (!b->phrases.empty() && scored) {
-                HIP_TRY(pool_alloc(dev, (void **)&b->d_pscore, (off + 64) * 8)); // (no clearing: k_phrase writes the entry of every match it keeps, and only
-                                                                                  //  the matches of queries that hold a phrase are ever read — k_score, k_tree_leaves)
+                HIP_TRY(b->d_pscore.alloc(dev, (off + 64) * 8)); // (no clearing: k_phrase writes the entry of every match it keeps, and only
+                                                                 //  the matches of queries that hold a phrase are ever read — k_score, k_tree_leaves)
         }
-        if (rich) {
-                b->h_prog.assign(prog, prog + prog_len); // (tri_batch_set_ranker maps its per-token weights onto the reportable terms)
-                b->h_queries.assign(queries, queries + nq);
+        if (batch_rich(b)) {
+                b->h_prog.assign(in.prog, in.prog + in.prog_len); // (tri_batch_set_ranker maps its per-token weights onto the reportable terms)
+                b->h_queries.assign(in.queries, in.queries + in.nq);
                 b->rich_R = std::max<uint32_t>(b->rich_R, 1);
-                HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_present, (off + 64) * 4));
-                HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_freq, (off + 64) * 2 * b->rich_R));
+                HIP_TRY(b->d_rich_present.alloc(dev, (off + 64) * 4));
+                HIP_TRY(b->d_rich_freq.alloc(dev, (off + 64) * 2 * b->rich_R));
                 if (b->rich_allow) {
-                        HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_allow, (off + 64) * 4));
+                        HIP_TRY(b->d_rich_allow.alloc(dev, (off + 64) * 4));
                         HIP_TRY(hipMemsetAsync(b->d_rich_allow, 0xff, (off + 64) * 4, dev->stream_up)); // (every other query's matches: all terms allowed)
                 }
                 if (b->n_rich_wide) { // wide-report queries: rows and high mask halves of their own (2 x stride + 8 bytes per output slot of theirs)
-                        HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_freq_wide, (b->rich_wide_cells + 64) * 2));
-                        HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_present_hi, (b->rich_wide_slots + 64) * 4));
-                        HIP_TRY(pool_alloc(dev, (void **)&b->d_rich_allow_hi, (b->rich_wide_slots + 64) * 4));
+                        HIP_TRY(b->d_rich_freq_wide.alloc(dev, (b->rich_wide_cells + 64) * 2));
+                        HIP_TRY(b->d_rich_present_hi.alloc(dev, (b->rich_wide_slots + 64) * 4));
+                        HIP_TRY(b->d_rich_allow_hi.alloc(dev, (b->rich_wide_slots + 64) * 4));
                         HIP_TRY(hipMemsetAsync(b->d_rich_allow_hi, 0xff, (b->rich_wide_slots + 64) * 4, dev->stream_up));
                 }
         }
         if (scored) {
+                const size_t nt = b->tasks.size(), topk = b->topk;
                 if (!topk)
-                        HIP_TRY(pool_alloc(dev, (void **)&b->d_all_scores, (off + 64) * 8));
-                HIP_TRY(pool_alloc(dev, (void **)&b->d_part_docs, (nt * topk + 1) * 4));
-                HIP_TRY(pool_alloc(dev, (void **)&b->d_part_scores, (nt * topk + 1) * 8));
+                        HIP_TRY(b->d_all_scores.alloc(dev, (off + 64) * 8));
+                HIP_TRY(b->d_part_docs.alloc(dev, (nt * topk + 1) * 4));
+                HIP_TRY(b->d_part_scores.alloc(dev, (nt * topk + 1) * 8));
         }
         if (b->n_tree) {
-                const size_t plw = b->plw, nterms = b->tree_terms.size(), nhid = b->tree_hidden.size(), nchunks = (plw + TREE_CHUNK_WORDS - 1) / TREE_CHUNK_WORDS;
-                const size_t w_rows = nterms * PL_PLANES * plw, w_prows = nhid * plw, w_qbits = (size_t)b->n_tree * plw, w_cc = (size_t)b->n_tree * nchunks + 64;
-                HIP_TRY(pool_alloc(dev, (void **)&b->d_tree_scratch, (w_rows + w_prows + w_qbits + w_cc + 2 * nterms + 64) * 4));
-                b->d_tree_rows = b->d_tree_scratch;
-                b->d_tree_prows = b->d_tree_rows + w_rows;
-                b->d_tree_qbits = b->d_tree_prows + w_prows;
-                b->d_tree_cc = b->d_tree_qbits + w_qbits;
-                b->d_tree_build = b->d_tree_cc + w_cc;
+                const size_t nterms = b->tree_terms.size();
+                HIP_TRY(b->d_tree_scratch.alloc(dev, tree_scratch(b, nullptr)));
+                tree_scratch(b, b->d_tree_scratch);
                 std::vector<uint32_t> build(2 * nterms);
                 for (size_t i = 0; i < nterms; ++i)
                         build[2 * i] = b->tree_terms[i], build[2 * i + 1] = (uint32_t)i;
                 if (nterms)
                         HIP_TRY(hipMemcpyAsync(b->d_tree_build, build.data(), build.size() * 4, hipMemcpyHostToDevice, dev->stream_up)); // (pageable source: staged before the call returns)
-                if (scored && topk)
-                        HIP_TRY(pool_alloc(dev, (void **)&b->d_tree_scores, (off + 64) * 8));
+                if (scored && b->topk)
+                        HIP_TRY(b->d_tree_scores.alloc(dev, (off + 64) * 8));
         }
-        HIP_TRY(hipEventRecord(b->ev[EV_UP], dev->stream_up));
-        b->info.nqueries = nq;
+        return TRI_OK;
+}
+
+static void create_info(tri_batch *b) {
+        const bool scored = batch_scored(b), rich = batch_rich(b);
+        const uint32_t topk = b->topk;
+        b->info.nqueries = b->nq;
         b->info.tree_queries = b->tree_queries;
         b->info.bitmap_queries = b->bitmap_queries;
         b->info.tree_scratch_bytes = b->tree_scratch_bytes;
-        b->info.out_capacity = off;
+        b->info.out_capacity = b->out_capacity;
         b->info.dense_queries = b->dense_queries;
         b->info.cand_queries = b->cand_queries;
         b->info.fused_queries = b->fused_queries;
@@ -1328,18 +1285,52 @@ extern "C" int tri_batch_create(tri_index *ix, const uint32_t *prog, size_t prog
         b->info.plane_bytes = (uint64_t)b->plane_terms.size() * (b->planes_hi ? PL_PLANES : 1u) * b->plw * 4; // (what this batch reads of its rows of the index's plane cache: plane 0, a scored batch the high parts too)
         b->info.launches = (!b->plane_terms.empty()) + (!b->ptasks.empty()) + (rich ? 2 : 0) + (b->n_rich_wide ? 2 : 0) + ((scored && trip::sched_first(*b, TASK_FUSED)) ? 1 : 0) + ((scored && topk) ? 1 : 0);
         for (uint32_t kind = 0; kind < TASK_KINDS; ++kind) // (a launch per schedule section; the tree kernels are not counted)
-                b->info.launches += kind != TASK_TREE && b.get()->*trip::SCHED_COUNT[kind];
+                b->info.launches += kind != TASK_TREE && b->*trip::SCHED_COUNT[kind];
         b->info.create_plan_ms = (float)(b->plan_ms[0] + b->plan_ms[1] + b->plan_ms[2] + b->plan_ms[3]);
+}
+
+extern "C" int tri_batch_create(tri_index *ix, const uint32_t *prog, size_t prog_len, const tri_query *queries, size_t nq, const double *weights,
+                                uint32_t flags, uint32_t topk, int similarity, tri_batch **out) {
+        if (const int rc = create_check_args(ix, prog, prog_len, queries, nq, flags, topk, similarity, out))
+                return rc;
+        tri_dev *dev = ix->dev;
+        HIP_TRY(hipSetDevice(dev->device));
+        const auto t_create = std::chrono::steady_clock::now();
+        static const bool dbg_create = getenv("TRINITY_DEBUG_CREATE") != nullptr; // (stderr: where a create's time goes past the planner)
+        double dbg_t[4] = {0, 0, 0, 0};
+        auto dbg_lap = [&](int i) {
+                if (dbg_create)
+                        dbg_t[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count();
+        };
+        auto b = std::make_unique<tri_batch>();
+        b->ix = ix;
+        b->dev.retain(dev);
+        b->flags = flags;
+        b->topk = topk;
+        b->similarity = similarity;
+        b->nq = nq;
+        const PlanInput in{prog, prog_len, queries, nq, weights, flags, topk, similarity};
+        if (const int rc = create_plan(b.get(), in))
+                return rc;
+        dbg_lap(0);
+        DevLock dev_lock(dev->mu); // (from here on: the device's pools, the index's plane cache, the streams — see tri_dev::mu)
+        if (const int rc = create_arena(b.get()))
+                return rc;
+        dbg_lap(1);
+        if (const int rc = create_buffers(b.get(), in, dbg_lap))
+                return rc;
+        HIP_TRY(hipEventRecord(b->ev[EV_UP], dev->stream_up));
+        create_info(b.get());
         b->info.create_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count();
         if (dbg_create)
                 fprintf(stderr, "[tri create] nq %zu: plan %.3f  arena+copy %.3f  planes/sparse %.3f  out(%.1f MB) %.3f  rest %.3f  total %.3f ms\n", nq, dbg_t[0], dbg_t[1] - dbg_t[0],
-                        dbg_t[2] - dbg_t[1], (double)off * 4 / 1e6, dbg_t[3] - dbg_t[2], b->info.create_ms - dbg_t[3], b->info.create_ms);
+                        dbg_t[2] - dbg_t[1], (double)b->out_capacity * 4 / 1e6, dbg_t[3] - dbg_t[2], b->info.create_ms - dbg_t[3], b->info.create_ms);
         *out = b.release();
         return TRI_OK;
 }
 
 extern "C" void tri_batch_destroy(tri_batch *b) {
-        delete b; // ~tri_batch releases the device buffers
+        delete b; // ~tri_batch waits, then the members release the device buffers
 }
 
 // ---- tri_batch_run's stages, in launch order: each ends with the event that closes its time (EV_PLANE_ROWS .. EV_TREE)
@@ -1348,7 +1339,7 @@ extern "C" void tri_batch_destroy(tri_batch *b) {
 static FilterSel filter_sel(const tri_batch *b) {
         if (b->filter_rows.empty())
                 return FilterSel{nullptr, nullptr, nullptr, 0u};
-        return FilterSel{b->d_filter_rows, (const uint32_t *)b->d_filter_tab, b->dev_at(b->tasks), (uint32_t)filter_words(b->ix)};
+        return FilterSel{b->d_filter_rows, (const uint32_t *)b->d_filter_tab.get(), b->dev_at(b->tasks), (uint32_t)filter_words(b->ix)};
 }
 // A persistent matching kernel for batch b: the kernel of this file (tri_launch), or — the batch has filters — its twin of filtered_kernels.hip, which takes the
 // same arguments and a FilterSel behind them
@@ -1359,13 +1350,13 @@ struct FilteredKernel<void (*)(A...)> {
         using type = void (*)(A..., FilterSel);
 };
 template <class Pick, class... Args>
-static void tri_launch_matching(const tri_batch *b, const int kernel, const int variant, Pick pick, const dim3 grid, const dim3 block, const hipStream_t stream, Args... args) {
+static void tri_launch_matching(const tri_batch *b, const int kernel, const int variant, Pick pick, const dim3 grid, const dim3 block, const hipStream_t stream, Args &&...args) {
         const FilterSel fsel = filter_sel(b);
         if (!fsel.rows)
-                return tri_launch(b->ix->codec, pick, grid, block, stream, args...);
+                return tri_launch(b->ix->codec, pick, grid, block, stream, std::forward<Args>(args)...);
         using Plain = decltype(+pick(std::integral_constant<int, CODEC_GOOGLE>()));
         const auto twin = reinterpret_cast<typename FilteredKernel<Plain>::type>(const_cast<void *>(filtered_kernel(kernel, b->ix->codec == TRI_CODEC_LUCENE ? CODEC_LUCENE : CODEC_GOOGLE, variant)));
-        hipLaunchKernelGGL(twin, grid, block, 0, stream, args..., fsel);
+        hipLaunchKernelGGL(twin, grid, block, 0, stream, std::forward<Args>(args)..., fsel);
 }
 // where the rows' source pointers lie in d_filter_tab: behind the row ids of the plan's slots
 static size_t filter_tab_ptrs_off(const tri_batch *b) { return (b->plan.size() * 4 + 15) & ~(size_t)15; }
@@ -1380,7 +1371,7 @@ static int run_filter_rows(tri_batch *b) {
         const uint32_t nrows = (uint32_t)b->filter_rows.size();
         for (uint32_t y0 = 0; y0 < nrows; y0 += 65535u) { // (gridDim.y <= 65535)
                 hipLaunchKernelGGL(k_filter_rows, dim3((unsigned)std::min<size_t>((n4 + FILTER_WG - 1) / FILTER_WG, 1024), std::min(65535u, nrows - y0)), dim3(FILTER_WG), 0, dev->stream,
-                                   (const uint4 *const *)(b->d_filter_tab + filter_tab_ptrs_off(b)) + y0, (const uint4 *)b->ix->d_masked, (uint4 *)b->d_filter_rows + (size_t)y0 * n4, n4);
+                                   (const uint4 *const *)(b->d_filter_tab + filter_tab_ptrs_off(b)) + y0, (const uint4 *)b->ix->d_masked.get(), (uint4 *)b->d_filter_rows.get() + (size_t)y0 * n4, n4);
                 HIP_TRY(hipGetLastError());
         }
         return TRI_OK;
@@ -1605,7 +1596,7 @@ static int run_phrases(tri_batch *b) {
                            b->d_ticket + TICKET_PHRASE_WORD, b->d_out, b->d_counts, b->d_pscore,
                            (b->flags & TRI_FLAG_ACCUMULATED_SCORE) ? 65535u : 1u, // exec.cpp:296 trackCnt
                            b->similarity, (const uint32_t *)ix->d_pcache, ix->pc_plw, (const uint32_t *)ix->d_prank, (const unsigned long long *)ix->d_phs,
-                           (const uint64_t *)ix->d_hs_off, (const uint32_t *)(ix->codec == TRI_CODEC_GOOGLE ? ix->d_term_row : nullptr));
+                           (const uint64_t *)ix->d_hs_off, ix->codec == TRI_CODEC_GOOGLE ? (const uint32_t *)ix->d_term_row : nullptr);
                 HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(b->ev[EV_PHRASE], dev->stream));
@@ -1636,7 +1627,7 @@ static int run_trees(tri_batch *b) {
                         HIP_TRY(hipGetLastError());
                 }
                 const bool scored_run = b->flags & TRI_FLAG_ACCUMULATED_SCORE, rich_run = b->flags & TRI_FLAG_MATCHED_TERMS;
-                double *tscores = scored_run ? (b->topk ? b->d_tree_scores : b->d_all_scores) : nullptr;
+                double *tscores = !scored_run ? nullptr : b->topk ? (double *)b->d_tree_scores : (double *)b->d_all_scores;
                 // the section's narrow records first (k_tree.hpp), then its wide ones (k_tree_wide.hpp: split_tree_section put them last); k_tree_expand reads no record
                 const uint32_t n_narrow = b->n_tree - b->n_tree_wide;
                 for (uint32_t y0 = 0; y0 < b->n_tree;) {
@@ -1656,7 +1647,7 @@ static int run_trees(tri_batch *b) {
 #define TREE_LEAVES_ARGS                                                                                                                                                                   \
         ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows,                          \
                 (const uint32_t *)b->d_tree_prows, (const uint32_t *)cc, (const uint32_t *)b->d_out, (const uint32_t *)b->d_counts, (const double *)b->dev_at(b->sweights),               \
-                (const double *)b->d_pscore, tscores, rich_run ? b->d_rich_allow : nullptr, plw, b->similarity, b->d_rich_allow_hi,                                                     \
+                (const double *)b->d_pscore, tscores, rich_run ? (uint32_t *)b->d_rich_allow : nullptr, plw, b->similarity, b->d_rich_allow_hi,                                                     \
                 (const DevRichWide *)b->dev_opt(b->rich_wide)
                                 if (wide)
                                         TRI_LAUNCH(k_tree_leaves_wide, ix->codec, grid, dim3(TREE_WG), dev->stream, TREE_LEAVES_ARGS);
@@ -1691,8 +1682,8 @@ static int launch_rich(tri_batch *b) {
 #define RICH_ARGS(SCHED, N, TICKET)                                                                                                                                                        \
         ix->d_index, ix->d_hits, ix->d_blk_hits, ix->d_hdir, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), SCHED, b->dev_at(b->sterms), N,         \
                 b->d_ticket + (WRITE ? TICKET_RICH_WRITE_WORD : TICKET_RICH_COUNT_WORD) + TICKET, b->d_out, b->d_counts, b->rich_R, b->d_rich_present, b->d_rich_freq, b->d_task_hits,     \
-                WRITE ? (const uint64_t *)b->d_task_pos_base : nullptr, WRITE ? b->d_rich_pool : nullptr, (const uint32_t *)b->d_rich_allow, WRITE ? b->d_rich_plen : nullptr,             \
-                WRITE ? b->d_rich_payload : nullptr
+                WRITE ? (const uint64_t *)b->d_task_pos_base : nullptr, WRITE ? (uint16_t *)b->d_rich_pool : nullptr, (const uint32_t *)b->d_rich_allow, WRITE ? (uint8_t *)b->d_rich_plen : nullptr,             \
+                WRITE ? (uint64_t *)b->d_rich_payload : nullptr
         if (n)
                 tri_launch(ix->codec, [](auto c) { return k_rich<c.value, WRITE>; }, dim3(std::min<uint32_t>(n, (uint32_t)dev->cus * 3)), dim3(AND_WG), dev->stream, RICH_ARGS(sched, n, 0));
         if (n_wide)
@@ -2085,36 +2076,23 @@ static int rich_write_pass(tri_batch *b) {
                 b->h_task_pos_base[i + 1] = b->h_task_pos_base[i] + th[i];
         const size_t total = b->h_task_pos_base[nt];
         if (total + 64 > b->rich_pool_cap) {
-                hipFree(b->d_rich_pool);
-                b->d_rich_pool = nullptr;
                 b->rich_pool_cap = total + total / 8 + 64;
-                HIP_TRY(hipMalloc((void **)&b->d_rich_pool, b->rich_pool_cap * 2));
+                HIP_TRY(b->d_rich_pool.alloc(b->rich_pool_cap * 2)); // (alloc: the old buffer is released first)
                 if (b->flags & TRI_FLAG_HIT_PAYLOADS) {
-                        hipFree(b->d_rich_plen);
-                        hipFree(b->d_rich_payload);
-                        b->d_rich_plen = nullptr;
-                        b->d_rich_payload = nullptr;
-                        HIP_TRY(hipMalloc((void **)&b->d_rich_plen, b->rich_pool_cap));
-                        HIP_TRY(hipMalloc((void **)&b->d_rich_payload, b->rich_pool_cap * 8));
+                        b->d_rich_plen.reset();
+                        b->d_rich_payload.reset();
+                        HIP_TRY(b->d_rich_plen.alloc(b->rich_pool_cap));
+                        HIP_TRY(b->d_rich_payload.alloc(b->rich_pool_cap * 8));
                 }
         }
         HIP_TRY(hipMemcpy(b->d_task_pos_base, b->h_task_pos_base.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemsetAsync(b->d_ticket + TICKET_RICH_WRITE_WORD, 0, (TICKET_RICH_WIDE + 1) * 4, dev->stream)); // (the wide instantiation's word too)
         // (a ranked batch: the WRITE pass and the rank pass timed apart — options rich_write_last_us / rank_last_us; the events go back to the handle's pool on
         //  every way out of the function)
-        struct RankEvents {
-                tri_dev *dev;
-                hipEvent_t e[3] = {};
-                ~RankEvents() {
-                        for (hipEvent_t x : e)
-                                if (x)
-                                        event_put(dev, x);
-                }
-        } rk{dev};
-        hipEvent_t(&rev)[3] = rk.e;
+        PooledEvent rev[3];
         if (b->rank_on) {
-                for (hipEvent_t &e : rev)
-                        HIP_TRY(event_get(dev, &e));
+                for (PooledEvent &e : rev)
+                        HIP_TRY(e.take(dev));
                 HIP_TRY(hipEventRecord(rev[0], dev->stream));
         }
         if (const int rc = launch_rich<true>(b))
@@ -2209,6 +2187,21 @@ static void reportable_tokens(const uint32_t *prog, const uint32_t plen, std::ve
         }
 }
 
+// the ranker's block (tri_batch::d_rank_block) at topk K: its sections named once, as batch_arena's are; zeroed from *zero_from on
+static size_t rank_block(tri_batch *b, uint8_t *base, const size_t K, size_t *zero_from) {
+        const size_t ns = b->sterms.size(), nt = b->tasks.size(), nq = b->nq;
+        Carver carve{base};
+        carve(b->d_rank_w, (ns + 1) * 8);
+        carve(b->d_rank_part_scores, (nt * K + 1) * 8);
+        carve(b->d_rank_part_docs, (nt * K + 1) * 4);
+        carve(b->d_rank_part_counts, (nt + 1) * 4);
+        *zero_from = carve.at;
+        carve(b->d_rank_scores, (nq * K + 1) * 8);
+        carve(b->d_rank_docs, (nq * K + 1) * 4);
+        carve(b->d_rank_counts, (nq + 1) * 4);
+        return carve.at;
+}
+
 extern "C" int tri_batch_set_ranker(tri_batch *b, const tri_ranker *spec, const double *weights) {
         if (!b)
                 return fail(TRI_ERR_INVALID, "tri_batch_set_ranker: null batch");
@@ -2235,8 +2228,7 @@ extern "C" int tri_batch_set_ranker(tri_batch *b, const tri_ranker *spec, const 
         HIP_TRY(hipSetDevice(dev->device));
         const uint32_t had = b->rank_on ? 2u + (b->n_rich_wide && b->tasks.size() > b->n_rich_wide ? 1u : 0u) : 0u; // (k_rich_rank per section of the schedule + k_rank_merge)
         if (!spec) {
-                pool_free(dev, b->d_rank_block);
-                b->d_rank_block = nullptr;
+                b->d_rank_block.reset();
                 b->rank_on = b->rank_done = false;
                 b->info.launches -= had;
                 return TRI_OK;
@@ -2265,31 +2257,16 @@ extern "C" int tri_batch_set_ranker(tri_batch *b, const tri_ranker *spec, const 
                         }
                 }
         }
-        size_t a = 0;
-        auto carve = [&](size_t bytes) {
-                const size_t at = a;
-                a += (bytes + 255) & ~(size_t)255;
-                return at;
-        };
-        const size_t a_w = carve((ns + 1) * 8), a_ps = carve((nt * K + 1) * 8), a_pd = carve((nt * K + 1) * 4), a_pc = carve((nt + 1) * 4), a_zero = a;
-        const size_t a_s = carve((nq * K + 1) * 8), a_d = carve((nq * K + 1) * 4), a_c = carve((nq + 1) * 4);
-        uint8_t *blk = nullptr;
-        HIP_TRY(pool_alloc(dev, (void **)&blk, a + 256));
-        // (the rows of queries the planner left out are never written: they stay zero)
-        if (hipMemsetAsync(blk + a_zero, 0, a - a_zero, dev->stream) != hipSuccess || hipMemcpyAsync(blk + a_w, w.data(), (ns + 1) * 8, hipMemcpyHostToDevice, dev->stream) != hipSuccess ||
-            hipStreamSynchronize(dev->stream) != hipSuccess) {
-                pool_free(dev, blk);
+        size_t a_zero = 0;
+        const size_t a = rank_block(b, nullptr, K, &a_zero);
+        Pooled<uint8_t> blk; // (the batch keeps the block it has until the new one stands)
+        HIP_TRY(blk.alloc(dev, a + 256));
+        // (the rows of queries the planner left out are never written: they stay zero; the weights open the block)
+        if (hipMemsetAsync(blk + a_zero, 0, a - a_zero, dev->stream) != hipSuccess || hipMemcpyAsync(blk, w.data(), (ns + 1) * 8, hipMemcpyHostToDevice, dev->stream) != hipSuccess ||
+            hipStreamSynchronize(dev->stream) != hipSuccess)
                 return fail(TRI_ERR_DEVICE, "tri_batch_set_ranker: %s", hipGetErrorString(hipGetLastError()));
-        }
-        pool_free(dev, b->d_rank_block);
-        b->d_rank_block = blk;
-        b->d_rank_w = (double *)(blk + a_w);
-        b->d_rank_part_scores = (double *)(blk + a_ps);
-        b->d_rank_part_docs = (uint32_t *)(blk + a_pd);
-        b->d_rank_part_counts = (uint32_t *)(blk + a_pc);
-        b->d_rank_scores = (double *)(blk + a_s);
-        b->d_rank_docs = (uint32_t *)(blk + a_d);
-        b->d_rank_counts = (uint32_t *)(blk + a_c);
+        b->d_rank_block = std::move(blk);
+        rank_block(b, b->d_rank_block, K, &a_zero);
         b->rank = *spec;
         b->rank_on = true;
         b->rank_done = false;
@@ -2299,41 +2276,28 @@ extern "C" int tri_batch_set_ranker(tri_batch *b, const tri_ranker *spec, const 
 
 // a collection batch (tri_cbatch_create ... below: "collections of segments"; here, because its result calls are read_side.hpp's too)
 struct tri_cbatch {
+        DevRef dev; // (first: released last.  The collection's own reference: its parts may be destroyed before it)
         std::vector<tri_batch *> parts;
-        std::vector<uint32_t *> d_slots; // per part: caller query -> plan slot
-        DevSource *d_src = nullptr;
-        uint32_t *d_top_docs = nullptr, *d_top_counts = nullptr;
-        float *d_top_scores = nullptr;
-        uint64_t *d_counts = nullptr;
+        std::vector<DevMem<uint32_t>> d_slots; // per part: caller query -> plan slot
+        DevMem<DevSource> d_src;
+        DevMem<uint32_t> d_top_docs, d_top_counts;
+        DevMem<float> d_top_scores;
+        DevMem<uint64_t> d_counts;
         // tri_cbatch_ranked (k_rank_merge_sources): the merged [nq][rank_k] blocks and the parts' {docs, scores, counts} table — allocated by the first run that finds
         // the collection ranked (every part carries a ranker, all tri_ranker structs bytewise equal), re-sized when topk changed; rank_why: why a run was not ranked
         bool ranked = false;
         uint32_t rank_k = 0;
-        uint32_t *d_rank_docs = nullptr, *d_rank_counts = nullptr;
-        double *d_rank_scores = nullptr;
-        DevRankSource *d_rank_src = nullptr;
+        DevMem<uint32_t> d_rank_docs, d_rank_counts;
+        DevMem<double> d_rank_scores;
+        DevMem<DevRankSource> d_rank_src;
         std::vector<DevRankSource> rank_src;
         std::string rank_why;
-        hipEvent_t rank_ev[2] = {}; // around the merge kernel (option crank_merge_last_us)
+        PooledEvent rank_ev[2]; // around the merge kernel (option crank_merge_last_us)
         bool rank_timed = false;
         bool ran = false, synced = false;
         ~tri_cbatch() {
-                if (!parts.empty())
-                        hipSetDevice(parts[0]->ix->dev->device);
-                for (auto p : d_slots)
-                        hipFree(p);
-                hipFree(d_src);
-                hipFree(d_top_docs);
-                hipFree(d_top_counts);
-                hipFree(d_top_scores);
-                hipFree(d_counts);
-                hipFree(d_rank_docs);
-                hipFree(d_rank_scores);
-                hipFree(d_rank_counts);
-                hipFree(d_rank_src);
-                for (hipEvent_t e : rank_ev)
-                        if (e)
-                                hipEventDestroy(e);
+                if (dev)
+                        hipSetDevice(dev->device);
         }
 };
 
@@ -2350,10 +2314,9 @@ namespace {
         int filter_new(tri_index *ix, std::unique_ptr<tri_filter> &f) {
                 f = std::make_unique<tri_filter>();
                 f->ix = ix;
-                f->dev = ix->dev;
-                dev_retain(ix->dev);
+                f->dev.retain(ix->dev);
                 f->words = filter_words(ix);
-                HIP_TRY(pool_alloc(ix->dev, (void **)&f->d_bits, f->words * 4));
+                HIP_TRY(f->d_bits.alloc(ix->dev, f->words * 4));
                 return TRI_OK;
         }
         // KEEP: the allow-list's bitmap becomes the drop bitmap; then wait for the filter to stand
@@ -2361,16 +2324,14 @@ namespace {
                 tri_dev *dev = f->dev;
                 if (mode == TRI_FILTER_KEEP) {
                         const size_t n4 = f->words / 4;
-                        hipLaunchKernelGGL(k_filter_complement, dim3((unsigned)std::min<size_t>((n4 + FILTER_WG - 1) / FILTER_WG, 1024)), dim3(FILTER_WG), 0, dev->stream, (uint4 *)f->d_bits, n4);
+                        hipLaunchKernelGGL(k_filter_complement, dim3((unsigned)std::min<size_t>((n4 + FILTER_WG - 1) / FILTER_WG, 1024)), dim3(FILTER_WG), 0, dev->stream, (uint4 *)f->d_bits.get(), n4);
                         HIP_TRY(hipGetLastError());
                 }
-                hipEvent_t done = nullptr;
-                HIP_TRY(event_get(dev, &done));
+                PooledEvent done;
+                HIP_TRY(done.take(dev));
                 const hipError_t e = hipEventRecord(done, dev->stream);
                 lock.unlock(); // (the wait stands outside the lock, like tri_batch_sync's)
-                const hipError_t e2 = e == hipSuccess ? hipEventSynchronize(done) : e;
-                event_put(dev, done);
-                HIP_TRY(e2);
+                HIP_TRY(e == hipSuccess ? hipEventSynchronize(done) : e);
                 return TRI_OK;
         }
 } // namespace
@@ -2385,16 +2346,11 @@ extern "C" int tri_filter_create(tri_index *ix, const uint32_t *docids, size_t n
         std::unique_ptr<tri_filter> f;
         if (const int rc = filter_new(ix, f))
                 return rc;
-        uint32_t *d_ids = nullptr;
-        struct Staging { // (released on every way out)
-                tri_dev *dev;
-                uint32_t *&p;
-                ~Staging() { pool_free(dev, p); }
-        } staging{dev, d_ids};
+        Pooled<uint32_t> d_ids; // (the docID list's staging buffer: released on every way out)
         std::unique_lock<std::recursive_mutex> lock(dev->mu);
         HIP_TRY(hipMemsetAsync(f->d_bits, 0, f->words * 4, dev->stream));
         if (n) {
-                HIP_TRY(pool_alloc(dev, (void **)&d_ids, n * 4));
+                HIP_TRY(d_ids.alloc(dev, n * 4));
                 HIP_TRY(hipMemcpyAsync(d_ids, docids, n * 4, hipMemcpyHostToDevice, dev->stream)); // (pageable source: staged before the call returns)
                 hipLaunchKernelGGL(k_filter_scatter, dim3((unsigned)std::min<size_t>((n + FILTER_WG - 1) / FILTER_WG, 4096)), dim3(FILTER_WG), 0, dev->stream, (const uint32_t *)d_ids, n,
                                    ix->max_doc, f->d_bits);
@@ -2448,7 +2404,7 @@ extern "C" int tri_filter_from_docset(tri_batch *b, size_t q, int mode, tri_filt
 }
 
 extern "C" void tri_filter_destroy(tri_filter *f) {
-        delete f; // ~tri_filter hands the bitmap back
+        delete f; // its d_bits hands the bitmap back
 }
 
 extern "C" int tri_batch_set_filters(tri_batch *b, tri_filter *const *filters, size_t nf, const uint32_t *filter_of_query) {
@@ -2490,19 +2446,21 @@ extern "C" int tri_batch_set_filters(tri_batch *b, tri_filter *const *filters, s
         if (rows.size() > b->filter_rows_cap || !b->d_filter_tab) {
                 if (b->ran && !b->synced) // (a run in flight reads the buffers that are about to go back to the pool)
                         HIP_TRY(hipStreamSynchronize(dev->stream));
-                pool_free(dev, b->d_filter_tab);
-                pool_free(dev, b->d_filter_rows);
-                b->d_filter_tab = nullptr, b->d_filter_rows = nullptr, b->filter_rows_cap = 0;
+                b->d_filter_tab.reset();
+                b->d_filter_rows.reset();
+                b->filter_rows_cap = 0;
                 b->filter_rows.clear();
-                HIP_TRY(pool_alloc(dev, (void **)&b->d_filter_tab, ptrs_off + std::max(rows.size(), b->nq) * sizeof(void *)));
-                HIP_TRY(pool_alloc(dev, (void **)&b->d_filter_rows, rows.size() * stride * 4));
+                HIP_TRY(b->d_filter_tab.alloc(dev, ptrs_off + std::max(rows.size(), b->nq) * sizeof(void *)));
+                HIP_TRY(b->d_filter_rows.alloc(dev, rows.size() * stride * 4));
                 b->filter_rows_cap = rows.size();
         }
         // one block — [row id per slot][source pointer per row] — on the engine stream: behind the runs already queued, which keep the assignment they were launched with
         std::vector<uint8_t> tab(ptrs_off + rows.size() * sizeof(void *), 0);
         memcpy(tab.data(), row_of_slot.data(), nslots * 4);
-        for (size_t r = 0; r < rows.size(); ++r)
-                memcpy(tab.data() + ptrs_off + r * sizeof(void *), &rows[r]->d_bits, sizeof(void *));
+        for (size_t r = 0; r < rows.size(); ++r) {
+                const uint32_t *bits = rows[r]->d_bits;
+                memcpy(tab.data() + ptrs_off + r * sizeof(void *), &bits, sizeof(void *));
+        }
         HIP_TRY(hipMemcpyAsync(b->d_filter_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, dev->stream)); // (pageable source: staged before the call returns)
         b->filter_rows = std::move(rows);
         return TRI_OK;
@@ -2526,25 +2484,24 @@ extern "C" int tri_cbatch_create(tri_batch *const *parts, size_t n, tri_cbatch *
         tri_dev *dev = parts[0]->ix->dev;
         HIP_TRY(hipSetDevice(dev->device));
         auto c = std::make_unique<tri_cbatch>();
+        c->dev.retain(dev);
         c->parts.assign(parts, parts + n);
         const size_t nq = parts[0]->nq, k = parts[0]->topk;
         std::vector<DevSource> src(n);
+        c->d_slots.resize(n);
         for (size_t i = 0; i < n; ++i) {
-                uint32_t *d = nullptr;
-                int rc;
-                if ((rc = dev_upload(&d, parts[i]->slot_of_query)))
+                if (const int rc = dev_upload(c->d_slots[i], parts[i]->slot_of_query))
                         return rc;
-                c->d_slots.push_back(d);
-                src[i] = {parts[i]->dev_at(parts[i]->plan), d, parts[i]->d_part_docs, parts[i]->d_part_scores, parts[i]->d_part_counts, parts[i]->d_qcounts};
+                src[i] = {parts[i]->dev_at(parts[i]->plan), c->d_slots[i], parts[i]->d_part_docs, parts[i]->d_part_scores, parts[i]->d_part_counts, parts[i]->d_qcounts};
         }
         int rc;
-        if ((rc = dev_upload(&c->d_src, src)))
+        if ((rc = dev_upload(c->d_src, src)))
                 return rc;
-        HIP_TRY(hipMalloc((void **)&c->d_counts, (nq + 1) * 8));
+        HIP_TRY(c->d_counts.alloc((nq + 1) * 8));
         if ((parts[0]->flags & TRI_FLAG_ACCUMULATED_SCORE) && k) {
-                HIP_TRY(hipMalloc((void **)&c->d_top_docs, (nq * k + 1) * 4));
-                HIP_TRY(hipMalloc((void **)&c->d_top_scores, (nq * k + 1) * 4));
-                HIP_TRY(hipMalloc((void **)&c->d_top_counts, (nq + 1) * 4));
+                HIP_TRY(c->d_top_docs.alloc((nq * k + 1) * 4));
+                HIP_TRY(c->d_top_scores.alloc((nq * k + 1) * 4));
+                HIP_TRY(c->d_top_counts.alloc((nq + 1) * 4));
         }
         *out = c.release();
         return TRI_OK;
@@ -2603,17 +2560,17 @@ static int cbatch_rank_prepare(tri_cbatch *c) {
         DevLock dev_lock(dev->mu);
         HIP_TRY(hipSetDevice(dev->device));
         if (c->rank_k != k) { // (no merge of an earlier run is in flight: tri_cbatch_sync waits for the one it queues)
-                hipFree(c->d_rank_docs);
-                hipFree(c->d_rank_scores);
-                hipFree(c->d_rank_counts);
-                c->d_rank_docs = c->d_rank_counts = nullptr, c->d_rank_scores = nullptr, c->rank_k = 0;
-                HIP_TRY(hipMalloc((void **)&c->d_rank_docs, (nq * k + 1) * 4));
-                HIP_TRY(hipMalloc((void **)&c->d_rank_scores, (nq * k + 1) * 8));
-                HIP_TRY(hipMalloc((void **)&c->d_rank_counts, (nq + 1) * 4));
+                c->d_rank_docs.reset();
+                c->d_rank_scores.reset();
+                c->d_rank_counts.reset();
+                c->rank_k = 0;
+                HIP_TRY(c->d_rank_docs.alloc((nq * k + 1) * 4));
+                HIP_TRY(c->d_rank_scores.alloc((nq * k + 1) * 8));
+                HIP_TRY(c->d_rank_counts.alloc((nq + 1) * 4));
                 c->rank_k = (uint32_t)k;
         }
         if (!c->d_rank_src)
-                HIP_TRY(hipMalloc((void **)&c->d_rank_src, n * sizeof(DevRankSource)));
+                HIP_TRY(c->d_rank_src.alloc(n * sizeof(DevRankSource)));
         c->rank_src.resize(n);
         for (size_t i = 0; i < n; ++i)
                 c->rank_src[i] = {c->parts[i]->d_rank_docs, c->parts[i]->d_rank_scores, c->parts[i]->d_rank_counts};
@@ -2640,9 +2597,9 @@ static int cbatch_rank_merge(tri_cbatch *c) {
                 return TRI_OK;
         DevLock dev_lock(dev->mu);
         HIP_TRY(hipSetDevice(dev->device));
-        for (hipEvent_t &e : c->rank_ev)
+        for (PooledEvent &e : c->rank_ev)
                 if (!e)
-                        HIP_TRY(hipEventCreate(&e));
+                        HIP_TRY(e.take(dev));
         HIP_TRY(hipEventRecord(c->rank_ev[0], dev->stream));
         hipLaunchKernelGGL(k_rank_merge_sources, dim3((uint32_t)((lanes + AND_WG - 1) / AND_WG)), dim3(AND_WG), 0, dev->stream, (const DevRankSource *)c->d_rank_src,
                            (uint32_t)c->parts.size(), (uint32_t)c->parts[0]->nq, c->rank_k, c->d_rank_docs, c->d_rank_scores, c->d_rank_counts);

@@ -14,25 +14,23 @@ namespace {
 // it when the call returns — after the stream has drained, so that an early error return hands no buffer back that a kernel still works on
 struct WriteScratch {
         tri_dev *dev;
-        std::vector<void *> held;
+        std::vector<Pooled<void>> held;
         uint64_t *scan_sums = nullptr; // (enc_scan's chunk sums, grown on demand)
         uint64_t scan_cap = 0;
         explicit WriteScratch(tri_dev *d) : dev(d) {}
         WriteScratch(const WriteScratch &) = delete;
         WriteScratch &operator=(const WriteScratch &) = delete;
-        ~WriteScratch() {
+        ~WriteScratch() { // (the drain comes first; `held` releases its buffers behind it)
                 if (!held.empty())
                         hipStreamSynchronize(dev->stream);
-                for (void *q : held)
-                        pool_free(dev, q);
         }
         template <class T>
         hipError_t get(T *&p, const size_t count) {
-                void *q = nullptr;
-                const hipError_t e = pool_alloc(dev, &q, count ? count * sizeof(T) : 8);
+                Pooled<void> q;
+                const hipError_t e = q.alloc(dev, count ? count * sizeof(T) : 8);
+                p = (T *)q.get();
                 if (e == hipSuccess)
-                        held.push_back(q);
-                p = (T *)q;
+                        held.push_back(std::move(q));
                 return e;
         }
 };
