@@ -651,3 +651,22 @@ def mixed_queries(c):
     at a word offset of the one-call delivery that is not a multiple of four."""
     out = ["{df33}", "{all} OR {odd}", "{first1} OR {last1}", "{all} {odd}", "{df31}", "{all} OR {edges}", "{df129}", "{odd} OR {holes}", "{df127}", "{all} NOT {lastwin}"]
     return [(c.q(t), 1) for t in out]
+
+
+# ---- the walk k_score and k_rich share (a term's blocks against a tile of matches) ---------------------------------------------------------------------------------------------
+D_WALK = 8192 + 37
+WALK_FEW = [5, 6, 40, D_WALK - 5, D_WALK - 2]  # by rank in `all` (docIDs start at 1): 5 and 6 share block 0; D - 5 is the last document of the last full block, D - 2 lies in the short block after it
+
+
+def walk_corpus():
+    """`all` (every docID of D = 8192 + 37: 258 blocks, the last one short), `third` (every third), `few` (five documents); frequencies cycle 1, 2, 3 by rank and
+    the positions are written (1 .. f).  Not in CORPORA: two queries, for tests/test_gpu_match_walk.py alone."""
+    ar = np.arange(1, D_WALK + 1, dtype=np.int64)
+    L = {"all": ar, "third": ar[ar % 3 == 0], "few": np.array(WALK_FEW, dtype=np.int64)}
+    return build({k: (_u32(d), 1 + np.arange(d.size) % 3) for k, d in L.items()})
+
+
+def walk_queries(c):
+    """`few AND all`: 5 matches against 258 blocks in range — match-driven; `all AND third`: 2 743 matches (two tiles of k_rich's 2048) against no more blocks
+    than matches — block-driven."""
+    return [(c.q("{few} {all}"), 1), (c.q("{all} {third}"), 1)]

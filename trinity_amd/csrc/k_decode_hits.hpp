@@ -316,15 +316,7 @@ __global__ __launch_bounds__(256) void k_hits_at_freq(const uint8_t *__restrict_
         const uint32_t target = pair_doc[i];
         uint32_t freq = DH_ABSENT, slot = DH_ABSENT, before = 0;
         const uint32_t *bl = blk_last + t.first_block;
-        uint32_t lo = 0, hi = t.nblocks; // the first block whose last document is >= target
-        while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (bl[mid] < target)
-                        lo = mid + 1;
-                else
-                        hi = mid;
-        }
-        const uint32_t b = lo;
+        const uint32_t b = first_ge(bl, 0u, t.nblocks, target); // the first block whose last document is >= target
         if (b < t.nblocks && target) {
                 const uint32_t off = blk_off[t.first_block + b];
                 const uint32_t n = TRI_BLOCK_N(t, b, index, off);

@@ -192,15 +192,7 @@ template <int CODEC>
 __device__ __noinline__ uint32_t fused_lookup_freq(const uint8_t *__restrict__ index, const uint32_t *__restrict__ blk_last, const uint32_t *__restrict__ blk_off,
                                                    const DevTerm &t, const uint32_t doc) {
         const uint32_t *bl = blk_last + t.first_block;
-        uint32_t lo = 0, hi = t.nblocks;
-        while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (bl[mid] < doc)
-                        lo = mid + 1;
-                else
-                        hi = mid;
-        }
-        const uint32_t b = lo;
+        const uint32_t b = first_ge(bl, 0u, t.nblocks, doc);
         const uint32_t off = blk_off[t.first_block + b];
         const uint32_t n = TRI_BLOCK_N(t, b, index, off);
         uint32_t d = b ? bl[b - 1] : 0, pos = n - 1;
@@ -346,6 +338,22 @@ __device__ __forceinline__ void row_decode(const uint8_t *__restrict__ index, co
                 }
         }
         row_streams<CODEC, NEEDF, POST>(index, t, b, rec_x, n, prev, last, w0, post, rec_y);
+}
+
+// Row b of term t into `post`, from the directory columns of whichever codec: LUCENE's row record (blk_rec); GOOGLE's payload offset (blk_off) and the
+// byte length of the block's deltas (the freqs start where they end: the difference of two blk_doff entries).
+template <int CODEC, bool NEEDF, class POST>
+__device__ __forceinline__ void decode_row(const uint8_t *__restrict__ index, const uint32_t *__restrict__ blk_off, const uint4 *__restrict__ blk_rec,
+                                           const uint32_t *__restrict__ blk_doff, const DevTerm &t, const uint32_t b, const uint32_t prev, const uint32_t last,
+                                           const uint32_t w0, POST &post PROF_ARG) {
+        if (CODEC == CODEC_LUCENE) {
+                const uint4 rec = blk_rec[t.first_block + b];
+                row_decode<CODEC, NEEDF, POST>(index, t, b, rec.x, rec.y, rec.z, rec.w, TRI_BLOCK_N(t, b, index, 0), prev, last, w0, post PROF_PASS);
+        } else {
+                const uint32_t off = blk_off[t.first_block + b];
+                const uint32_t dlen = blk_doff[t.first_block + b + 1] - blk_doff[t.first_block + b] - 1u;
+                row_decode<CODEC, NEEDF, POST>(index, t, b, off, dlen, 0, 0, TRI_BLOCK_N(t, b, index, off), prev, last, w0, post PROF_PASS);
+        }
 }
 
 // k_fused's form: the row into the window words; returns the row's first document past the window as rel - W (>= 2^31: none).
@@ -512,12 +520,7 @@ __device__ __forceinline__ void fused_sweep(FusedShared &sh, const uint32_t w0, 
         const uint32_t wave = uni(threadIdx.x >> 6);
         constexpr uint32_t DPW = HW ? 2 : 1; // documents per word
         // (the lane's word address is recomputed per chunk from the hardware lane count: kept in a register across the flush calls it
-        //  was spilled, and every chunk began with a scratch round trip)
-        auto lane_id = []() {
-                uint32_t l;
-                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-                return l;
-        };
+        //  was spilled, and every chunk began with a scratch round trip: lane_id(), wave_prims.hpp)
         uint32_t wn = 0;                     // entries on this wave's list (wave-uniform)
         const uint32_t fmode = (GEN && PK == 2) ? uni(sh.fq.mode) : 0u, tt_nslots = (GEN && PK == 2) ? uni(sh.fq.nslots) : 0u,
                        tt_fbits = (GEN && PK == 2) ? uni(sh.fq.fbits) : 0u, tt_fmask = (1u << tt_fbits) - 1u;
@@ -682,13 +685,7 @@ __global__ __launch_bounds__(FUS_WG, (FUS_WGS_PER_CU * FUS_WG + 255) / 256) void
         PROF_DECL;
         PROF_START();
         for (;;) {
-                if (wave == 0) { // uniform draw (see k_and)
-                        const uint32_t old = atomicAdd(ticket, 1u);
-                        sh.bcast[0] = uni(old) >> 6;
-                }
-                __syncthreads();
-                const uint32_t ticket_no = uni(sh.bcast[0]);
-                __syncthreads();
+                const uint32_t ticket_no = draw_task(sh.bcast, ticket, wave);
                 if (ticket_no >= ntasks)
                         break;
                 const uint32_t tix = sched[ticket_no];
@@ -763,16 +760,7 @@ __global__ __launch_bounds__(FUS_WG, (FUS_WGS_PER_CU * FUS_WG + 255) / 256) void
                                 e_hi = win[myt.win_off + (wfirst + 1) * CELLS];
                                 pf = win[myt.win_off + (wfirst + 2) * CELLS];
                         } else {
-                                uint32_t lo = 0, hi = myt.nblocks; // first block whose last document >= the task's first docID
-                                const uint32_t key = wfirst * W;
-                                while (lo < hi) {
-                                        const uint32_t mid = (lo + hi) >> 1;
-                                        if (mybl[mid] < key)
-                                                lo = mid + 1;
-                                        else
-                                                hi = mid;
-                                }
-                                cur = lo;
+                                cur = first_ge(mybl, 0u, myt.nblocks, wfirst * W); // first block whose last document >= the task's first docID
                                 e_lo = cur < myt.nblocks ? mybl[cur] : 0xffffffffu; // (short lists: e_lo / e_hi hold the cursor block's last / previous docID)
                                 e_hi = cur ? mybl[cur - 1] : 0u;
                         }

@@ -250,15 +250,7 @@ __global__ __launch_bounds__(64) void k_isect_runs(const uint64_t *__restrict__ 
                         const bool in = ((grp >> lane) & 1ull) && d >= t;
                         uint32_t e = 0;
                         if (in) { // epoch: the bounds at or below d
-                                uint32_t lo = 0, hi = q.nbounds;
-                                while (lo < hi) {
-                                        const uint32_t mid = (lo + hi) >> 1;
-                                        if (bd[mid] <= d)
-                                                lo = mid + 1;
-                                        else
-                                                hi = mid;
-                                }
-                                e = lo;
+                                e = first_gt(bd, 0u, q.nbounds, d);
                         }
                         uint64_t rem2 = __ballot(in);
                         while (rem2) {

@@ -2,46 +2,19 @@
 // Part of libtrinity_hip.so (MI355X / gfx950); included by trinity_hip.hip.  New code, no reference source.
 #pragma once
 #include "codec_streams.hpp"
+#include "dev_search.hpp" // (first_ge / first_gt / gallop_ge, term_block_range: the kernels' scalar searches)
+#include "wave_prims.hpp" // (uni, lane_id, wave_excl_scan, row8_incl_scan, draw_task)
 
 // ------------------------------------------------------------------------------------------ k_and
 constexpr int AND_WG = 256;   // candidate-tile kernel (k_and) and the scoring kernels
 constexpr int DENSE_WG = 512; // bitmap-window kernel (k_and_dense): 8 waves share one 38 KB window state
 static_assert(TILE_BLOCKS == AND_WG, "the candidate kernel maps one 32-candidate row to each of its 256 lanes"); // (TILE_BLOCKS, TILE_CANDS: dev_structs.hpp)
 
-// Values that are workgroup-uniform by construction but read back from LDS look divergent to the compiler; a
-// loop whose exit depends on one gets exec-masked structurisation, which is fatal around s_barrier (lanes
-// "leave" the loop at different times).  uni() pins such values into an SGPR so the branch is scalar.
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 #include "k_filter.hpp" // (per-query document filters: FilterSel / filter_pick, which every kernel that drops masked documents calls once per task)
 
 // LDS candidate layout: logical slot j lives at phys(j); rotating each 32-slot row by its row number keeps
 // the one-lane-per-row writes of the lead decode (lane t writes row t, column i) off a single bank.
 __device__ __forceinline__ uint32_t phys(uint32_t j) { return (j & ~31u) | ((j + (j >> 5)) & 31u); }
-
-// Exclusive prefix sum across the wave's 64 lanes (every lane active) and the wave's total.  Six DPP adds — within each row of 16 lanes by row_shr:1 / 2 / 4 / 8, then
-// row_bcast:15 carries rows 0 / 2's sums into rows 1 / 3 and row_bcast:31 the lower half's into the upper — and a v_readlane: no LDS crossbar trips (until round 6 this was
-// six __shfl_up steps: a ds_bpermute_b32 and an s_waitcnt lgkmcnt(0) each, a chain of seven LDS round trips per scan in k_psets' / k_and's inner loops).
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t &total) {
-        uint32_t x = v;
-        // (written out: left to the compiler, an update_dpp + add pair became v_mov 0 / v_mov_dpp / v_add — eighteen instructions — where registers were tight.  A VALU
-        //  result read by a DPP instruction wants two wait states: the s_nop 1 between them; the ones at the ends stand for what the compiler cannot see into)
-        asm volatile("s_nop 1\n\t"
-                     "v_add_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "s_nop 1\n\t"
-                     "v_add_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "s_nop 1\n\t"
-                     "v_add_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "s_nop 1\n\t"
-                     "v_add_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "s_nop 1\n\t"
-                     "v_add_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-                     "s_nop 1\n\t"
-                     "v_add_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-                     "s_nop 1"
-                     : "+v"(x));
-        total = (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-        return x - v;
-}
 
 // (SPAN_BITS, SPAN_WORDS, CELL_LOG2, CELL_DOCS, CELLS_PER_SPAN: dev_structs.hpp — the host planner cuts tasks by them)
 // Window bitmap layout in LDS: logical word w lives at bm[w + (w >> 5)] — every row of 32 words is followed by one pad
@@ -150,24 +123,9 @@ __device__ __forceinline__ bool load_block_bytes32(const uint8_t *__restrict__ p
         return block_bytes32_finish(p, r, v);
 }
 
-// The first candidate at or behind `ptr` that is >= doc (C: none), found by GALLOPING from ptr: a block of a rare term spans the docID range of
-// thousands of candidates, and the lane that merges it must not walk them one by one (measured: a 21-document list against a tile of 8192
-// candidates took 680 us of single-lane LDS reads — cfg3's k_and spent half its span in a handful of such tiles)
-__device__ __forceinline__ uint32_t cand_gallop(const AndShared &sh, uint32_t ptr, const uint32_t C, const uint32_t doc) {
-        uint32_t step = 1, lo = ptr;
-        while (lo + step <= C && sh.cand[phys(lo + step - 1)] < doc) {
-                lo += step;
-                step <<= 1;
-        }
-        uint32_t hi = min(lo + step - 1, C);
-        while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (sh.cand[phys(mid)] < doc)
-                        lo = mid + 1;
-                else
-                        hi = mid;
-        }
-        return lo;
+// The first candidate at or behind `ptr` that is >= doc (C: none): gallop_ge (dev_search.hpp) through the rotated LDS layout
+__device__ __forceinline__ uint32_t cand_gallop(const AndShared &sh, const uint32_t ptr, const uint32_t C, const uint32_t doc) {
+        return gallop_ge([&sh](const uint32_t j) { return sh.cand[phys(j)]; }, ptr, C, doc);
 }
 
 // Merge one block of term t against the candidates from `ptr` on (cv = candidate at ptr): set the hit bit of every
@@ -329,15 +287,7 @@ __device__ void and_filter_tile(AndShared &sh, const uint8_t *__restrict__ index
                                 beyond = last >= cmax;
                                 if (prev < cmax) {
                                         // first candidate > prev
-                                        uint32_t lo = 0, hi = C;
-                                        while (lo < hi) {
-                                                const uint32_t mid = (lo + hi) >> 1;
-                                                if (sh.cand[phys(mid)] <= prev)
-                                                        lo = mid + 1;
-                                                else
-                                                        hi = mid;
-                                        }
-                                        uint32_t ptr = lo;
+                                        uint32_t ptr = first_gt([&sh](const uint32_t j) { return sh.cand[phys(j)]; }, 0u, C, prev);
                                         uint32_t cv = ptr < C ? sh.cand[phys(ptr)] : 0xffffffffu;
                                         PROF_LAP(6);
                                         if (cv <= last) {
@@ -390,15 +340,7 @@ __device__ void and_filter_tile(AndShared &sh, const uint8_t *__restrict__ index
                         }
                         if (j < C) {
                                 cv = sh.cand[phys(j)];
-                                uint32_t lo = rlo, hi = rhi; // first block with last >= cv lies in [rlo, rhi]
-                                while (lo < hi) {
-                                        const uint32_t mid = (lo + hi) >> 1;
-                                        if (bl[mid] < cv)
-                                                lo = mid + 1;
-                                        else
-                                                hi = mid;
-                                }
-                                bj = lo; // == nblocks: beyond the list
+                                bj = first_ge(bl, rlo, rhi, cv); // first block with last >= cv lies in [rlo, rhi]; == nblocks: beyond the list
                         }
                         uint32_t prevb = __shfl_up(bj, 1, 64);
                         if ((tid & 63u) == 0)
@@ -1024,13 +966,7 @@ __global__ __launch_bounds__(DENSE_WG, TRI_DENSE_WAVES) void k_and_dense(const u
         PROF_DECL;
         PROF_START();
         for (;;) {
-                if (wave == 0) { // uniform draw: 64 lanes add 1 each (one +64 atomic), see k_and
-                        const uint32_t old = atomicAdd(ticket, 1u);
-                        sh.bcast[0] = uni(old) >> 6;
-                }
-                __syncthreads();
-                const uint32_t ticket_no = uni(sh.bcast[0]);
-                __syncthreads();
+                const uint32_t ticket_no = draw_task(sh.bcast, ticket, wave);
                 if (ticket_no >= ntasks)
                         break;
                 const uint32_t tix = sched[ticket_no];

@@ -66,6 +66,13 @@ __device__ __forceinline__ uint32_t rank_rec_word(const uint32_t first /* the gr
                 before += i < (k >> 1) ? (uint32_t)__popc(w8[i]) : 0u;
         return before;
 }
+// ... the first n words of a workgroup's records: rdir[g] = group g's first posting, pl = its plane 0 (both in LDS; every thread of the workgroup calls)
+__device__ __forceinline__ void write_rank_records(uint32_t *__restrict__ rec, const uint32_t *rdir, const uint32_t *pl, const uint32_t n) {
+        for (uint32_t i = threadIdx.x; i < n; i += AND_WG) {
+                const uint32_t g = i / PL_RANK_WORDS, k = i % PL_RANK_WORDS;
+                rec[i] = rank_rec_word(rdir[g], pl + 8u * g, k);
+        }
+}
 
 // One workgroup per (plane row, window): the rows (<= 32 documents each) of the term that reach the window are decoded, one lane
 // per row, into LDS planes, which are then written out whole — every word of every plane is written by exactly one workgroup,
@@ -91,32 +98,9 @@ __global__ __launch_bounds__(AND_WG) void k_term_planes(const uint8_t *__restric
         const uint32_t w0 = w * PL_W;
         // rows that can hold documents of [w0, w0 + PL_W): first row whose last docID >= w0 ... first row whose last docID >= the next
         // window's first docID (it may still begin inside this one)
-        uint32_t b_lo, b_hi;
-        if (t.win_off != 0xffffffffu) {
-                b_lo = win[t.win_off + w * PL_CELLS];
-                b_hi = win[t.win_off + (w + 1) * PL_CELLS];
-        } else { // (a short list: planes are made for long ones, but the planner may be told to give every term one)
-                uint32_t lo = 0, hi = t.nblocks;
-                while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (bl[mid] < w0)
-                                lo = mid + 1;
-                        else
-                                hi = mid;
-                }
-                b_lo = lo;
-                hi = t.nblocks;
-                while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (bl[mid] < w0 + PL_W)
-                                lo = mid + 1;
-                        else
-                                hi = mid;
-                }
-                b_hi = lo;
-        }
-        b_lo = uni(b_lo);
-        b_hi = uni(min(b_hi, t.nblocks - 1));
+        // (a short list bisects its directory: planes are made for long ones, but the planner may be told to give every term one)
+        const BlockRange r = term_block_range(bl, win, t, w0, w0 + PL_W);
+        const uint32_t b_lo = uni(r.lo), b_hi = uni(min(r.hi, t.nblocks - 1));
         __syncthreads();
         if (b_lo < t.nblocks)
                 for (uint32_t b = b_lo + tid; b <= b_hi; b += AND_WG) {
@@ -125,24 +109,14 @@ __global__ __launch_bounds__(AND_WG) void k_term_planes(const uint8_t *__restric
 #ifdef TRI_PROF
                         ProfClock prof_;
 #endif
-                        if (CODEC == CODEC_LUCENE) {
-                                const uint4 rec = blk_rec[t.first_block + b];
-                                row_decode<CODEC, true, PlanePost>(index, t, b, rec.x, rec.y, rec.z, rec.w, TRI_BLOCK_N(t, b, index, 0), prev, last, w0, post PROF_PASS);
-                        } else {
-                                const uint32_t off = blk_off[t.first_block + b];
-                                const uint32_t dlen = blk_doff[t.first_block + b + 1] - blk_doff[t.first_block + b] - 1u;
-                                row_decode<CODEC, true, PlanePost>(index, t, b, off, dlen, 0, 0, TRI_BLOCK_N(t, b, index, off), prev, last, w0, post PROF_PASS);
-                        }
+                        decode_row<CODEC, true, PlanePost>(index, blk_off, blk_rec, blk_doff, t, b, prev, last, w0, post PROF_PASS);
                 }
         __syncthreads();
         uint32_t *pa = planes0 + (size_t)row * stride0 + (size_t)w * PL_WORDS;
         if (prank) { // (rank of a document = its group's entry + the plane-0 bits of the group before it, both in ONE 64-byte record: k_phrase.hpp)
                 static_assert(PL_RANK_DOCS == 256 && PL_RANK_WORDS == 16, "a record: eight (rank, plane-0 word) pairs, one cache line");
                 uint32_t *rec = prank + ((size_t)row * (plw / (PL_RANK_DOCS / 32u)) + (size_t)w * (PL_W / PL_RANK_DOCS)) * PL_RANK_WORDS;
-                for (uint32_t i = tid; i < (PL_W / PL_RANK_DOCS) * PL_RANK_WORDS; i += AND_WG) {
-                        const uint32_t g = i / PL_RANK_WORDS, k = i % PL_RANK_WORDS;
-                        rec[i] = rank_rec_word(rdir[g], pl + 8u * g, k);
-                }
+                write_rank_records(rec, rdir, pl, (PL_W / PL_RANK_DOCS) * PL_RANK_WORDS);
         }
         if (!hi) { // plane 0 alone: all a DocumentsOnly batch reads
                 for (uint32_t i = tid; i < PL_WORDS; i += AND_WG)
@@ -208,32 +182,8 @@ __global__ __launch_bounds__(AND_WG) void k_term_plane0(const uint8_t *__restric
         const uint32_t *bl = blk_last + t.first_block;
         const uint32_t w0 = wfirst * PL_W, w1 = w0 + wn * PL_W; // (the planner keeps max docID below 2^31: no wrap)
         // rows that can hold documents of [w0, w1): first row whose last docID >= w0 ... first row whose last docID >= w1 (it may still begin inside)
-        uint32_t b_lo, b_hi;
-        if (t.win_off != 0xffffffffu) {
-                b_lo = win[t.win_off + wfirst * PL_CELLS];
-                b_hi = win[t.win_off + (wfirst + wn) * PL_CELLS];
-        } else {
-                uint32_t lo = 0, hi = t.nblocks;
-                while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (bl[mid] < w0)
-                                lo = mid + 1;
-                        else
-                                hi = mid;
-                }
-                b_lo = lo;
-                hi = t.nblocks;
-                while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (bl[mid] < w1)
-                                lo = mid + 1;
-                        else
-                                hi = mid;
-                }
-                b_hi = lo;
-        }
-        b_lo = uni(b_lo);
-        b_hi = uni(min(b_hi, t.nblocks - 1));
+        const BlockRange r = term_block_range(bl, win, t, w0, w1);
+        const uint32_t b_lo = uni(r.lo), b_hi = uni(min(r.hi, t.nblocks - 1));
         __syncthreads();
         if (b_lo < t.nblocks)
                 for (uint32_t b = b_lo + tid; b <= b_hi; b += AND_WG) {
@@ -243,14 +193,7 @@ __global__ __launch_bounds__(AND_WG) void k_term_plane0(const uint8_t *__restric
                         ProfClock prof_;
 #endif
                         // (documents beyond the group's last window land in the sink: a short last group's w1 is the docID space's end anyway)
-                        if (CODEC == CODEC_LUCENE) {
-                                const uint4 rec = blk_rec[t.first_block + b];
-                                row_decode<CODEC, false, Plane0Post>(index, t, b, rec.x, rec.y, rec.z, rec.w, TRI_BLOCK_N(t, b, index, 0), prev, last, w0, post PROF_PASS);
-                        } else {
-                                const uint32_t off = blk_off[t.first_block + b];
-                                const uint32_t dlen = blk_doff[t.first_block + b + 1] - blk_doff[t.first_block + b] - 1u;
-                                row_decode<CODEC, false, Plane0Post>(index, t, b, off, dlen, 0, 0, TRI_BLOCK_N(t, b, index, off), prev, last, w0, post PROF_PASS);
-                        }
+                        decode_row<CODEC, false, Plane0Post>(index, blk_off, blk_rec, blk_doff, t, b, prev, last, w0, post PROF_PASS);
                 }
         __syncthreads();
         uint32_t *pa = planes0 + (size_t)row * plw + (size_t)wfirst * PL_WORDS;
@@ -258,10 +201,7 @@ __global__ __launch_bounds__(AND_WG) void k_term_plane0(const uint8_t *__restric
                 pa[i] = pl[i];
         if (prank) { // (a 64-byte record per PL_RANK_DOCS documents: the group's first posting, its eight plane-0 words — k_term_planes)
                 uint32_t *rec = prank + ((size_t)row * (plw / (PL_RANK_DOCS / 32u)) + (size_t)wfirst * (PL_W / PL_RANK_DOCS)) * PL_RANK_WORDS;
-                for (uint32_t i = tid; i < wn * (PL_W / PL_RANK_DOCS) * PL_RANK_WORDS; i += AND_WG) {
-                        const uint32_t gg = i / PL_RANK_WORDS, k = i % PL_RANK_WORDS;
-                        rec[i] = rank_rec_word(rdir[gg], pl + 8u * gg, k);
-                }
+                write_rank_records(rec, rdir, pl, wn * (PL_W / PL_RANK_DOCS) * PL_RANK_WORDS);
         }
 }
 
@@ -605,14 +545,7 @@ __device__ __noinline__ uint32_t planes_lookup_freq(const uint8_t *__restrict__ 
 #ifdef TRI_PROF
         ProfClock prof_;
 #endif
-        if (CODEC == CODEC_LUCENE) {
-                const uint4 rec = blk_rec[t.first_block + b];
-                row_decode<CODEC, true, FreqProbe>(index, t, b, rec.x, rec.y, rec.z, rec.w, TRI_BLOCK_N(t, b, index, 0), prev, last, 0u, probe PROF_PASS);
-        } else {
-                const uint32_t off = blk_off[t.first_block + b];
-                const uint32_t dlen = blk_doff[t.first_block + b + 1] - blk_doff[t.first_block + b] - 1u;
-                row_decode<CODEC, true, FreqProbe>(index, t, b, off, dlen, 0, 0, TRI_BLOCK_N(t, b, index, off), prev, last, 0u, probe PROF_PASS);
-        }
+        decode_row<CODEC, true, FreqProbe>(index, blk_off, blk_rec, blk_doff, t, b, prev, last, 0u, probe PROF_PASS);
         return probe.f & 0xffffu;
 }
 
@@ -627,14 +560,7 @@ __device__ __noinline__ void planes_list_row(const uint8_t *__restrict__ index, 
 #ifdef TRI_PROF
         ProfClock prof_;
 #endif
-        if (CODEC == CODEC_LUCENE) {
-                const uint4 rec = blk_rec[t.first_block + b];
-                row_decode<CODEC, true, ListPost>(index, t, b, rec.x, rec.y, rec.z, rec.w, TRI_BLOCK_N(t, b, index, 0), prev, last, 0u, post PROF_PASS);
-        } else {
-                const uint32_t off = blk_off[t.first_block + b];
-                const uint32_t dlen = blk_doff[t.first_block + b + 1] - blk_doff[t.first_block + b] - 1u;
-                row_decode<CODEC, true, ListPost>(index, t, b, off, dlen, 0, 0, TRI_BLOCK_N(t, b, index, off), prev, last, 0u, post PROF_PASS);
-        }
+        decode_row<CODEC, true, ListPost>(index, blk_off, blk_rec, blk_doff, t, b, prev, last, 0u, post PROF_PASS);
         for (uint32_t i = post.i; i < 32; ++i)
                 out[i] = PLK_PAD;
 }
@@ -690,15 +616,7 @@ typedef const __attribute__((address_space(1))) PlkU2 *PlkG2;
 // where `doc` stands in a sorted list of n entries (docID << 1 | flag; padding sorts last), PLK_NOT_FOUND when the list does not hold it
 constexpr uint32_t PLK_NOT_FOUND = 0xffffffffu;
 template <typename P> __device__ __forceinline__ uint32_t planes_list_find(const P ls, const uint32_t n, const uint32_t doc) {
-        uint32_t lo = 0, hi = n;
-        const uint32_t key = doc << 1;
-        while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (ls[mid] < key)
-                        lo = mid + 1;
-                else
-                        hi = mid;
-        }
+        const uint32_t lo = first_ge(ls, 0u, n, doc << 1);
         const uint32_t f = lo < n ? ls[lo] : PLK_PAD;
         return (f >> 1) == doc ? lo : PLK_NOT_FOUND;
 }
@@ -1114,13 +1032,7 @@ __global__ __launch_bounds__(PLK_WG, (PLK_WGS_PER_CU * PLK_WG + 255) / 256) void
         const unsigned long long wg_t0 = wall_clock64(); // (100 MHz)
 #endif
         for (;;) {
-                if (wave == 0) { // uniform draw (see k_and)
-                        const uint32_t old = atomicAdd(ticket, 1u);
-                        sh.bcast[0] = uni(old) >> 6;
-                }
-                __syncthreads();
-                const uint32_t ticket_no = uni(sh.bcast[0]);
-                __syncthreads();
+                const uint32_t ticket_no = draw_task(sh.bcast, ticket, wave);
                 if (ticket_no >= ntasks)
                         break;
                 const uint32_t tix = sched[ticket_no];
@@ -1194,24 +1106,9 @@ __global__ __launch_bounds__(PLK_WG, (PLK_WGS_PER_CU * PLK_WG + 255) / 256) void
                                 nrows = row0 < myt.nblocks ? min(r1, myt.nblocks - 1) - row0 + 1 : 0;
                         } else if (!dense) {
                                 const uint32_t *bl = blk_last + myt.first_block;
-                                uint32_t lo = 0, hi = myt.nblocks;
-                                while (lo < hi) {
-                                        const uint32_t mid = (lo + hi) >> 1;
-                                        if (bl[mid] < d_lo)
-                                                lo = mid + 1;
-                                        else
-                                                hi = mid;
-                                }
-                                row0 = lo;
-                                hi = myt.nblocks;
-                                while (lo < hi) {
-                                        const uint32_t mid = (lo + hi) >> 1;
-                                        if (bl[mid] < d_hi)
-                                                lo = mid + 1;
-                                        else
-                                                hi = mid;
-                                }
-                                nrows = row0 < myt.nblocks ? min(lo, myt.nblocks - 1) - row0 + 1 : 0;
+                                row0 = first_ge(bl, 0u, myt.nblocks, d_lo);
+                                const uint32_t r1 = first_ge(bl, row0, myt.nblocks, d_hi);
+                                nrows = row0 < myt.nblocks ? min(r1, myt.nblocks - 1) - row0 + 1 : 0;
                         }
                         // the lists' places in the scratch region: an exclusive scan over the slots (lanes 0 .. nslots-1 hold distinct slots)
                         uint32_t base = 0;

@@ -47,6 +47,7 @@ __global__ __launch_bounds__(PROBE_WG, TRI_PROBE_WAVES) void k_probe(const uint8
         const uint32_t lane = threadIdx.x & 63u;
         uint32_t *const cand = sh.cand[uni(threadIdx.x >> 6)];
         // a wave draws its own tickets (one atomic per task and wave; the next ticket is requested before the current task is run)
+        // (not draw_task: a task per WAVE, drawn by lane 0 a task ahead — no workgroup barrier, no LDS word)
         uint32_t tk = lane == 0 ? atomicAdd(ticket, 1u) : 0u;
         tk = uni(tk);
         while (tk < ntasks) {

@@ -149,15 +149,7 @@ __device__ __forceinline__ uint32_t psets_round(PsetShared &sh, R &&request, F &
         if (lane == 0)
                 sh.cnt[par][wave] = fill;
         __syncthreads();
-        uint32_t own = sh.cnt[par][lane & (PSET_WAVES - 1u)], pre = own;
-        asm volatile("s_nop 1\n\t"
-                     "v_add_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "s_nop 1\n\t"
-                     "v_add_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "s_nop 1\n\t"
-                     "v_add_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                     "s_nop 1"
-                     : "+v"(pre));
+        const uint32_t own = sh.cnt[par][lane & (PSET_WAVES - 1u)], pre = row8_incl_scan(own);
         const uint32_t base = (uint32_t)__builtin_amdgcn_readlane((int)(pre - own), (int)wave);
         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)pre, (int)PSET_WAVES - 1);
 #if defined(TRI_PSET_VARIANT) && (TRI_PSET_VARIANT == 1 || TRI_PSET_VARIANT == 2) // (perf probes: no copy-out)
@@ -242,7 +234,7 @@ __global__ __launch_bounds__(PSET_WG, TRI_PSET_WAVES) void k_psets(const DevPset
         //      workgroup runs the current task — the ticket's atomic and the record's two dependent loads (order[] -> units[]) are off the
         //      critical path.  Lane l of wave 0 carries word l of the 16-word record.
         uint32_t nt = 0xffffffffu; // (wave 0) the ticket after the one in sh.tick[]
-        if (wave == 0) {
+        if (wave == 0) { // (not draw_task: pipelined — wave 0 keeps the next ticket in a register a task ahead, and the numbers cross through sh.tick[] with the unit)
                 const uint32_t t0 = uni(atomicAdd(ticket, 1u)) >> 6; // uniform draw: 64 lanes add 1 each (one +64 atomic), see k_and
                 uint32_t wd = 0;
                 if (t0 < ntasks)
@@ -480,14 +472,7 @@ __global__ __launch_bounds__(PSCAT_WG) void k_psets_prep(const DevPsetUnit *__re
 #ifdef TRI_PROF
                         ProfClock prof_;
 #endif
-                        if (CODEC == CODEC_LUCENE) {
-                                const uint4 rec = blk_rec[t.first_block + b];
-                                row_decode<CODEC, false, PscatPost>(index, t, b, rec.x, rec.y, rec.z, rec.w, TRI_BLOCK_N(t, b, index, 0), prev, last, 0u, post PROF_PASS);
-                        } else {
-                                const uint32_t off = blk_off[t.first_block + b];
-                                const uint32_t dlen = blk_doff[t.first_block + b + 1] - blk_doff[t.first_block + b] - 1u;
-                                row_decode<CODEC, false, PscatPost>(index, t, b, off, dlen, 0, 0, TRI_BLOCK_N(t, b, index, off), prev, last, 0u, post PROF_PASS);
-                        }
+                        decode_row<CODEC, false, PscatPost>(index, blk_off, blk_rec, blk_doff, t, b, prev, last, 0u, post PROF_PASS);
                 }
                 __syncthreads();
                 if (pass)

@@ -46,6 +46,8 @@ struct RichShared {
         uint32_t bcast[4];
         uint32_t hits; // COUNT: hits of the task so far
 };
+static_assert(sizeof(RichShared) == 33848, "k_rich's LDS: cand / mptr / blkof lie as k_score's do (the two kernels walk a term's blocks the same way)");
+// (rich_tasks keeps its own searches and draw, as k_score does: through dev_search.hpp's gallop_ge its COUNT pass measured 0.5 % slower — DESIGN.md §26)
 
 // the kernels' body (k_rich: WIDE = false, wd unused; k_rich_wide: WIDE = true) — every thread of the workgroup calls it
 template <int CODEC, bool WRITE, bool WIDE>

@@ -68,14 +68,7 @@ __device__ __forceinline__ uint32_t rank_pairs_wave(const uint16_t *__restrict__
                 const uint32_t p = a[i];
                 if (!p)
                         continue;
-                uint32_t lo = 0, hi = lb;
-                while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (b[mid] < p + 1u)
-                                lo = mid + 1;
-                        else
-                                hi = mid;
-                }
+                const uint32_t lo = first_ge(b, 0u, lb, p + 1u);
                 c += (lo < lb && b[lo] == p + 1u) ? 1u : 0u;
         }
         for (int d = 32; d; d >>= 1)

@@ -146,7 +146,8 @@ struct ScoreShared {
         uint32_t bcast[4];
         TopK tk;
 };
-
+static_assert(sizeof(ScoreShared) == 72784, "k_score's LDS: what its workgroups per CU are sized by (SCORE_WGS_PER_CU)");
+// (k_score and score_lookup_freq keep their own searches and draw: through dev_search.hpp's gallop_ge the match-then-score path measured 0.9 % slower — DESIGN.md §26)
 
 // ---- the order k_score runs its tasks in: heaviest first, by their MATCH counts — which only the device knows, once the matching kernels are through.  In the schedule's
 //      order (k_and's: by the plane row a task probes) cfg3's 6 209 tasks — half of them without a match, a fifth of them 77 % of the work — kept 68 % of the

@@ -315,15 +315,7 @@ __global__ __launch_bounds__(TREE_WG) void k_tree_leaves(const uint8_t *__restri
                                 s += (double)sim_score(sim, sweights[q.score_base + nd.score], f);
                         } else { // the phrase's score for this document: its hidden query's list holds it (k_phrase: scorer->score(id, matchCnt, weight))
                                 const DevQuery hq = plan[nd.arg];
-                                uint32_t lo = 0, hi = counts[hq.first_task];
-                                while (lo < hi) {
-                                        const uint32_t mid = (lo + hi) >> 1;
-                                        if (out[hq.out_off + mid] < doc)
-                                                lo = mid + 1;
-                                        else
-                                                hi = mid;
-                                }
-                                s += pscore[hq.out_off + lo];
+                                s += pscore[hq.out_off + first_ge(out + hq.out_off, 0u, counts[hq.first_task], doc)];
                         }
                 }
                 if (all_scores)
