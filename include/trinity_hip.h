@@ -37,7 +37,9 @@ extern "C" {
                                 within 9: tri_batch_set_ranker / tri_batch_ranked (the default mode ranks its matches on the device: a proximity score, top-K per query; no struct grew),
                                 tri_cbatch_ranked / tri_cbatch_matched_terms[_wide] / tri_cbatch_matched_payloads (the default mode over a collection);
                                 within 9: tri_isect_run / _status / _results / _histogram / _get_info / _destroy, options isect_max_bytes / isect_max_masks / isect_max_runs
-                                (Trinity::intersect: token-set co-occurrence counts; no existing struct grew) */
+                                (Trinity::intersect: token-set co-occurrence counts; no existing struct grew);
+                                within 9: tri_perc_create / _query_status / _set_enabled / _get_info / _destroy / _match, tri_perc_result_pairs / _doc_counts / _get_info / _destroy,
+                                options perc_max_bytes / perc_prune (the percolator: documents matched against a resident set of stored queries; no existing struct grew) */
 
 /* status codes */
 #define TRI_OK 0
@@ -379,6 +381,70 @@ int tri_isect_results(const tri_isect *, size_t r, uint64_t *masks, uint32_t *co
 int tri_isect_histogram(const tri_isect *, size_t r, uint64_t *masks, uint32_t *counts, uint32_t *first_docs, size_t cap, size_t *n);
 int tri_isect_get_info(const tri_isect *, tri_isect_info *);
 void tri_isect_destroy(tri_isect *);
+
+/* ---- the percolator: documents matched against stored queries (percolator.h:1-60, percolator.cpp:5-137: percolator_query::match walks one exec_node tree per
+ * (query, document) on one thread; its header names Twitter's predicate index as what it lacks, percolator.h:1-3).  Here a SET of stored queries is resident on the
+ * device and a batch of documents that was never indexed is tested against all of them: no tri_index, no postings decoded; the answer is (query, document) pairs.
+ * A stored query is a postfix program in the vocabulary above; TERM operands index the percolator's OWN dictionary, 0 .. nterms-1 (the application interns its
+ * strings, as percolator_query::CCTX::resolve_query_term does, percolator.h:30-45).  For ONE document (percolator.cpp:9-137): TERM: the document holds the term
+ * (match_term); AND / OR: all / any child (matchallterms, matchanyterms, logicaland, logicalor, matchallnodes, matchanynodes); NOT(2): lhs and not rhs (logicalnot,
+ * :86-90); OPT(2): the main side (logicaland(x, consttrueexpr), :80-84, :129); SOME: at least `min` of the children (:98-107); PHRASE(n): match_phrase, which the
+ * reference leaves to the document proxy and the device FIXES as the Phrase iterator's rule — some position p != 0 of the first word has p + j among the positions
+ * of word j for every j (position 0 never starts a phrase; a phrase may repeat a word; at most 16 words).  Percolator programs only: NOT(1), unarynot (:45-46), is
+ * true where its operand is false (tri_batch_create keeps refusing it).  The empty program is constfalse (:76-78): it never matches.
+ * tri_perc_create (percolator_query::percolator_query, percolator.h:47-58): lowers and uploads the set once.  A malformed program (what tri_batch_create refuses, a
+ * TERM >= nterms) fails the call with TRI_ERR_INVALID; a tree of more than 1024 nodes (a node per token, less a phrase's words) or one whose fold needs more than 64
+ * stack words is left out ALONE — tri_perc_query_status: TRI_ERR_UNSUPPORTED for it, as tri_batch_query_status; it matches nothing and the rest of the set runs.
+ * tri_perc_set_enabled: unregisters / registers queries again without a rebuild (every query starts enabled); an index >= nq is TRI_ERR_INVALID, nothing changed.
+ * tri_perc_get_info: the set's size.  tri_perc_destroy: after every result of the set, before its tri_dev.
+ * tri_perc_match (percolator_query::match, percolator.cpp:5-7, for every stored query and every document of the batch): synchronous, like tri_isect_run.  Documents
+ * are numbered 0 .. ndocs-1 in the order given.  TRI_ERR_INVALID, nothing written, the message names the document and the term: a null argument, ndocs of 0 or above
+ * 65536, doc_first that does not ascend, a document's terms not strictly ascending (0xffffffff, a term unknown to the dictionary, is ignored and stands last), a term
+ * id >= nterms, frequencies that run past npositions, positions that descend within a posting, a non-zero `reserved`.  TRI_ERR_UNSUPPORTED for the whole call: its
+ * pooled scratch would exceed option perc_max_bytes, or it answers 2^32 pairs or more (split the call).  TRI_ERR_NOMEM as elsewhere.
+ * tri_perc_result_pairs: every matching pair, in the order asked for — TRI_PERC_BY_QUERY: query ascending, then document; TRI_PERC_BY_DOCUMENT: document ascending,
+ * then query ("which rules fired for this document").  Both orders are made on the device and are deterministic.  queries == NULL: *n only; cap < the pairs, or an
+ * order outside the two: TRI_ERR_INVALID, nothing written.  tri_perc_result_doc_counts: the queries that matched each document.
+ * Options (tri_dev_set_option, read by tri_perc_match).  "perc_max_bytes": the pooled scratch of a call (default 4 GB).  "perc_prune": default 1 — a stored query is
+ * evaluated only if the batch holds one of its leaves (a term it names, a phrase all of whose words occur in the batch), or if it matches a document holding none of
+ * its terms (a pure negation, NOT(1)); 0: every enabled query is evaluated (for measurement: the pairs are the same).
+ * Threading and teardown follow the rules at the top: one thread at a time per tri_dev; results before their set, sets before their tri_dev. */
+typedef struct tri_perc tri_perc;               /* a resident set of stored queries, on one tri_dev */
+typedef struct tri_perc_result tri_perc_result; /* the answer of one tri_perc_match */
+typedef struct tri_perc_docs {                  /* a batch of documents */
+        uint32_t ndocs;                         /* 1 .. 65536 a call (a leaf row is at most 8 KB; split longer streams) */
+        const uint64_t *doc_first;              /* [ndocs + 1] into terms / freqs */
+        const uint32_t *terms;                  /* per document strictly ascending */
+        const uint32_t *freqs;                  /* positions of that (document, term); may be 0: held, but in no phrase */
+        const uint16_t *positions;              /* concatenated, non-descending within a (document, term) */
+        uint64_t npositions;
+        uint32_t reserved;                      /* 0 */
+} tri_perc_docs;
+typedef struct tri_perc_info {
+        uint64_t queries, unsupported; /* stored; of them left out (tri_perc_query_status) */
+        uint64_t terms, phrases;       /* distinct terms the queries name, distinct multi-word phrases: the set's leaf table */
+        uint64_t device_bytes;         /* resident */
+        uint32_t nterms, reserved;     /* the dictionary's size as given */
+} tri_perc_info;
+typedef struct tri_perc_result_info {
+        uint32_t ndocs, leaf_rows, phrase_rows; /* rows built: term leaves present in the batch, phrases all of whose words are */
+        uint32_t evaluated, hit_queries;        /* queries evaluated after the prune; of them those with a match */
+        uint32_t reserved;
+        uint64_t pairs, scratch_bytes;
+        float rows_ms, phrases_ms, select_ms, eval_ms, compact_ms, total_ms; /* device time per stage (HIP events); the call end to end on the host */
+} tri_perc_result_info;
+#define TRI_PERC_BY_QUERY 0
+#define TRI_PERC_BY_DOCUMENT 1
+int tri_perc_create(tri_dev *, const uint32_t *prog, size_t prog_len, const tri_query *queries, size_t nq, uint32_t nterms, tri_perc **out);
+int tri_perc_query_status(const tri_perc *, int32_t *status /* [nq] */);
+int tri_perc_set_enabled(tri_perc *, const uint32_t *queries, size_t n, int enabled);
+int tri_perc_get_info(const tri_perc *, tri_perc_info *);
+void tri_perc_destroy(tri_perc *);
+int tri_perc_match(tri_perc *, const tri_perc_docs *, tri_perc_result **out);
+int tri_perc_result_pairs(const tri_perc_result *, int order, uint32_t *queries, uint32_t *docs, size_t cap, size_t *n);
+int tri_perc_result_doc_counts(const tri_perc_result *, uint32_t *counts /* [ndocs] */);
+int tri_perc_result_get_info(const tri_perc_result *, tri_perc_result_info *);
+void tri_perc_result_destroy(tri_perc_result *);
 
 /* ---- batched query execution (span seam) -----------------------------------------------------------
  * Replaces, for a whole batch of queries at once: queryexec_ctx::build_iterator + build_span

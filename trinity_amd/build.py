@@ -34,7 +34,7 @@ def hipcc():
 
 
 def build_hip(force=False):
-    if force or _newer(LIB_HIP, _deps(HIP_SRCS) + [os.path.join(PKG, "csrc", "host", n) for n in ("result_rows.hpp", "isect_rows.hpp")]):  # (read_side.hpp's host transforms, isect_side.hpp's replay)
+    if force or _newer(LIB_HIP, _deps(HIP_SRCS) + [os.path.join(PKG, "csrc", "host", n) for n in ("result_rows.hpp", "isect_rows.hpp", "perc_lower.hpp")]):  # (read_side.hpp's host transforms, isect_side.hpp's replay, perc_side.hpp's lowering)
         cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-o", LIB_HIP] + HIP_SRCS + ["-ldl"]
         subprocess.run(cmd, check=True)
     return LIB_HIP
@@ -166,9 +166,25 @@ def build_mirror_isect_test(force=False):
     return MIRROR_ISECT_BIN
 
 
+MIRROR_PERC_SRC = os.path.join(ROOT, "tests", "cpp", "host_mirror_perc_test.cpp")
+MIRROR_PERC_BIN = os.path.join(ROOT, "tests", "cpp", "host_mirror_perc_test")
+
+
+def build_mirror_perc_test(force=False):
+    """The percolator of the operator surface (csrc/host/trinity_gpu.hpp: percolator_query, its document proxy, PercolatorSet over tri_perc_create / tri_perc_match)
+    compiled into its driver; in-tree, so that it travels to the GPU box, where tests/test_host_mirror_perc.py runs it."""
+    deps = [MIRROR_PERC_SRC, os.path.join(ROOT, "tests", "cpp", "perc_case_file.hpp"), os.path.join(PKG, "csrc", "host", "trinity_gpu.hpp"), os.path.join(PKG, "csrc", "host", "google_encoder.hpp"),
+            os.path.join(ROOT, "include", "trinity_hip.h")]  # fmt: skip
+    if force or _newer(MIRROR_PERC_BIN, deps):
+        build_hip()
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", MIRROR_PERC_BIN, MIRROR_PERC_SRC, "-L" + PKG, "-ltrinity_hip", "-Wl,-rpath,$ORIGIN/../../trinity_amd"]
+        subprocess.run(cmd, check=True)
+    return MIRROR_PERC_BIN
+
+
 def build_all(force=False):
     return (build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force), build_mirror_wide_terms_test(force),
-            build_mirror_hits_test(force), build_mirror_rank_test(force), build_mirror_collection_test(force), build_mirror_isect_test(force))
+            build_mirror_hits_test(force), build_mirror_rank_test(force), build_mirror_collection_test(force), build_mirror_isect_test(force), build_mirror_perc_test(force))
 
 
 def kernels_stamp():

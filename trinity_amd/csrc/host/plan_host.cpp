@@ -5,6 +5,7 @@
 #include "../planner.hpp"
 #include "../lucene_enc_units.hpp"
 #include "lucene_encoder.hpp"
+#include "perc_lower.hpp"
 
 #include <cstdlib>
 #include <memory>
@@ -266,5 +267,30 @@ void tri_host_index_facts(void *h, uint64_t *info6, uint32_t *per_term3) {
                 per_term3[3 * t + 1] = H.terms[t].nblocks;
                 per_term3[3 * t + 2] = H.terms[t].nblocks ? H.blk_last[H.terms[t].first_block + H.terms[t].nblocks - 1] : 0;
         }
+}
+
+// the percolator's host half (perc_lower.hpp) without a device: what tri_perc_create does to a set of programs — status[nq], info6 = { unsupported, distinct terms,
+// distinct phrases, record words, deepest stack, queries that hold on a document without any of their leaves } — and what tri_perc_match refuses of a batch.
+// Both return the TRI_* code and leave the message in err
+int tri_host_perc_lower(const uint32_t *prog, uint64_t prog_len, const uint32_t *queries2, uint64_t nq, uint32_t nterms, int32_t *status, uint64_t *info6, char *err, uint64_t errcap) {
+        perc::Lowered L;
+        std::string e;
+        const int rc = perc::lower(prog, prog_len, reinterpret_cast<const tri_query *>(queries2), nq, nterms, L, e);
+        put_err(err, errcap, e);
+        if (rc != TRI_OK)
+                return rc;
+        for (uint64_t q = 0; q < nq; ++q)
+                status[q] = L.status[q];
+        uint64_t absent = 0;
+        for (const uint32_t f : L.qflags)
+                absent += (f & perc::Q_ABSENT) != 0;
+        info6[0] = L.unsupported, info6[1] = L.leaf_term.size(), info6[2] = L.phrase_first.size() - 1, info6[3] = L.recs.size(), info6[4] = L.stack_max, info6[5] = absent;
+        return TRI_OK;
+}
+int tri_host_perc_check_docs(const tri_perc_docs *docs, uint32_t nterms, char *err, uint64_t errcap) {
+        std::string e;
+        const int rc = perc::check_docs(docs, nterms, e);
+        put_err(err, errcap, e);
+        return rc;
 }
 }

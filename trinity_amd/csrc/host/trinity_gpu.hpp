@@ -1351,4 +1351,192 @@ namespace trinity_amd {
                                 dws->set(dec->execCtxTermID, out[h].pos);
                 }
         }
+
+        // ---- the percolator (percolator.h:1-60, percolator.cpp:5-137): documents matched against stored queries.  The text-to-tree step (compile_query)
+        //      stays out, as it does for queries: a percolator_query is built from a postfix program whose TERM operands index the query's own distinct terms.
+        struct percolator_document_proxy { // percolator.h:10-20
+                virtual bool match_term(const uint16_t term) = 0;
+                virtual bool match_phrase(const uint16_t *phraseTerms, const uint16_t phraseTermsCnt) = 0;
+                virtual ~percolator_document_proxy() = default;
+        };
+
+        class percolator_query final { // percolator.h:22-60
+              public:
+                percolator_query() = default; // constfalse (percolator.cpp:76-78): never matches
+                // program: postfix tokens (TRI_TOK), TERM operands = indices into `terms` (the query's distinct terms, as CCTX::resolve_query_term numbers them)
+                percolator_query(std::vector<uint32_t> program, std::vector<std::string> terms) : prog(std::move(program)), distinct(std::move(terms)) {}
+                const std::string &term_by_index(const uint16_t idx) const { return distinct.at(idx); } // percolator.h:52
+                const std::vector<std::string> &distinct_terms() const { return distinct; }
+                const std::vector<uint32_t> &program() const { return prog; }
+                operator bool() const noexcept { return !prog.empty(); } // percolator.h:56-58
+                // percolator.cpp:5-137, the recursion over exec_nodes as a walk over the postfix program: one document, one thread
+                bool match(percolator_document_proxy &src) const {
+                        struct V {
+                                bool v;
+                                uint16_t term;
+                        };
+                        std::vector<V> st;
+                        for (const uint32_t t : prog) {
+                                const uint32_t op = t >> 28, arg = t & 0x0fffffffu;
+                                if (op == TRI_OP_TERM) {
+                                        st.push_back({src.match_term(uint16_t(arg)), uint16_t(arg)}); // match_term, :11-12
+                                        continue;
+                                }
+                                const uint32_t n = op == TRI_OP_SOME ? (arg & 0xffffu) : arg;
+                                if (n < 1 || n > st.size())
+                                        throw invalid_argument("percolator_query: malformed program");
+                                const V *k = st.data() + st.size() - n;
+                                bool v = false;
+                                uint32_t cnt = 0;
+                                for (uint32_t i = 0; i < n; ++i)
+                                        cnt += k[i].v;
+                                switch (op) {
+                                        case TRI_OP_AND: // matchallterms / logicaland / matchallnodes
+                                                v = cnt == n;
+                                                break;
+                                        case TRI_OP_OR: // matchanyterms / logicalor / matchanynodes
+                                                v = cnt != 0;
+                                                break;
+                                        case TRI_OP_NOT: // unarynot :45-46, logicalnot :86-90
+                                                v = n == 1 ? !k[0].v : (k[0].v && !k[1].v);
+                                                break;
+                                        case TRI_OP_OPT: // logicaland(x, consttrueexpr), :80-84, :129
+                                                v = k[0].v;
+                                                break;
+                                        case TRI_OP_SOME: // matchsome :98-107
+                                                v = cnt >= (arg >> 16);
+                                                break;
+                                        case TRI_OP_PHRASE: { // match_phrase, :13-17
+                                                std::vector<uint16_t> words(n);
+                                                for (uint32_t i = 0; i < n; ++i)
+                                                        words[i] = k[i].term;
+                                                v = n == 1 ? k[0].v : src.match_phrase(words.data(), uint16_t(n));
+                                        } break;
+                                        default:
+                                                throw invalid_argument("percolator_query: malformed program");
+                                }
+                                st.resize(st.size() - n);
+                                st.push_back({v, 0});
+                        }
+                        return st.size() == 1 && st[0].v;
+                }
+
+              private:
+                std::vector<uint32_t> prog;
+                std::vector<std::string> distinct;
+        };
+
+        // A document for the percolator: term -> ascending positions.  Its proxy applies the device's phrase rule (the Phrase iterator's: some position p != 0 of
+        // the first word has p + j among the positions of word j), so that the host recursion and the device answer the same question.
+        using percolator_document = std::vector<std::pair<std::string, std::vector<tokenpos_t>>>;
+        class percolator_positions_proxy final : public percolator_document_proxy {
+              public:
+                percolator_positions_proxy(const percolator_query &q, const percolator_document &d) : q(q) {
+                        for (const auto &kv : d)
+                                by_term[kv.first] = &kv.second;
+                }
+                bool match_term(const uint16_t term) override { return by_term.count(q.term_by_index(term)) != 0; }
+                bool match_phrase(const uint16_t *terms, const uint16_t n) override {
+                        std::vector<const std::vector<tokenpos_t> *> p(n);
+                        for (uint16_t j = 0; j < n; ++j) {
+                                const auto it = by_term.find(q.term_by_index(terms[j]));
+                                if (it == by_term.end())
+                                        return false;
+                                p[j] = it->second;
+                        }
+                        for (const tokenpos_t at : *p[0]) {
+                                bool ok = at != 0;
+                                for (uint32_t j = 1; j < n && ok; ++j)
+                                        ok = uint32_t(at) + j <= 0xffffu && std::binary_search(p[j]->begin(), p[j]->end(), tokenpos_t(at + j));
+                                if (ok)
+                                        return true;
+                        }
+                        return false;
+                }
+
+              private:
+                const percolator_query &q;
+                std::unordered_map<std::string, const std::vector<tokenpos_t> *> by_term;
+        };
+
+        // A resident set of stored queries on the device (tri_perc_create / tri_perc_match): add() queries, commit() once, match() batches of documents.
+        class PercolatorSet final {
+              public:
+                struct match_pair {
+                        uint32_t query, document;
+                };
+                explicit PercolatorSet(tri_dev *device) : dev(device) {}
+                ~PercolatorSet() { tri_perc_destroy(h); }
+                PercolatorSet(const PercolatorSet &) = delete;
+                PercolatorSet &operator=(const PercolatorSet &) = delete;
+                // returns the query's index in the set: what match() reports
+                uint32_t add(const percolator_query &q) {
+                        if (h)
+                                throw invalid_argument("PercolatorSet::add after commit");
+                        first.push_back({uint32_t(prog.size()), uint32_t(q.program().size())});
+                        for (const uint32_t t : q.program())
+                                prog.push_back((t >> 28) == TRI_OP_TERM ? TRI_TOK(TRI_OP_TERM, intern(q.term_by_index(uint16_t(t & 0x0fffffffu)))) : t);
+                        return uint32_t(first.size() - 1);
+                }
+                void commit() {
+                        if (h)
+                                throw invalid_argument("PercolatorSet::commit twice");
+                        check(tri_perc_create(dev, prog.data(), prog.size(), first.data(), first.size(), uint32_t(dict.size()), &h));
+                }
+                void set_enabled(const std::vector<uint32_t> &queries, const bool on) { check(tri_perc_set_enabled(h, queries.data(), queries.size(), on)); }
+                std::vector<int32_t> status() const {
+                        std::vector<int32_t> st(first.size());
+                        check(tri_perc_query_status(h, st.data()));
+                        return st;
+                }
+                // every (query, document) pair that matches; order: TRI_PERC_BY_QUERY / TRI_PERC_BY_DOCUMENT
+                std::vector<match_pair> match(const std::vector<percolator_document> &documents, const int order = TRI_PERC_BY_QUERY) const {
+                        if (!h)
+                                throw invalid_argument("PercolatorSet::match before commit");
+                        std::vector<uint64_t> doc_first{0};
+                        std::vector<uint32_t> terms, freqs;
+                        std::vector<tokenpos_t> positions;
+                        std::vector<std::pair<uint32_t, const std::vector<tokenpos_t> *>> row;
+                        for (const percolator_document &d : documents) {
+                                row.clear();
+                                for (const auto &kv : d) {
+                                        const auto it = dict.find(kv.first);
+                                        if (it != dict.end()) // (a term no stored query names: nothing can ask for it)
+                                                row.emplace_back(it->second, &kv.second);
+                                }
+                                std::sort(row.begin(), row.end());
+                                for (const auto &r : row) {
+                                        terms.push_back(r.first);
+                                        freqs.push_back(uint32_t(r.second->size()));
+                                        positions.insert(positions.end(), r.second->begin(), r.second->end());
+                                }
+                                doc_first.push_back(terms.size());
+                        }
+                        tri_perc_docs D{};
+                        D.ndocs = uint32_t(documents.size());
+                        D.doc_first = doc_first.data(), D.terms = terms.data(), D.freqs = freqs.data(), D.positions = positions.data(), D.npositions = positions.size();
+                        tri_perc_result *r = nullptr;
+                        check(tri_perc_match(h, &D, &r));
+                        struct Free {
+                                tri_perc_result *r;
+                                ~Free() { tri_perc_result_destroy(r); }
+                        } guard{r};
+                        size_t n = 0;
+                        check(tri_perc_result_pairs(r, order, nullptr, nullptr, 0, &n));
+                        std::vector<uint32_t> q(n + 1), d(n + 1);
+                        check(tri_perc_result_pairs(r, order, q.data(), d.data(), n, &n));
+                        std::vector<match_pair> out(n);
+                        for (size_t i = 0; i < n; ++i)
+                                out[i] = {q[i], d[i]};
+                        return out;
+                }
+
+              private:
+                uint32_t intern(const std::string &s) { return dict.emplace(s, uint32_t(dict.size())).first->second; }
+                tri_dev *dev;
+                tri_perc *h{nullptr};
+                std::vector<uint32_t> prog;
+                std::vector<tri_query> first;
+                std::unordered_map<std::string, uint32_t> dict;
+        };
 } // namespace trinity_amd

@@ -19,6 +19,7 @@
 //                        same tree.  Static LDS: the record 32 KB + bits[32][256] 32 KB + cnt[64][256] 64 KB = 128 KB
 // (a workgroup may declare 160 KB on gfx950).  k_tree_expand, k_tree_gather, k_tree_topk, k_term_planes and k_rich read no node record: as they are.
 #pragma once
+#include "tree_fold.hpp" // the fold itself (tree_wide_fold, tree_wide_slot): k_perc.hpp runs it too
 
 struct TreeWideNodes {
         uint4 node4[2 * TREE_WIDE_MAX_NODES]; // DevTreeNodeW as two 16-byte halves: a { op | cbits << 8 | parent << 16, arg, row, score }, b { rmask, ord | nkids << 16, thr | pop << 16 | pcbits << 24, pad (a leaf: the report mask's high word) }
@@ -39,10 +40,6 @@ __device__ __forceinline__ uint32_t tree_wide_load(TreeWideNodes &sh, const uint
 __device__ __forceinline__ const uint32_t *tree_wide_row(const uint32_t row, const uint32_t *__restrict__ trows, const uint32_t *__restrict__ prows, const uint32_t plw) {
         return (row & TREE_ROW_PHRASE) ? prows + (size_t)(row & ~TREE_ROW_PHRASE) * plw : trows + (size_t)row * PL_PLANES * plw;
 }
-// a stack slot (uniform).  The planner bounds a record's stack (lower_tree): the mask only keeps a damaged record's stores inside the array
-__device__ __forceinline__ uint32_t tree_wide_slot(const uint32_t sp) { return sp & (TREE_WIDE_STACK - 1u); }
-static_assert((TREE_WIDE_STACK & (TREE_WIDE_STACK - 1u)) == 0, "tree_wide_slot masks");
-
 // ---- the tree per bitmap word.  grid: (chunks of the docID space, wide tree queries); sched[y]: the query's task
 struct TreeEvalWideShared {
         TreeWideNodes t;
@@ -64,55 +61,9 @@ __global__ __launch_bounds__(TREE_WG) void k_tree_eval_wide(const DevQuery *__re
                 const uint32_t w = chunk * TREE_CHUNK_WORDS + pass * TREE_WG + tid;
                 if (w >= plw)
                         continue;
-                uint32_t sp = 0, m = 0;
-                for (uint32_t n = 0; n < nn; ++n) { // (uniform: the record, and with it sp, is the same for every thread)
-                        const uint4 a = sh.t.node4[2 * n], b = sh.t.node4[2 * n + 1];
-                        const uint32_t op = uni(a.x & 0xffu);
-                        uint32_t v;
-                        if (op == TRI_OP_TERM || op == TRI_OP_PHRASE)
-                                v = tree_wide_row(uni(a.z), trows, prows, plw)[w];
-                        else if (op == TRI_OP_SOME) { // DisjunctionSome: count >= thr, from the top plane down — greater so far, or equal so far and this bit decides
-                                const uint32_t cb = uni((a.x >> 8) & 0xffu), thr = uni(b.z & 0xffffu);
-                                uint32_t gt = 0, eq = 0xffffffffu;
-                                for (uint32_t p = cb; p-- > 0;) {
-                                        const uint32_t c = sh.stk[tree_wide_slot(sp - cb + p)][tid];
-                                        const uint32_t tb = ((thr >> p) & 1u) ? 0xffffffffu : 0u;
-                                        gt |= eq & c & ~tb;
-                                        eq &= ~(c ^ tb);
-                                }
-                                v = (thr >> cb) ? 0u : (gt | eq); // (a threshold the planes cannot reach: never — the parser drops such a matchsome)
-                                sp -= cb;
-                        } else // AND / OR / NOT / OPT: the accumulator is the node's word
-                                v = sh.stk[tree_wide_slot(--sp)][tid];
-                        if ((a.x >> 16) == TREE_NO_PARENT) { // (uniform) the root: the last node
-                                m = v;
-                                continue;
-                        }
-                        const uint32_t ord = uni(b.y & 0xffffu), pop = uni((b.z >> 16) & 0xffu), pcb = uni(b.z >> 24);
-                        if (ord == 0) { // the parent's accumulator begins as this word
-                                sh.stk[tree_wide_slot(sp)][tid] = v;
-                                if (pop == TRI_OP_SOME) {
-                                        for (uint32_t p = 1; p < pcb; ++p)
-                                                sh.stk[tree_wide_slot(sp + p)][tid] = 0u;
-                                        sp += pcb;
-                                } else
-                                        ++sp;
-                        } else if (pop == TRI_OP_AND)
-                                sh.stk[tree_wide_slot(sp - 1)][tid] &= v;
-                        else if (pop == TRI_OP_OR)
-                                sh.stk[tree_wide_slot(sp - 1)][tid] |= v;
-                        else if (pop == TRI_OP_NOT) // Filter (docset_iterators.cpp:652-677): required AND NOT excluded
-                                sh.stk[tree_wide_slot(sp - 1)][tid] &= ~v;
-                        else if (pop == TRI_OP_SOME) { // one more child into the bit-sliced count
-                                uint32_t carry = v;
-                                for (uint32_t p = 0; p < pcb; ++p) {
-                                        uint32_t &c = sh.stk[tree_wide_slot(sp - pcb + p)][tid];
-                                        const uint32_t t = c & carry;
-                                        c ^= carry;
-                                        carry = t;
-                                }
-                        } // (TRI_OP_OPT, its optional side: Optional's documents are its main side's, docset_iterators.h:174-206)
-                }
+                uint32_t m = tree_wide_fold<false>(
+                        nn, [&](const uint32_t n, uint4 &a, uint4 &b) { a = sh.t.node4[2 * n], b = sh.t.node4[2 * n + 1]; },
+                        [&](const uint4 &a) { return tree_wide_row(uni(a.z), trows, prows, plw)[w]; }, [&](const uint32_t slot) -> uint32_t & { return sh.stk[slot][tid]; });
                 if (masked) // masked_documents_registry::test (docidupdates.h:90-119): documents updated / deleted elsewhere never match
                         m &= ~masked[w];
                 qbits[(size_t)qi * plw + w] = m;

@@ -71,6 +71,9 @@ struct tri_options {
         uint64_t isect_max_masks = 262144;     // ... most slots of a request's table H (distinct considered masks; 16 + 4 bytes each): sized by the call's widest request (2 x 2^groups) up to this
         uint64_t isect_max_runs = 524288;      // ... of its table C ((mask, epoch) run credits; 12 bytes each): sized after pass 1 from H's exact bound, up to this.  A request that
                                                // overflows either table answers TRI_ERR_UNSUPPORTED
+        uint64_t perc_max_bytes = 4ull << 30;  // tri_perc_match (perc_side.hpp): the pooled scratch of a call — the batch, a row per leaf it holds, a row of match words per candidate query, the pairs
+                                               // in both orders; beyond it the call is TRI_ERR_UNSUPPORTED (split it)
+        uint64_t perc_prune = 1;               // ... 0: every enabled stored query is evaluated, whether the batch holds one of its leaves or not (for measurement: the pairs are the same)
         uint64_t probe_max_blocks = 0;         // > 0: a lead list of at most this many blocks against lists that all have planes runs in k_probe (a wave per task) instead of
                                                // k_and's candidate tiles.  Off by default — measured at cfg2 (step ms / k_probe / k_and): 0: 2.14 / - / 0.78; 64: 2.25 / 0.15 / 0.75;
                                                // 256: 2.26 / 0.22 / 0.70; 1024: 2.35 / 0.41 / 0.59; all: 2.55 / 0.82 / 0.41 — k_and's time is its tail, not its task count

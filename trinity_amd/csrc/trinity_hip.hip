@@ -479,6 +479,7 @@ struct tri_batch : BatchPlan {
 #include "k_isect.hpp"
 #include "k_tree.hpp"
 #include "k_tree_wide.hpp"
+#include "k_perc.hpp"
 #include "k_commit.hpp"
 #include "k_lencode.hpp"
 #include "filtered_kernels.hpp"
@@ -555,7 +556,8 @@ namespace {
                              {"cand_xcd", &tri_options::cand_xcd},
                              {"plan_threads", &tri_options::plan_threads},
                              {"probe_max_blocks", &tri_options::probe_max_blocks}, {"phrase_task_div", &tri_options::phrase_task_div}, {"plan_hot_us", &tri_options::plan_hot_us}, {"plan_pin", &tri_options::plan_pin}, {"planes_order", &tri_options::planes_order}, {"pset_order", &tri_options::pset_order}, {"scatter_bitmap_slack", &tri_options::scatter_bitmap_slack}, {"tree_max_bytes", &tri_options::tree_max_bytes}, {"tree_max_nodes", &tri_options::tree_max_nodes}, {"tree_wide_min_nodes", &tri_options::tree_wide_min_nodes}, {"rich_max_terms", &tri_options::rich_max_terms}, {"result_bitmaps", &tri_options::result_bitmaps}, {"cand_task_cost", &tri_options::cand_task_cost}, {"dense_window_cost", &tri_options::dense_window_cost},
-                             {"isect_max_bytes", &tri_options::isect_max_bytes}, {"isect_max_masks", &tri_options::isect_max_masks}, {"isect_max_runs", &tri_options::isect_max_runs}};
+                             {"isect_max_bytes", &tri_options::isect_max_bytes}, {"isect_max_masks", &tri_options::isect_max_masks}, {"isect_max_runs", &tri_options::isect_max_runs},
+                             {"perc_max_bytes", &tri_options::perc_max_bytes}, {"perc_prune", &tri_options::perc_prune}};
                 for (const auto &e : table)
                         if (!strcmp(e.name, name))
                                 return &(o.*(e.field));
@@ -2801,6 +2803,7 @@ extern "C" int tri_gather_results(tri_batch *b, tri_comm *c, void *counts_all, v
 // the encoders, commit and merge on the device: tri_encode_*, tri_commit_*, tri_merge_* and the scratch they allocate from
 #include "write_side.hpp"
 #include "isect_side.hpp"
+#include "perc_side.hpp"
 
 #ifdef TRI_PROF
 // perf-probe builds: read back and reset the per-phase cycle totals (dev_stream.hpp)

@@ -52,6 +52,26 @@ class TriIsectInfo(C.Structure):
                 ("c_size", C.POINTER(C.c_uint32)), ("lds_spills", C.POINTER(C.c_uint32))]  # fmt: skip
 
 
+class TriPercDocs(C.Structure):
+    _fields_ = [("ndocs", C.c_uint32), ("doc_first", C.c_void_p), ("terms", C.c_void_p), ("freqs", C.c_void_p), ("positions", C.c_void_p), ("npositions", C.c_uint64),
+                ("reserved", C.c_uint32)]  # fmt: skip
+
+
+class TriPercInfo(C.Structure):
+    _fields_ = [("queries", C.c_uint64), ("unsupported", C.c_uint64), ("terms", C.c_uint64), ("phrases", C.c_uint64), ("device_bytes", C.c_uint64), ("nterms", C.c_uint32),
+                ("reserved", C.c_uint32)]  # fmt: skip
+
+
+class TriPercResultInfo(C.Structure):
+    _fields_ = [("ndocs", C.c_uint32), ("leaf_rows", C.c_uint32), ("phrase_rows", C.c_uint32), ("evaluated", C.c_uint32), ("hit_queries", C.c_uint32), ("reserved", C.c_uint32),
+                ("pairs", C.c_uint64), ("scratch_bytes", C.c_uint64), ("rows_ms", C.c_float), ("phrases_ms", C.c_float), ("select_ms", C.c_float), ("eval_ms", C.c_float),
+                ("compact_ms", C.c_float), ("total_ms", C.c_float)]  # fmt: skip
+
+
+PERC_BY_QUERY, PERC_BY_DOCUMENT = 0, 1
+ERR_INVALID, ERR_UNSUPPORTED = -1, -3
+
+
 class TriIndexInfo(C.Structure):
     _fields_ = [
         ("index_bytes", C.c_uint64),
@@ -128,6 +148,8 @@ ABI_SYMBOLS = [
     "tri_comm_unique_id", "tri_comm_create", "tri_comm_create_custom", "tri_comm_destroy", "tri_gather_results",
     "tri_filter_create", "tri_filter_from_docset", "tri_filter_destroy", "tri_batch_set_filters",
     "tri_isect_run", "tri_isect_status", "tri_isect_results", "tri_isect_histogram", "tri_isect_get_info", "tri_isect_destroy",
+    "tri_perc_create", "tri_perc_query_status", "tri_perc_set_enabled", "tri_perc_get_info", "tri_perc_destroy", "tri_perc_match",
+    "tri_perc_result_pairs", "tri_perc_result_doc_counts", "tri_perc_result_get_info", "tri_perc_result_destroy",
 ]  # fmt: skip
 
 _hip = None
@@ -221,6 +243,18 @@ def hip_lib():
     L.tri_isect_destroy.argtypes = [vp]
     L.tri_isect_destroy.restype = None
     L.tri_batch_ranked.argtypes = [vp, vp, vp, vp]
+    L.tri_perc_create.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, C.POINTER(vp)]
+    L.tri_perc_query_status.argtypes = [vp, vp]
+    L.tri_perc_set_enabled.argtypes = [vp, vp, C.c_size_t, C.c_int]
+    L.tri_perc_get_info.argtypes = [vp, C.POINTER(TriPercInfo)]
+    L.tri_perc_destroy.argtypes = [vp]
+    L.tri_perc_destroy.restype = None
+    L.tri_perc_match.argtypes = [vp, C.POINTER(TriPercDocs), C.POINTER(vp)]
+    L.tri_perc_result_pairs.argtypes = [vp, C.c_int, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.tri_perc_result_doc_counts.argtypes = [vp, vp]
+    L.tri_perc_result_get_info.argtypes = [vp, C.POINTER(TriPercResultInfo)]
+    L.tri_perc_result_destroy.argtypes = [vp]
+    L.tri_perc_result_destroy.restype = None
     _hip = L
     return L
 
@@ -249,6 +283,8 @@ def host_lib():
     L.tri_synth_segment_terms.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.tri_synth_segment_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.tri_synth_queries.argtypes = [C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.tri_host_perc_lower.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64]
+    L.tri_host_perc_check_docs.argtypes = [C.POINTER(TriPercDocs), C.c_uint32, C.c_char_p, C.c_uint64]
     _host = L
     return L
 
@@ -508,6 +544,93 @@ class Intersection:
         if self.h:
             hip_lib().tri_isect_destroy(self.h)
             self.h = C.c_void_p()
+
+
+def perc_docs(doc_first, terms, freqs, positions, reserved=0):
+    """(tri_perc_docs, the arrays it points into) of a batch of documents: doc_first[ndocs + 1] into terms / freqs, positions concatenated."""
+    keep = (np.ascontiguousarray(doc_first, dtype=np.uint64), np.ascontiguousarray(terms, dtype=np.uint32), np.ascontiguousarray(freqs, dtype=np.uint32),
+            np.ascontiguousarray(positions, dtype=np.uint16))  # fmt: skip
+    d = TriPercDocs(keep[0].size - 1, keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data, keep[3].size, reserved)
+    return d, keep
+
+
+class PercolatorResult:
+    """The answer of one tri_perc_match call."""
+
+    def __init__(self, h, ndocs):
+        self.h, self.ndocs = h, ndocs
+
+    def pairs(self, order=PERC_BY_QUERY):
+        """(queries, documents) of every matching pair, in `order` (PERC_BY_QUERY / PERC_BY_DOCUMENT)."""
+        n = C.c_size_t()
+        _check(hip_lib().tri_perc_result_pairs(self.h, order, None, None, 0, C.byref(n)))
+        q, d = np.zeros(max(1, n.value), dtype=np.uint32), np.zeros(max(1, n.value), dtype=np.uint32)
+        _check(hip_lib().tri_perc_result_pairs(self.h, order, q.ctypes.data, d.ctypes.data, n.value, C.byref(n)))
+        return q[: n.value], d[: n.value]
+
+    def doc_counts(self):
+        c = np.zeros(self.ndocs, dtype=np.uint32)
+        _check(hip_lib().tri_perc_result_doc_counts(self.h, c.ctypes.data))
+        return c
+
+    @property
+    def info(self):
+        i = TriPercResultInfo()
+        _check(hip_lib().tri_perc_result_get_info(self.h, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in TriPercResultInfo._fields_ if k != "reserved"}
+
+    def close(self):
+        if self.h:
+            hip_lib().tri_perc_result_destroy(self.h)
+            self.h = None
+
+
+class Percolator:
+    """A resident set of stored queries (tri_perc_create, percolator.h:47-58): postfix programs whose TERM operands index the percolator's own
+    dictionary 0 .. nterms-1.  match(documents) tests a batch of documents against all of them."""
+
+    def __init__(self, dev, programs, nterms):
+        flat_prog, q = flatten(programs)
+        self.dev, self.nq, self.h = dev, len(programs), C.c_void_p()
+        _check(hip_lib().tri_perc_create(dev.h, flat_prog.ctypes.data, flat_prog.size, q.ctypes.data, self.nq, nterms, C.byref(self.h)))
+
+    @classmethod
+    def create(cls, dev, programs, nterms):
+        return cls(dev, programs, nterms)
+
+    @classmethod
+    def from_flat(cls, dev, flat_prog, queries, nterms):
+        """a set laid out by the caller: the flat u32 program and the (nq, 2) u32 table of (offset, length), as flatten() returns them"""
+        self = object.__new__(cls)
+        self.dev, self.nq, self.h = dev, len(queries), C.c_void_p()
+        _check(hip_lib().tri_perc_create(dev.h, flat_prog.ctypes.data, flat_prog.size, queries.ctypes.data, self.nq, nterms, C.byref(self.h)))
+        return self
+
+    def status(self):
+        st = np.zeros(max(1, self.nq), dtype=np.int32)
+        _check(hip_lib().tri_perc_query_status(self.h, st.ctypes.data))
+        return st[: self.nq]
+
+    def set_enabled(self, queries, enabled=True):
+        q = np.ascontiguousarray(queries, dtype=np.uint32)
+        _check(hip_lib().tri_perc_set_enabled(self.h, q.ctypes.data, q.size, int(bool(enabled))))
+
+    @property
+    def info(self):
+        i = TriPercInfo()
+        _check(hip_lib().tri_perc_get_info(self.h, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in TriPercInfo._fields_ if k != "reserved"}
+
+    def match(self, doc_first, terms, freqs, positions):
+        d, keep = perc_docs(doc_first, terms, freqs, positions)
+        r = C.c_void_p()
+        _check(hip_lib().tri_perc_match(self.h, C.byref(d), C.byref(r)))
+        return PercolatorResult(r, d.ndocs)
+
+    def close(self):
+        if self.h:
+            hip_lib().tri_perc_destroy(self.h)
+            self.h = None
 
 
 def host_encode_google(docs, freqs, positions, term_first, payload_lens=None, payloads=None):
