@@ -214,6 +214,33 @@ def test_tree_limits(T, dev):
         p.close()
 
 
+def test_the_wide_fold_at_its_limits(T, dev):
+    """tests/wide_tree_cases.py's programs over terms 0 .. 59 as ONE stored set — matchsomes of 300 and 1020 children at thresholds around 255 / 256 and 510 / 511 (the
+    ninth and tenth counter plane of csrc/tree_fold.hpp), a 1024-node OR, the 64-level alternation and the chain of nested matchsomes (64 stack words each) — against 130
+    documents, document j holding terms 0 .. j % 61 - 1: every count 0 .. 60 occurs, and the restatement's answer is the closed form h(j) >= ceil(thr / multiplicity);
+    with perc_prune at 1 and at 0."""
+    import wide_tree_cases as W
+
+    progs, docs = W.perc_programs(), W.perc_docs()
+    bits = PC.match_batch(progs, docs)
+    for name, b in zip(W.PERC_CASES, bits):
+        assert b == sum(1 << j for j in range(len(docs)) if j % W.HMOD >= W.CLOSED[name]), name
+    assert bits[W.PERC_CASES.index("some300_255")] != bits[W.PERC_CASES.index("some300_256")] == bits[W.PERC_CASES.index("some300_260")]
+    arrays = PC.arrays_of(docs)
+    p = T.Percolator(dev, progs, W.NLADDER)
+    try:
+        assert p.status().tolist() == [0] * len(progs)
+        for prune in (1, 0):
+            dev.set_option("perc_prune", prune)
+            try:
+                info = check(T, p, progs, arrays, docs, bits)
+            finally:
+                dev.set_option("perc_prune", 1)
+            assert info["hit_queries"] == len(progs) and (prune or info["evaluated"] == len(progs))
+    finally:
+        p.close()
+
+
 def test_many_queries_and_the_prune(T, dev):
     """70 000 stored programs over 64 documents: past 65 535 in every count a grid is sized by; perc_prune 0 and 1 give the same pairs, 1 evaluates fewer queries"""
     rng = np.random.default_rng(3)
