@@ -9,6 +9,7 @@ import pytest
 
 import oracle_lib as O
 import perc_cases as PC
+from perc_limit_cases import check, cut  # (one call against the restatement, both orders exact: shared with tests/test_gpu_perc_limits.py)
 from random_programs import random_program
 
 pytestmark = pytest.mark.gpu
@@ -54,33 +55,6 @@ def wide_corpus(fixtures):
     ix = O.Index.generate(4097, c["V"], c["slots"], c["seed"])
     arrays = PC.corpus_batch(ix.corpus, 4097)
     return c["V"], arrays, PC.docs_of(*arrays)
-
-
-def cut(arrays, ndocs):
-    doc_first, terms, freqs, pos = arrays
-    n = int(doc_first[ndocs])
-    return doc_first[: ndocs + 1], terms[:n], freqs[:n], pos[: int(freqs[:n].sum())]
-
-
-def check(T, p, programs, arrays, docs=None, bits=None):
-    """One call; both orders and the per-document counts equal the restatement's.  Returns the result's info."""
-    ndocs = len(arrays[0]) - 1
-    if bits is None:
-        bits = PC.match_batch(programs, docs if docs is not None else PC.docs_of(*arrays))
-    (q1, d1), (q2, d2), counts = PC.pairs_of(bits, ndocs)
-    r = p.match(*arrays)
-    try:
-        gq, gd = r.pairs(T.PERC_BY_QUERY)
-        assert gd.size == 0 or int(gd.max()) < ndocs
-        assert np.array_equal(gq, q1) and np.array_equal(gd, d1)
-        gq, gd = r.pairs(T.PERC_BY_DOCUMENT)
-        assert np.array_equal(gq, q2) and np.array_equal(gd, d2)
-        assert np.array_equal(r.doc_counts(), counts)
-        info = r.info
-        assert info["pairs"] == q1.size and info["ndocs"] == ndocs and info["hit_queries"] == sum(1 for b in bits if b)
-        return info
-    finally:
-        r.close()
 
 
 def negations(T):

@@ -79,19 +79,30 @@ __global__ __launch_bounds__(PERC_WG) void k_perc_scan_sums(const uint32_t *__re
 // one workgroup: sums[] becomes its exclusive scan; total[0 .. 1] = the sum of everything, 64 bits
 __global__ __launch_bounds__(PERC_WG) void k_perc_scan_tops(uint32_t *__restrict__ sums, const uint32_t nb, uint32_t *__restrict__ total) {
         __shared__ uint32_t red[PERC_WG / 64 + 1];
-        unsigned long long run = 0;
+        __shared__ unsigned long long part[PERC_WG / 64];
+        uint32_t run = 0;            // the offsets: 32 bits
+        unsigned long long mine = 0; // the total, this thread's share: ONE round of 256 block sums can reach 2^32 and more, so the round's 32-bit `tot` cannot carry it
         for (uint32_t b0 = 0; b0 < nb; b0 += PERC_WG) { // (uniform)
                 const uint32_t i = b0 + threadIdx.x;
                 const uint32_t v = i < nb ? sums[i] : 0u;
                 uint32_t tot;
                 const uint32_t ex = perc_block_scan(red, v, tot);
                 if (i < nb)
-                        sums[i] = (uint32_t)run + ex; // (a call of 2^32 pairs or more is refused from total[]: the wrapped offsets are never used)
+                        sums[i] = run + ex; // (a call of 2^32 pairs or more is refused from total[]: the wrapped offsets are never used)
                 run += tot;
+                mine += v;
         }
+        for (int k = 32; k; k >>= 1)
+                mine += __shfl_xor(mine, k);
+        if ((threadIdx.x & 63u) == 0)
+                part[threadIdx.x >> 6] = mine;
+        __syncthreads();
         if (threadIdx.x == 0) {
-                total[0] = (uint32_t)run;
-                total[1] = (uint32_t)(run >> 32);
+                unsigned long long all = 0;
+                for (uint32_t k = 0; k < PERC_WG / 64; ++k)
+                        all += part[k];
+                total[0] = (uint32_t)all;
+                total[1] = (uint32_t)(all >> 32);
         }
 }
 // out[i] = the sum of the elements before i (in == out is fine: a thread reads its elements before it writes them)
