@@ -39,7 +39,9 @@ extern "C" {
                                 within 9: tri_isect_run / _status / _results / _histogram / _get_info / _destroy, options isect_max_bytes / isect_max_masks / isect_max_runs
                                 (Trinity::intersect: token-set co-occurrence counts; no existing struct grew);
                                 within 9: tri_perc_create / _query_status / _set_enabled / _get_info / _destroy / _match, tri_perc_result_pairs / _doc_counts / _get_info / _destroy,
-                                options perc_max_bytes / perc_prune (the percolator: documents matched against a resident set of stored queries; no existing struct grew) */
+                                options perc_max_bytes / perc_prune (the percolator: documents matched against a resident set of stored queries; no existing struct grew);
+                                within 9: tri_encode_lucene_payloads / tri_commit_lucene_payloads (the Lucene-shaped codec carries hit payloads: written, merged by
+                                tri_merge_lucene, read by tri_decode_hits[_at] and tri_batch_matched_payloads; no struct grew) */
 
 /* status codes */
 #define TRI_OK 0
@@ -298,8 +300,11 @@ int tri_decode_terms(tri_index *, const uint32_t *terms, size_t n, uint32_t *doc
  * Per hit k: positions[k] = term_hit::pos, the u16 running sum of the document's position deltas (it restarts at 0 with every document);
  * payload_lens[k] = term_hit::payloadLen; payloads[k] = term_hit::payload, the word as materialize_hits leaves it: the word and the current length restart at
  * 0 with each document, a new payload overwrites only the word's first min(len, 8) bytes, length 0 clears it (what tri_batch_matched_payloads delivers for the
- * matches of a query).  A LUCENE index gives lengths and words of 0: these segments carry no payloads.  payload_lens and payloads are both NULL (positions
- * only) or both given.
+ * matches of a query).  That is the GOOGLE codec's rule (google_codec.cpp:547-583).  A LUCENE index follows lucene_codec.cpp:767-856 instead: the word is cleared
+ * and the hit's own payloadLen bytes are copied for EVERY hit, so a hit's length and word depend on that hit alone and nothing is carried from hit to hit — the
+ * two codecs answer the same for the same postings exactly when, within every document, no non-zero length is shorter than an earlier non-zero length since
+ * the last zero-length hit.  The upload validates a LUCENE segment's payloads (every length <= 8, a block's byte count against its lengths, the tail's end against
+ * the term's chunk: TRI_ERR_FORMAT otherwise).  payload_lens and payloads are both NULL (positions only) or both given.
  *
  * tri_decode_hits — whole lists, for EVERY document of each term, in list order.  out_offsets[n + 1] are prefix offsets in hits; term i's hits lie document
  * after document, document j of the term owning freq[j] hits, freq being exactly what tri_decode_terms returns for it: the caller's cumulative sum of those
@@ -685,15 +690,15 @@ int tri_merge_google(tri_dev *, tri_index *const *parts, size_t nparts, const ui
                      tri_term *terms_out, tri_commit_stats *stats);
 /* Codecs::Lucene::IndexSession::merge (lucene_codec.cpp:963-1396), likewise for a whole dictionary (ABI 8): the same walk — participants most recent first, the most recent
  * holder's posting wins, dropped when that participant masks the document — over lucene_codec indexes uploaded WITH their hits.data; what is kept is re-encoded by the device's
- * Lucene-shaped encoder (tri_encode_lucene: PFOR128 ints() payload, positions only — a participant's payloads are not carried, as in tri_encode_lucene): index_out / hits_out =
- * the merged `index` and `hits.data`, terms_out[t] as tri_encode_lucene.  The bytes equal the host encoder's over the merged postings; the walk is the one
+ * Lucene-shaped encoder (tri_encode_lucene_payloads: PFOR128 ints() payload; a kept posting's hits go over with their payloads, length and bytes, as append_from copies
+ * them): index_out / hits_out = the merged `index` and `hits.data`, terms_out[t] as tri_encode_lucene.  The bytes equal the host encoder's over the merged postings; the walk is the one
  * tests/golden/ref_merge.json pins for the Google codec (the reference's Lucene side needs FastPFor: unbuildable here, so this pair stays unpinned by reference bytes).
  * index_out == NULL: sizing call (*index_len, *hits_len). */
 int tri_merge_lucene(tri_dev *, tri_index *const *parts, size_t nparts, const uint32_t *part_terms, size_t nterms, uint8_t *index_out, size_t cap, size_t *index_len,
                      uint8_t *hits_out, size_t hits_cap, size_t *hits_len, tri_term *terms_out, tri_commit_stats *stats);
 
 /* tri_commit_google with the session's encoder being the Lucene-shaped codec's (commit is codec-agnostic: sess->new_encoder(), indexer.cpp:323): the same sort
- * and gather, then tri_encode_lucene's device encoder — `index` + `hits.data`; payload-less hits. */
+ * and gather, then tri_encode_lucene's device encoder — `index` + `hits.data`; payload-less hits (with payloads: tri_commit_lucene_payloads below). */
 int tri_commit_lucene(tri_dev *, const uint32_t *term_ids, const uint32_t *doc_ids, const uint32_t *freqs, const uint16_t *positions, size_t npostings, size_t npositions,
                       uint8_t *index_out, size_t cap, size_t *index_len, uint8_t *hits_out, size_t hits_cap, size_t *hits_len, uint32_t *term_ids_out, tri_term *terms_out,
                       size_t terms_cap, size_t *nterms, tri_commit_stats *stats);
@@ -706,6 +711,20 @@ int tri_commit_lucene(tri_dev *, const uint32_t *term_ids, const uint32_t *doc_i
 int tri_encode_google_payloads(tri_dev *, const uint32_t *docs, const uint32_t *freqs, const uint16_t *positions, const uint8_t *payload_lens,
                                const uint64_t *payloads, size_t npositions, const uint64_t *term_first, size_t nterms, uint8_t *index_out, size_t cap,
                                size_t *index_len, tri_term *terms_out);
+
+/* tri_encode_lucene / tri_commit_lucene with hit payloads (Encoder::new_hit(pos, payload), lucene_codec.cpp:240-304, 342-366): payload_lens[h] (0 .. 8) and
+ * payloads[h] (the payload's first byte in the low 8 bits) per hit, parallel to positions[], as in tri_encode_google_payloads / tri_commit_google.  In hits.data a
+ * full block of 128 hits is ints(position deltas) ints(payload lengths) varbyte(sum of the lengths) the payloads' bytes in hit order; the tail of fewer than 128
+ * hits is per hit varbyte(position delta << 1 | the length differs from the tail's previous hit's) [u8 new length] — that state starts at 0 with the tail and
+ * runs across document boundaries — and then the tail's payload bytes.  The term header's positionsChunkSize and the skiplist's lastHitsBlockOffset count the
+ * payload bytes.  A position-0 hit WITH a payload is a counted hit; one without is refused.  Byte-identical to trinity_amd/csrc/host/lucene_encoder.hpp.
+ * payload_lens == NULL: no hit has a payload — tri_encode_lucene / tri_commit_lucene, byte for byte.  payload_lens without payloads: TRI_ERR_INVALID. */
+int tri_encode_lucene_payloads(tri_dev *, const uint32_t *docs, const uint32_t *freqs, const uint16_t *positions, const uint8_t *payload_lens, const uint64_t *payloads,
+                               size_t npositions, const uint64_t *term_first, size_t nterms, uint8_t *index_out, size_t index_cap, size_t *index_len, uint8_t *hits_out,
+                               size_t hits_cap, size_t *hits_len, tri_term *terms_out);
+int tri_commit_lucene_payloads(tri_dev *, const uint32_t *term_ids, const uint32_t *doc_ids, const uint32_t *freqs, const uint16_t *positions, const uint8_t *payload_lens,
+                               const uint64_t *payloads, size_t npostings, size_t npositions, uint8_t *index_out, size_t cap, size_t *index_len, uint8_t *hits_out,
+                               size_t hits_cap, size_t *hits_len, uint32_t *term_ids_out, tri_term *terms_out, size_t terms_cap, size_t *nterms, tri_commit_stats *stats);
 
 #ifdef __cplusplus
 }

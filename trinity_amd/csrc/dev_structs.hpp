@@ -22,6 +22,9 @@ struct DevTerm {
 constexpr uint32_t TERM_FULL_BLOCKS = 1u;
 constexpr uint32_t TERM_SPARSE = 2u; // GOOGLE: fewer than 1 document in 28 docIDs on average — most blocks hold a multi-byte delta, so the
                                      // bitmap kernel parses them from registers in place instead of trying the static one-byte path
+constexpr uint32_t TERM_HIT_PAYLOADS = 4u; // LUCENE with hits.data: some hit of the term carries a payload; pdir_off[term] is its row in pdir[]
+                                           // ({length group offset, payload bytes offset, payload bytes before quarters 1 | 2 << 10 | 3 << 20} per full
+                                           // 128-hit block, then where the tail's payload bytes start — all offsets into hits.data)
 
 // documents in block b of term t
 #define TRI_BLOCK_N(t, b, index, off) (((t).flags & TERM_FULL_BLOCKS) ? ((b) + 1 == (t).nblocks ? (t).last_n : 32u) : (uint32_t)(index)[(off)-1])

@@ -3,7 +3,9 @@
 // Write side of the codec seam, same call protocol as Trinity::Codecs::Encoder (codecs.h:176-200).  The container is the
 // reference's (lucene_codec.cpp:163-388): per term a 14-byte header {hitsDataOffset, sumHits,
 // positionsChunkSize, skiplistSize}, 128-document blocks as two ints() groups (doc deltas, freqs), a varbyte tail, one
-// 22-byte skiplist entry per block; hit positions go to a separate hits.data stream in blocks of 128 hits.  The ints()
+// 22-byte skiplist entry per block; hit positions and payloads go to a separate hits.data stream in blocks of 128 hits
+// (a full block: ints(position deltas) ints(payload lengths) varbyte(payload bytes) the bytes; the tail: per hit
+// varbyte(delta << 1 | length changed) [u8 length], then the tail's payload bytes).  The ints()
 // payload is this repo's PFOR128 (include/pfor128.md) because the reference's (lemire/FastPFor) is absent: PARITY
 // UNPINNED for those bytes.  New code; independent of oracle/.
 #pragma once
@@ -110,6 +112,7 @@ namespace trinity_amd {
                                 uint32_t deltas[BLOCK_SIZE], freqs[BLOCK_SIZE], hitPos[BLOCK_SIZE], hitLen[BLOCK_SIZE];
                                 uint32_t lastDoc{0}, buffered{0}, hitsInBlock{0}, sumHits{0}, termDocs{0}, termStart{0}, posStart{0};
                                 uint32_t lastHitsBlockOffset{0}, lastHitsBlockTotalHits{0}, lastPos{0};
+                                std::vector<uint8_t> payloadsBuf; // the payload bytes of the hits buffered in hitPos / hitLen, in hit order
 
                                 template <class T>
                                 static void put(std::vector<uint8_t> &o, T v) {
@@ -133,6 +136,7 @@ namespace trinity_amd {
                                         posStart = uint32_t(sess->positionsOut.size());
                                         lastHitsBlockOffset = lastHitsBlockTotalHits = 0;
                                         skiplist.clear();
+                                        payloadsBuf.clear();
                                         put<uint32_t>(sess->indexOut, posStart);
                                         put<uint32_t>(sess->indexOut, 0); // sumHits, patched by end_term
                                         put<uint32_t>(sess->indexOut, 0); // positions chunk size
@@ -151,18 +155,25 @@ namespace trinity_amd {
                                         lastDoc = id;
                                         lastPos = 0;
                                 }
-                                void new_hit(uint32_t pos) { // payload-less hits only (the synthetic corpus carries none)
-                                        if (!pos)
+                                // (lucene_codec.cpp:240-304; the same call as google_encoder.hpp's: a position-0 hit WITH a payload is a counted hit, one without is none)
+                                void new_hit(uint32_t pos, const uint8_t *hitPayload = nullptr, uint8_t payloadLen = 0) {
+                                        if (!pos && !payloadLen)
                                                 return;
+                                        if (payloadLen > 8)
+                                                throw std::invalid_argument("a payload holds at most 8 bytes (lucene_codec.cpp:262)");
                                         ++freqs[buffered];
                                         hitPos[hitsInBlock] = pos - lastPos;
-                                        hitLen[hitsInBlock] = 0;
+                                        hitLen[hitsInBlock] = payloadLen;
                                         lastPos = pos;
+                                        if (payloadLen)
+                                                payloadsBuf.insert(payloadsBuf.end(), hitPayload, hitPayload + payloadLen);
                                         if (++hitsInBlock == BLOCK_SIZE) {
                                                 sumHits += hitsInBlock;
                                                 ints_encode(hitPos, sess->positionsOut, payload);
                                                 ints_encode(hitLen, sess->positionsOut, payload);
-                                                put_varbyte32(sess->positionsOut, 0); // payload bytes of this block
+                                                put_varbyte32(sess->positionsOut, uint32_t(payloadsBuf.size())); // payload bytes of this block, then the bytes
+                                                sess->positionsOut.insert(sess->positionsOut.end(), payloadsBuf.begin(), payloadsBuf.end());
+                                                payloadsBuf.clear();
                                                 lastHitsBlockTotalHits = sumHits;
                                                 lastHitsBlockOffset = uint32_t(sess->positionsOut.size()) - posStart;
                                                 hitsInBlock = 0;
@@ -179,8 +190,17 @@ namespace trinity_amd {
                                                         put_varbyte32(out, deltas[i]);
                                                         put_varbyte32(out, freqs[i]);
                                                 }
-                                        for (uint32_t i = 0; i < hitsInBlock; ++i) // tail hits: (posDelta << 1 | newLen) [len]; no payloads here
-                                                put_varbyte32(sess->positionsOut, hitPos[i] << 1);
+                                        uint32_t lastLen = 0; // tail hits: (posDelta << 1 | newLen) [len], then the tail's payload bytes (lucene_codec.cpp:342-366)
+                                        for (uint32_t i = 0; i < hitsInBlock; ++i) {
+                                                if (hitLen[i] != lastLen) {
+                                                        lastLen = hitLen[i];
+                                                        put_varbyte32(sess->positionsOut, hitPos[i] << 1 | 1);
+                                                        sess->positionsOut.push_back(uint8_t(lastLen));
+                                                } else
+                                                        put_varbyte32(sess->positionsOut, hitPos[i] << 1);
+                                        }
+                                        sess->positionsOut.insert(sess->positionsOut.end(), payloadsBuf.begin(), payloadsBuf.end());
+                                        payloadsBuf.clear();
                                         const uint32_t posSize = uint32_t(sess->positionsOut.size()) - posStart;
                                         const uint16_t nskip = uint16_t(skiplist.size());
                                         std::memcpy(out.data() + termStart + 4, &sumHits, 4);

@@ -139,9 +139,11 @@ void tri_host_plan_query_maps(void *p, uint32_t *slot_of_query, int32_t *qstatus
 // ---- the Lucene-shaped encoder two ways, for the CPU tests: the sequential host encoder (lucene_encoder.hpp: the state machine the reference's encoder is),
 //      and the device encoder's UNITS (lucene_enc_units.hpp) run in plain loops with serial prefix sums in between — exactly what k_lencode.hpp's kernels and
 //      the device scans do.  Both write index / hits.data / the term table {documents, offset, size}; return 0, or -1 when a buffer is too small.
+//      The *_payloads forms take the hits' payloads parallel to pos[] (plens[h] 0 .. 8 bytes, the low bytes of payloads[h]; plens == nullptr: none, and then
+//      they ARE the plain forms); the sequential one returns -2 for what the encoder refuses (a payload of more than 8 bytes).
 extern "C" {
-int tri_host_lucene_encode(const uint32_t *docs, const uint32_t *freqs, const uint16_t *pos, const uint64_t *term_first, uint64_t nterms, uint8_t *index_out, uint64_t icap,
-                           uint64_t *ilen, uint8_t *hits_out, uint64_t hcap, uint64_t *hlen, uint32_t *terms3) {
+int tri_host_lucene_encode_payloads(const uint32_t *docs, const uint32_t *freqs, const uint16_t *pos, const uint8_t *plens, const uint64_t *payloads, const uint64_t *term_first,
+                                    uint64_t nterms, uint8_t *index_out, uint64_t icap, uint64_t *ilen, uint8_t *hits_out, uint64_t hcap, uint64_t *hlen, uint32_t *terms3) try {
         using namespace trinity_amd::Codecs;
         Lucene::IndexSession sess;
         Lucene::Encoder enc(&sess);
@@ -150,8 +152,13 @@ int tri_host_lucene_encode(const uint32_t *docs, const uint32_t *freqs, const ui
                 enc.begin_term();
                 for (uint64_t p = term_first[t]; p < term_first[t + 1]; ++p) {
                         enc.begin_document(docs[p]);
-                        for (uint32_t i = 0; i < freqs[p]; ++i)
-                                enc.new_hit(pos[h++]);
+                        for (uint32_t i = 0; i < freqs[p]; ++i, ++h) {
+                                uint8_t bytes[8];
+                                const uint8_t len = plens ? plens[h] : 0;
+                                for (uint32_t k = 0; k < 8; ++k)
+                                        bytes[k] = len ? (uint8_t)(payloads[h] >> (8 * k)) : 0;
+                                enc.new_hit(pos[h], bytes, len);
+                        }
                         enc.end_document();
                 }
                 trinity_amd::term_index_ctx tctx;
@@ -166,9 +173,15 @@ int tri_host_lucene_encode(const uint32_t *docs, const uint32_t *freqs, const ui
         if (*hlen) // (a session without hits has no buffer to copy from)
                 memcpy(hits_out, sess.positionsOut.data(), *hlen);
         return 0;
+} catch (const std::invalid_argument &) {
+        return -2;
 }
-int tri_host_lucene_encode_units(const uint32_t *docs, const uint32_t *freqs, const uint16_t *pos, const uint64_t *term_first, uint64_t nterms, uint8_t *index_out, uint64_t icap,
-                                 uint64_t *ilen, uint8_t *hits_out, uint64_t hcap, uint64_t *hlen, uint32_t *terms3) {
+int tri_host_lucene_encode(const uint32_t *docs, const uint32_t *freqs, const uint16_t *pos, const uint64_t *term_first, uint64_t nterms, uint8_t *index_out, uint64_t icap,
+                           uint64_t *ilen, uint8_t *hits_out, uint64_t hcap, uint64_t *hlen, uint32_t *terms3) {
+        return tri_host_lucene_encode_payloads(docs, freqs, pos, nullptr, nullptr, term_first, nterms, index_out, icap, ilen, hits_out, hcap, hlen, terms3);
+}
+int tri_host_lucene_encode_units_payloads(const uint32_t *docs, const uint32_t *freqs, const uint16_t *pos, const uint8_t *plens, const uint64_t *payloads, const uint64_t *term_first,
+                                          uint64_t nterms, uint8_t *index_out, uint64_t icap, uint64_t *ilen, uint8_t *hits_out, uint64_t hcap, uint64_t *hlen, uint32_t *terms3) {
         const uint64_t np = term_first[nterms];
         std::vector<uint64_t> hit_off(np + 1, 0), dblk_first(nterms + 1, 0), hblk_first(nterms + 1, 0);
         for (uint64_t p = 0; p < np; ++p)
@@ -178,7 +191,7 @@ int tri_host_lucene_encode_units(const uint32_t *docs, const uint32_t *freqs, co
                 hblk_first[t + 1] = hblk_first[t] + (hit_off[term_first[t + 1]] - hit_off[term_first[t]]) / LENC_BLOCK;
         }
         std::vector<uint32_t> hdelta(hit_off[np] + 1);
-        LencArgs a{docs, freqs, pos, hit_off.data(), term_first, hdelta.data(), dblk_first.data(), hblk_first.data(), nterms};
+        LencArgs a{docs, freqs, pos, hit_off.data(), term_first, hdelta.data(), dblk_first.data(), hblk_first.data(), nterms, plens, payloads};
         for (uint64_t p = 0; p < np; ++p)
                 lenc_unit_hdelta(a, p, hdelta.data());
         const uint64_t nd = dblk_first[nterms], nh = hblk_first[nterms];
@@ -207,6 +220,10 @@ int tri_host_lucene_encode_units(const uint32_t *docs, const uint32_t *freqs, co
                 terms3[3 * t] = (uint32_t)(term_first[t + 1] - term_first[t]), terms3[3 * t + 1] = (uint32_t)term_off[t], terms3[3 * t + 2] = lenc_term_index_size(a, pl, t);
         }
         return 0;
+}
+int tri_host_lucene_encode_units(const uint32_t *docs, const uint32_t *freqs, const uint16_t *pos, const uint64_t *term_first, uint64_t nterms, uint8_t *index_out, uint64_t icap,
+                                 uint64_t *ilen, uint8_t *hits_out, uint64_t hcap, uint64_t *hlen, uint32_t *terms3) {
+        return tri_host_lucene_encode_units_payloads(docs, freqs, pos, nullptr, nullptr, term_first, nterms, index_out, icap, ilen, hits_out, hcap, hlen, terms3);
 }
 }
 
@@ -257,6 +274,20 @@ uint32_t tri_host_index_hits_dir(void *h, uint32_t term, uint32_t *out, uint32_t
                 out[b] = H.blk_hits[t.first_block + b];
         *nfull = H.has_hdir && t.nblocks ? H.hdir[t.pad] : 0;
         return t.nblocks;
+}
+
+// LUCENE with hits.data: the term's payload directory as the upload records it (index_host.hpp pdir[]: {length group offset, payload bytes offset, payload bytes
+// before quarters 1 | 2 << 10 | 3 << 20} per full 128-hit group, then where the tail's payload bytes start).  Returns its words — 0: no hit of the term carries a
+// payload (the term is not flagged TERM_HIT_PAYLOADS and has no row) —, at most cap of them written to out
+uint32_t tri_host_index_payload_dir(void *h, uint32_t term, uint32_t *out, uint32_t cap) {
+        const HostIndex &H = *static_cast<HostIndex *>(h);
+        const DevTerm &t = H.terms[term];
+        if (!H.has_hdir || !(t.flags & TERM_HIT_PAYLOADS))
+                return 0;
+        const uint32_t n = 3 * H.hdir[t.pad] + 1;
+        for (uint32_t i = 0; out && i < n && i < cap; ++i)
+                out[i] = H.pdir[H.pdir_off[term] + i];
+        return n;
 }
 
 void tri_host_index_facts(void *h, uint64_t *info6, uint32_t *per_term3) {

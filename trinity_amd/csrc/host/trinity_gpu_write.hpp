@@ -124,15 +124,13 @@ namespace trinity_amd {
                         size_t indexLen = 0, hitsLen = 0, nterms = 0;
                         const uint8_t *pl = anyPayload ? payloadLens.data() : nullptr;
                         const uint64_t *pv = anyPayload ? payloads.data() : nullptr;
-                        if (codec == Codec::Lucene && anyPayload)
-                                throw invalid_argument("SegmentIndexSession::commit: the Lucene-shaped encoder of this engine carries no payloads");
                         auto call = [&](uint8_t *index, size_t icap, uint8_t *hits, size_t hcap, uint32_t *ids, tri_term *tctx, size_t tcap) {
                                 if (codec == Codec::Google)
                                         check(tri_commit_google(dev, termIDs.data(), docIDs.data(), freqs.data(), positions.data(), pl, pv, termIDs.size(), positions.size(), index, icap,
                                                                 &indexLen, ids, tctx, tcap, &nterms, &out.stats));
                                 else
-                                        check(tri_commit_lucene(dev, termIDs.data(), docIDs.data(), freqs.data(), positions.data(), termIDs.size(), positions.size(), index, icap, &indexLen,
-                                                                hits, hcap, &hitsLen, ids, tctx, tcap, &nterms, &out.stats));
+                                        check(tri_commit_lucene_payloads(dev, termIDs.data(), docIDs.data(), freqs.data(), positions.data(), pl, pv, termIDs.size(), positions.size(), index,
+                                                                         icap, &indexLen, hits, hcap, &hitsLen, ids, tctx, tcap, &nterms, &out.stats));
                         };
                         call(nullptr, 0, nullptr, 0, nullptr, nullptr, 0);
                         out.index.resize(indexLen);

@@ -41,6 +41,7 @@ struct HostIndex {
         std::vector<tri_term> tctx;
         std::vector<uint64_t> docbytes, hitbytes;
         std::vector<uint32_t> blk_last, blk_off, blk_hits, hdir, blk_doff, win;
+        std::vector<uint32_t> pdir, pdir_off; // LUCENE with hits.data: the payload directory of the terms flagged TERM_HIT_PAYLOADS; per term its row (else ~0)
         std::vector<RowRec> blk_rec;
         std::vector<uint8_t> dstream;
         uint32_t max_doc = 0, nwin = 0;
@@ -56,7 +57,7 @@ struct HostIndex {
         std::vector<uint8_t> dev_index, dev_hits;
         uint64_t transcoded_groups = 0;
         void release_device_columns() {
-                for (auto *v : {&blk_off, &blk_hits, &hdir, &blk_doff, &win})
+                for (auto *v : {&blk_off, &blk_hits, &hdir, &blk_doff, &win, &pdir, &pdir_off})
                         std::vector<uint32_t>().swap(*v);
                 std::vector<RowRec>().swap(blk_rec);
                 std::vector<uint8_t>().swap(dstream);
@@ -358,6 +359,8 @@ inline int build_host_index(const uint8_t *index, size_t len, const uint8_t *hit
                 blk_doff.reserve(len / 96 + nterms);
         }
         const bool want_hits = codec == TRI_CODEC_LUCENE && hits_len;
+        if (want_hits)
+                H.pdir_off.assign(nterms, 0xffffffffu);
         blk_last.reserve(len / 96 + nterms);
         blk_off.reserve(len / 96 + nterms);
         uint64_t postings = 0, docb = 0, hitb = 0;
@@ -477,21 +480,73 @@ inline int build_host_index(const uint8_t *index, size_t len, const uint8_t *hit
                                 const uint32_t nfull = sumHits / 128;
                                 dt.pad = (uint32_t)hdir.size();
                                 hdir.push_back(nfull);
+                                // the payloads are READ, not only stepped over: every length at most 8 (lucene_codec.cpp:262), a block's payloadBytes the sum of its
+                                // lengths, the tail's hits and payload bytes ending exactly where the chunk ends — a reader that trusts the directory below then
+                                // never leaves the chunk.  pdir rows of the term are kept only when one of its lengths is not zero
+                                const size_t pdir_at = H.pdir.size();
+                                bool any_payload = false;
                                 for (uint32_t hb = 0; hb < nfull; ++hb) {
                                         hdir.push_back((uint32_t)(hp - hits));
-                                        for (int g = 0; g < 2; ++g) {
-                                                const size_t used = h_ints_skip(hp, hend);
-                                                if (!used || hp + used > hend)
+                                        size_t used = h_ints_skip(hp, hend);
+                                        if (!used || hp + used > hend)
+                                                return herr(err, TRI_ERR_FORMAT, "term %zu: bad hits block %u", ti, hb);
+                                        hp += used;
+                                        const uint32_t len_off = (uint32_t)(hp - hits);
+                                        uint32_t sum = 0, quarter[4] = {0, 0, 0, 0};
+                                        if (hp + 1 < hend && !hp[0] && !hp[1]) // (128 zero lengths: what every payload-less writer leaves)
+                                                used = 2;
+                                        else {
+                                                used = h_ints_decode(hp, hend, vals);
+                                                if (!used)
                                                         return herr(err, TRI_ERR_FORMAT, "term %zu: bad hits block %u", ti, hb);
-                                                hp += used;
+                                                for (uint32_t i = 0; i < 128; ++i) {
+                                                        if (vals[i] > 8)
+                                                                return herr(err, TRI_ERR_FORMAT, "term %zu: hits block %u: a payload of %u bytes (at most 8: lucene_codec.cpp:262)", ti, hb, vals[i]);
+                                                        quarter[i >> 5] += vals[i];
+                                                }
+                                                sum = quarter[0] + quarter[1] + quarter[2] + quarter[3];
                                         }
+                                        hp += used;
+                                        if (hp >= hend || hp + h_vb_len(*hp) > hend)
+                                                return herr(err, TRI_ERR_FORMAT, "term %zu: hits block %u is truncated", ti, hb);
                                         uint32_t payloadBytes;
                                         hp += h_vb_get(hp, payloadBytes);
-                                        if (hp + payloadBytes > hend)
+                                        if (payloadBytes != sum)
+                                                return herr(err, TRI_ERR_FORMAT, "term %zu: hits block %u declares %u payload bytes, its lengths add up to %u", ti, hb, payloadBytes, sum);
+                                        if ((uint64_t)(hend - hp) < payloadBytes)
                                                 return herr(err, TRI_ERR_FORMAT, "term %zu: hits block %u payload overruns the chunk", ti, hb);
+                                        // (a quarter's payload bytes start at most 3 * 32 * 8 = 768 bytes into the block's: 10 bits each)
+                                        H.pdir.insert(H.pdir.end(), {len_off, (uint32_t)(hp - hits), quarter[0] | (quarter[0] + quarter[1]) << 10 | (quarter[0] + quarter[1] + quarter[2]) << 20});
+                                        any_payload |= sum != 0;
                                         hp += payloadBytes;
                                 }
                                 hdir.push_back((uint32_t)(hp - hits));
+                                uint32_t tail_len = 0, tail_sum = 0;
+                                for (uint32_t i = 0; i < sumHits % 128; ++i) {
+                                        if (hp >= hend || hp + h_vb_len(*hp) > hend)
+                                                return herr(err, TRI_ERR_FORMAT, "term %zu: the hits tail is truncated", ti);
+                                        uint32_t v;
+                                        hp += h_vb_get(hp, v);
+                                        if (v & 1) {
+                                                if (hp >= hend)
+                                                        return herr(err, TRI_ERR_FORMAT, "term %zu: the hits tail is truncated", ti);
+                                                tail_len = *hp++;
+                                                if (tail_len > 8)
+                                                        return herr(err, TRI_ERR_FORMAT, "term %zu: the hits tail: a payload of %u bytes (at most 8: lucene_codec.cpp:262)", ti, tail_len);
+                                        }
+                                        tail_sum += tail_len;
+                                }
+                                if ((uint64_t)(hend - hp) < tail_sum)
+                                        return herr(err, TRI_ERR_FORMAT, "term %zu: the hits tail's %u payload bytes overrun the chunk", ti, tail_sum);
+                                if ((uint64_t)(hend - hp) != tail_sum)
+                                        return herr(err, TRI_ERR_FORMAT, "term %zu: %llu stray bytes behind the hits tail", ti, (unsigned long long)(hend - hp) - tail_sum);
+                                H.pdir.push_back((uint32_t)(hp - hits)); // where the tail's payload bytes start
+                                any_payload |= tail_sum != 0;
+                                if (any_payload) {
+                                        dt.flags |= TERM_HIT_PAYLOADS;
+                                        H.pdir_off[ti] = (uint32_t)pdir_at;
+                                } else
+                                        H.pdir.resize(pdir_at);
                         }
                         const uint64_t db = (uint64_t)(end - base); // 14-byte header + block bytes, no skiplist, no hits.data
                         H.docbytes[ti] = db;

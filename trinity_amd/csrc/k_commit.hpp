@@ -168,9 +168,9 @@ __global__ __launch_bounds__(256) void k_merge_hits(const uint8_t *__restrict__ 
         }
 }
 // ... LUCENE: a term's positions are ONE stream in hits.data, found by count (blk_hits[]: the hits before the row; hdir[]: the 128-hit blocks' offsets — k_phrase.hpp);
-// this engine's Lucene-shaped segments carry no payloads (lucene_encoder.hpp), so length and word are zero
+// a hit's payload length and word come from its ordinal (lucene_pay_stream.hpp) for the terms flagged TERM_HIT_PAYLOADS, and are zero for every other term
 __global__ __launch_bounds__(256) void k_merge_hits_lucene(const uint8_t *__restrict__ hits, const uint32_t *__restrict__ blk_hits, const uint32_t *__restrict__ hdir,
-                                                           const DevTerm *__restrict__ terms, const MergeJob *__restrict__ jobs, const uint32_t njobs, const uint32_t *__restrict__ freqs,
+                                                           const uint32_t *__restrict__ pdir, const DevTerm *__restrict__ terms, const MergeJob *__restrict__ jobs, const uint32_t njobs, const uint32_t *__restrict__ freqs,
                                                            const uint64_t *__restrict__ hit_off, uint16_t *__restrict__ pos_out, uint8_t *__restrict__ plens_out,
                                                            uint64_t *__restrict__ payloads_out) {
         const HitCtx ctx{hits, blk_hits, hdir};
@@ -188,6 +188,7 @@ __global__ __launch_bounds__(256) void k_merge_hits_lucene(const uint8_t *__rest
                                 continue;
                         HitStream<CODEC_LUCENE> s;
                         s.init(ctx, t.pad, blk_hits[gb]);
+                        const bool carries = (t.flags & TERM_HIT_PAYLOADS) != 0;
                         for (uint32_t i = 0; i < n; ++i) {
                                 const uint32_t f = freqs[at + i];
                                 uint64_t dst = hit_off[at + i];
@@ -195,10 +196,14 @@ __global__ __launch_bounds__(256) void k_merge_hits_lucene(const uint8_t *__rest
                                 for (uint32_t h = 0; h < f; ++h, ++dst) {
                                         pos += s.next();
                                         pos_out[dst] = (uint16_t)pos;
-                                        plens_out[dst] = 0;
-                                        payloads_out[dst] = 0;
+                                        if (!carries) {
+                                                plens_out[dst] = 0;
+                                                payloads_out[dst] = 0;
+                                        }
                                 }
                         }
+                        if (carries) // (the row's hits lie one after the other in the outputs, as in hits.data: hit_off[] is the running sum of the frequencies)
+                                lpay_fill(hits, hdir, t.pad, pdir, pdir[job.term], blk_hits[gb], total, plens_out + hit_off[at], payloads_out + hit_off[at]);
                 }
         }
 }

@@ -1,7 +1,7 @@
 // k_decode_hits.hpp — the hits of whole postings lists and of (term, document) pairs (codec seam: materialize_hits)
 // Part of libtrinity_hip.so (MI355X / gfx950); included by trinity_hip.hip.  New code, no reference source.
 #pragma once
-#include "k_phrase.hpp"
+#include "lucene_pay_stream.hpp"
 
 // Codecs::PostingsListIterator::materialize_hits (codecs.h:211-246; google_codec.cpp:533-594; lucene_codec.cpp:767-856) for EVERY document of a
 // list (tri_decode_hits) or for chosen documents (tri_decode_hits_at).  Per hit: term_hit::pos — the u16 running sum of the position deltas,
@@ -25,6 +25,9 @@
 //                  That needs the pieces' starts without a parse, so a long document inside a walked GOOGLE block stays with its lane
 // Pairs, two passes (a lane per pair): k_hits_at_freq brackets the block through blk_last[], finds the slot with DeltaStream and reads the
 // frequency; the host scans the frequencies; k_hits_at_write locates the hits as k_phrase / k_rich do and stores them.
+// LUCENE payloads (lucene_pay_stream.hpp): a hit's (length, word) depend on its ordinal alone, so for whole lists they are filled by a kernel of their own over
+// the hit blocks of the terms flagged TERM_HIT_PAYLOADS (k_decode_hit_payloads, behind k_decode_hits, which has stored zeros), and for pairs by the lane that
+// wrote the pair's positions, through LPayStream.  Terms without payloads, and calls without payload outputs, run what they ran before.
 // All stores are plain vector stores; nothing here keeps state on the index.
 struct HitsJob {
         uint32_t term;
@@ -346,7 +349,8 @@ __global__ __launch_bounds__(256) void k_hits_at_freq(const uint8_t *__restrict_
 
 template <int CODEC>
 __global__ __launch_bounds__(256) void k_hits_at_write(const uint8_t *__restrict__ index, const uint8_t *__restrict__ hits, const uint32_t *__restrict__ blk_off,
-                                                       const uint32_t *__restrict__ blk_hits, const uint32_t *__restrict__ hdir, const DevTerm *__restrict__ terms,
+                                                       const uint32_t *__restrict__ blk_hits, const uint32_t *__restrict__ hdir, const uint32_t *__restrict__ pdir,
+                                                       const DevTerm *__restrict__ terms,
                                                        const uint32_t *__restrict__ pair_term, const uint32_t npairs, const uint32_t *__restrict__ freqs, const uint32_t *__restrict__ at_block,
                                                        const uint32_t *__restrict__ at_slot, const uint32_t *__restrict__ at_before, const uint64_t *__restrict__ hit_off,
                                                        uint16_t *__restrict__ pos_out, uint8_t *__restrict__ plen_out, uint64_t *__restrict__ payload_out) {
@@ -377,6 +381,9 @@ __global__ __launch_bounds__(256) void k_hits_at_write(const uint8_t *__restrict
                 for (uint32_t k = 0; k < slot; ++k)
                         dh_skip_doc(hs, fs.next());
                 dh_walk_doc(hs, f, dst, out);
-        } else
+        } else {
                 dh_plain_doc<CODEC>(ctx, t.pad, hits_at + at_before[i], f, dst, out);
+                if (out.plen && (t.flags & TERM_HIT_PAYLOADS)) // (over the zeros dh_plain_doc stored: the same lane, in program order)
+                        lpay_fill(hits, hdir, t.pad, pdir, pdir[pair_term[i]], hits_at + at_before[i], f, out.plen + dst, out.payload + dst);
+        }
 }

@@ -1,7 +1,7 @@
 // k_rich.hpp — the default ("rich match") execution mode: per match, the query terms that matched it and their hits
 // Part of libtrinity_hip.so (MI355X / gfx950); included by trinity_hip.hip.  New code, no reference source.
 #pragma once
-#include "k_phrase.hpp"
+#include "lucene_pay_stream.hpp"
 
 // exec_query without DocumentsOnly / AccumulatedScoreScheme hands every match to consider(const matched_document &) with
 // matchedTerms[] = the query's postings iterators that sit on the document (collect_doc_matching_terms,
@@ -52,8 +52,8 @@ static_assert(sizeof(RichShared) == 33848, "k_rich's LDS: cand / mptr / blkof li
 // the kernels' body (k_rich: WIDE = false, wd unused; k_rich_wide: WIDE = true) — every thread of the workgroup calls it
 template <int CODEC, bool WRITE, bool WIDE>
 __device__ __forceinline__ void rich_tasks(const uint8_t *__restrict__ index, const uint8_t *__restrict__ hits, const uint32_t *__restrict__ blk_hits,
-                                           const uint32_t *__restrict__ hdir, const uint32_t *__restrict__ blk_last, const uint32_t *__restrict__ blk_off,
-                                           const DevTerm *__restrict__ terms, const DevQuery *__restrict__ plan, const DevTask *__restrict__ tasks,
+                                           const uint32_t *__restrict__ hdir, const uint32_t *__restrict__ pdir, const uint32_t *__restrict__ blk_last,
+                                           const uint32_t *__restrict__ blk_off, const DevTerm *__restrict__ terms, const DevQuery *__restrict__ plan, const DevTask *__restrict__ tasks,
                                            const uint32_t *__restrict__ sched, const uint32_t *__restrict__ rterms, const uint32_t ntasks,
                                            uint32_t *__restrict__ ticket, const uint32_t *__restrict__ out, const uint32_t *__restrict__ counts, const uint32_t R,
                                            uint32_t *__restrict__ present, uint16_t *__restrict__ freq, uint32_t *__restrict__ task_hits,
@@ -61,7 +61,8 @@ __device__ __forceinline__ void rich_tasks(const uint8_t *__restrict__ index, co
                                            uint8_t *__restrict__ pool_plen, uint64_t *__restrict__ pool_payload, const RichWideArgs &wd) {
         // pool_plen / pool_payload (or null; TRI_FLAG_HIT_PAYLOADS): per hit, parallel to `pool`, term_hit::payloadLen and ::payload as
         // Google::Decoder::materialize_hits leaves them (google_codec.cpp:533-594) — the payload word is carried from hit to hit within a
-        // document and only its first payloadLen bytes are rewritten, exactly as the reference's local variable is
+        // document and only its first payloadLen bytes are rewritten, exactly as the reference's local variable is.  LUCENE (lucene_codec.cpp:767-856): the word is
+        // cleared for every hit and its payloadLen bytes copied — read through LPayStream from the hit's ordinal, for the terms flagged TERM_HIT_PAYLOADS
         // allow (or null): per match, the reportable terms an iterator of the query tree sits on — general trees, where holding a term
         // is not enough (the matching kernel left the mask; every other query's matches carry all ones)
         __shared__ RichShared sh;
@@ -273,14 +274,17 @@ __device__ __forceinline__ void rich_tasks(const uint8_t *__restrict__ index, co
                                                                 HitStream<CODEC> hs;
                                                                 hs.init(ctx, t.pad, h0);
                                                                 uint32_t pos = 0;
+                                                                const bool carries = pool_payload && (t.flags & TERM_HIT_PAYLOADS); // (the flag is the term's: the same for every lane)
                                                                 for (uint32_t h = 0; h < (f & 0xffffu); ++h) {
                                                                         pos = (pos + hs.next()) & 0xffffu;
                                                                         d[h] = (uint16_t)pos;
-                                                                        if (pool_payload) { // (the Lucene-shaped segments of this repo carry no payloads)
+                                                                        if (pool_payload && !carries) { // (no hit of the term carries a payload)
                                                                                 pool_plen[(uint64_t)(d + h - pool)] = 0;
                                                                                 pool_payload[(uint64_t)(d + h - pool)] = 0;
                                                                         }
                                                                 }
+                                                                if (carries)
+                                                                        lpay_fill(hits, hdir, t.pad, pdir, pdir[term], h0, f & 0xffffu, pool_plen + (d - pool), pool_payload + (d - pool));
                                                         }
                                                         h0 += f;
                                                 }
@@ -354,12 +358,12 @@ __device__ __forceinline__ void rich_tasks(const uint8_t *__restrict__ index, co
 
 #define RICH_PARAMS                                                                                                                                                                         \
         const uint8_t *__restrict__ index, const uint8_t *__restrict__ hits, const uint32_t *__restrict__ blk_hits, const uint32_t *__restrict__ hdir,                                    \
-                const uint32_t *__restrict__ blk_last, const uint32_t *__restrict__ blk_off, const DevTerm *__restrict__ terms, const DevQuery *__restrict__ plan,                        \
+                const uint32_t *__restrict__ pdir, const uint32_t *__restrict__ blk_last, const uint32_t *__restrict__ blk_off, const DevTerm *__restrict__ terms, const DevQuery *__restrict__ plan,                        \
                 const DevTask *__restrict__ tasks, const uint32_t *__restrict__ sched, const uint32_t *__restrict__ rterms, const uint32_t ntasks, uint32_t *__restrict__ ticket,         \
                 const uint32_t *__restrict__ out, const uint32_t *__restrict__ counts, const uint32_t R, uint32_t *__restrict__ present, uint16_t *__restrict__ freq,                     \
                 uint32_t *__restrict__ task_hits, const uint64_t *__restrict__ task_pos_base, uint16_t *__restrict__ pool, const uint32_t *__restrict__ allow,                            \
                 uint8_t *__restrict__ pool_plen, uint64_t *__restrict__ pool_payload
-#define RICH_PASS index, hits, blk_hits, hdir, blk_last, blk_off, terms, plan, tasks, sched, rterms, ntasks, ticket, out, counts, R, present, freq, task_hits, task_pos_base, pool, allow, pool_plen, pool_payload
+#define RICH_PASS index, hits, blk_hits, hdir, pdir, blk_last, blk_off, terms, plan, tasks, sched, rterms, ntasks, ticket, out, counts, R, present, freq, task_hits, task_pos_base, pool, allow, pool_plen, pool_payload
 // every task of a batch without wide-report queries; of one with them: every task but theirs (the first part of BatchPlan::rich_sched)
 template <int CODEC, bool WRITE>
 __global__ __launch_bounds__(AND_WG) void k_rich(RICH_PARAMS) {

@@ -9,7 +9,11 @@
 //   hit block k of a term = its hits [128 k, 128 k + 128) in posting order            -> one group of position deltas (a document's first hit: from 0)
 //   skiplist entry j      = {bytes of the blocks before j (+ 14), document before block j, where hit block floor(h / 128) starts, 128 j,
 //                            128 floor(h / 128), h mod 128} with h = the term's hits before block j's first document
-// so sizes are computed per unit, prefix sums place the units, and every unit writes its own bytes.  Payload-less hits (what the host encoder writes).
+// so sizes are computed per unit, prefix sums place the units, and every unit writes its own bytes.
+// Hit payloads (lucene_codec.cpp:240-304, 342-366) ride in the same units: a full hit block is `ints(deltas) ints(lengths) varbyte(bytes) the bytes`, the tail
+// is per hit `varbyte(delta << 1 | length differs from the tail's previous hit) [u8 length]` and then the tail's payload bytes.  Both are functions of the hit
+// block's own 128 hits (of the tail's own hits), so the sizes stay per unit and the skiplist's hit-block offsets and the header's chunk size come out of the
+// same prefix sums.  plens == nullptr: no hit has a payload — ints(128 zeros) = {0, 0}, varbyte(0): the three bytes of LENC_HIT_TRAILER, and a flag-less tail.
 // New code, no reference source.
 #pragma once
 #include "pfor128_group.hpp"
@@ -28,6 +32,8 @@ struct LencArgs {
         const uint64_t *dblk_first;    // [nterms + 1]: full document blocks before every term
         const uint64_t *hblk_first;    // [nterms + 1]: full hit blocks before every term
         uint64_t nterms;
+        const uint8_t *plens;          // [nhits]: a hit's payload length, 0 .. 8 (nullptr: no hit has a payload)
+        const uint64_t *payloads;      // [nhits]: its payload, the low plens[h] bytes
 };
 
 // the term that owns global block g (first[] ascends; first[t] <= g < first[t + 1])
@@ -65,6 +71,18 @@ struct LencAt {
         TRI_HD uint32_t operator()(const uint32_t i) const { return v[at + i]; }
 };
 
+struct LencLen {
+        const uint8_t *v;
+        uint64_t at;
+        TRI_HD uint32_t operator()(const uint32_t i) const { return v[at + i]; }
+};
+// the low `len` bytes of a payload word, in memory order
+TRI_HD inline uint8_t *lenc_put_payload(uint8_t *o, const uint64_t word, const uint32_t len) {
+        for (uint32_t i = 0; i < len; ++i)
+                *o++ = (uint8_t)(word >> (8 * i));
+        return o;
+}
+
 // ---- unit B, per full document block g: its bytes
 TRI_HD inline uint32_t lenc_unit_dblk_size(const LencArgs &a, const uint64_t g) {
         const uint64_t t = lenc_term_of(a.dblk_first, a.nterms, g), p0 = a.term_first[t] + LENC_BLOCK * (g - a.dblk_first[t]);
@@ -73,17 +91,29 @@ TRI_HD inline uint32_t lenc_unit_dblk_size(const LencArgs &a, const uint64_t g) 
 // ---- unit C, per full hit block h: its bytes
 TRI_HD inline uint32_t lenc_unit_hblk_size(const LencArgs &a, const uint64_t h) {
         const uint64_t t = lenc_term_of(a.hblk_first, a.nterms, h), h0 = a.hit_off[a.term_first[t]] + LENC_BLOCK * (h - a.hblk_first[t]);
-        return pfor128_plan(LencAt{a.hdelta, h0}).bytes + LENC_HIT_TRAILER;
+        const uint32_t deltas = pfor128_plan(LencAt{a.hdelta, h0}).bytes;
+        if (!a.plens)
+                return deltas + LENC_HIT_TRAILER;
+        uint32_t sum = 0;
+        for (uint32_t i = 0; i < LENC_BLOCK; ++i)
+                sum += a.plens[h0 + i];
+        return deltas + pfor128_plan(LencLen{a.plens, h0}).bytes + pf_vlen(sum) + sum;
 }
-// ---- unit D, per term: the bytes of its varbyte tails (documents that fill no block: (delta, frequency) pairs; hits that fill no block: delta << 1)
+// ---- unit D, per term: the bytes of its varbyte tails (documents that fill no block: (delta, frequency) pairs; hits that fill no block: delta << 1 | flag, a
+//      length byte where the flag is set — the length differs from the tail's previous hit's, 0 before the first, whatever document the hits belong to —, and
+//      the tail's payload bytes)
 TRI_HD inline void lenc_unit_tail_size(const LencArgs &a, const uint64_t t, uint32_t *tail_docs, uint32_t *tail_hits) {
         const uint64_t p_lo = a.term_first[t], p_hi = a.term_first[t + 1], p_tail = p_lo + (p_hi - p_lo) / LENC_BLOCK * LENC_BLOCK;
         uint32_t bd = 0, bh = 0;
         for (uint64_t p = p_tail; p < p_hi; ++p)
                 bd += pf_vlen(a.docs[p] - (p == p_lo ? 0u : a.docs[p - 1])) + pf_vlen(a.freqs[p]);
         const uint64_t h_lo = a.hit_off[p_lo], h_hi = a.hit_off[p_hi], h_tail = h_lo + (h_hi - h_lo) / LENC_BLOCK * LENC_BLOCK;
-        for (uint64_t h = h_tail; h < h_hi; ++h)
-                bh += pf_vlen(a.hdelta[h] << 1);
+        uint32_t last_len = 0;
+        for (uint64_t h = h_tail; h < h_hi; ++h) {
+                const uint32_t len = a.plens ? a.plens[h] : 0u, flag = len != last_len;
+                bh += pf_vlen(a.hdelta[h] << 1 | flag) + flag + len;
+                last_len = len;
+        }
         *tail_docs = bd;
         *tail_hits = bh;
 }
@@ -136,7 +166,18 @@ TRI_HD inline void lenc_unit_hblk_write(const LencArgs &a, const LencPlace &pl, 
         uint8_t *o = hits_out + pl.hterm_off[t] + (pl.hoff[h] - pl.hoff[a.hblk_first[t]]);
         const LencAt gh{a.hdelta, h0};
         o = pfor128_emit(gh, pfor128_plan(gh), o);
-        o[0] = 0, o[1] = 0, o[2] = 0; // ints(128 payload lengths, all zero) = {0, varbyte 0}; varbyte(0 payload bytes)
+        if (!a.plens) {
+                o[0] = 0, o[1] = 0, o[2] = 0; // ints(128 payload lengths, all zero) = {0, varbyte 0}; varbyte(0 payload bytes)
+                return;
+        }
+        const LencLen gl{a.plens, h0};
+        o = pfor128_emit(gl, pfor128_plan(gl), o);
+        uint32_t sum = 0;
+        for (uint32_t i = 0; i < LENC_BLOCK; ++i)
+                sum += a.plens[h0 + i];
+        o = pf_put_varbyte(o, sum);
+        for (uint32_t i = 0; i < LENC_BLOCK; ++i)
+                o = lenc_put_payload(o, a.payloads[h0 + i], a.plens[h0 + i]);
 }
 // ---- unit G, per term: the header and the two tails
 TRI_HD inline void lenc_unit_term_write(const LencArgs &a, const LencPlace &pl, const uint64_t t, uint8_t *index_out, uint8_t *hits_out) {
@@ -154,6 +195,16 @@ TRI_HD inline void lenc_unit_term_write(const LencArgs &a, const LencPlace &pl, 
                 o = pf_put_varbyte(o, a.freqs[p]);
         }
         uint8_t *ho = hits_out + pl.hterm_off[t] + (pl.hoff[a.hblk_first[t + 1]] - pl.hoff[a.hblk_first[t]]);
-        for (uint64_t h = h_lo + (h_hi - h_lo) / LENC_BLOCK * LENC_BLOCK; h < h_hi; ++h)
-                ho = pf_put_varbyte(ho, a.hdelta[h] << 1);
+        const uint64_t h_tail = h_lo + (h_hi - h_lo) / LENC_BLOCK * LENC_BLOCK;
+        uint32_t last_len = 0;
+        for (uint64_t h = h_tail; h < h_hi; ++h) {
+                const uint32_t len = a.plens ? a.plens[h] : 0u, flag = len != last_len;
+                ho = pf_put_varbyte(ho, a.hdelta[h] << 1 | flag);
+                if (flag)
+                        *ho++ = (uint8_t)len;
+                last_len = len;
+        }
+        if (a.plens)
+                for (uint64_t h = h_tail; h < h_hi; ++h)
+                        ho = lenc_put_payload(ho, a.payloads[h], a.plens[h]);
 }

@@ -298,6 +298,8 @@ struct tri_index : HostIndex {
         DevMem<uint8_t> d_index, d_hits;
         DevMem<uint32_t> d_blk_last, d_blk_off, d_win;
         DevMem<uint32_t> d_blk_hits, d_hdir; // where a directory row's hits start — LUCENE + hits.data: hit ordinal within the term
+        DevMem<uint32_t> d_pdir;             // LUCENE + hits.data: [term] = the term's payload directory row in this same array (~0: no hit of it carries a payload), then the rows
+        bool any_hit_payloads = false;       // ... and whether any term has one
                                                            // (+ hdir: the 128-hit blocks of hits.data); GOOGLE: byte offset into index[]
         // GOOGLE: the document deltas of every block re-laid out as one contiguous stream per term ([n][n-1 prefix varints] per
         // block, bytes exactly as in the chunk) with its own offset column.  In the chunk a block's deltas are followed by its
@@ -677,6 +679,16 @@ extern "C" int tri_index_upload(tri_dev *dev, const uint8_t *index, size_t len, 
                 HIP_TRY(hipMemcpy(ix->d_hits, hits, hits_len, hipMemcpyHostToDevice));
                 if (ix->has_hdir && ((rc = dev_upload(ix->d_blk_hits, ix->blk_hits)) || (rc = dev_upload(ix->d_hdir, ix->hdir))))
                         return rc;
+                if (ix->has_hdir) { // the payload directory (index_host.hpp), built on the image the device gets: the terms' rows made offsets into ONE array
+                        std::vector<uint32_t> pd(ix->pdir_off);
+                        for (uint32_t &o : pd)
+                                if (o != 0xffffffffu)
+                                        o += (uint32_t)nterms;
+                        ix->any_hit_payloads = !ix->pdir.empty();
+                        pd.insert(pd.end(), ix->pdir.begin(), ix->pdir.end());
+                        if ((rc = dev_upload(ix->d_pdir, pd)))
+                                return rc;
+                }
         }
         if (codec == TRI_CODEC_GOOGLE && (rc = dev_upload(ix->d_blk_hits, ix->blk_hits)))
                 return rc;
@@ -865,6 +877,25 @@ extern "C" int tri_decode_hits(tri_index *ix, const uint32_t *terms, size_t n, u
         TRI_LAUNCH(k_decode_hits, ix->codec, dim3(gx, gy), dim3(256), dev->stream, (const uint8_t *)ix->d_index, (const uint8_t *)ix->d_hits, (const uint32_t *)ix->d_blk_off,
                    (const uint32_t *)ix->d_blk_hits, (const uint32_t *)ix->d_hdir, (const DevTerm *)ix->d_terms, (const HitsJob *)d_jobs, nj,
                    (const uint64_t *)d_cnt, d_pos, d_len, d_pay);
+        // LUCENE: the payloads of the terms that carry some, over the zeros k_decode_hits stored (the same stream: behind it) — a wave per 128-hit block
+        DevMem<LPayJob> d_pjobs;
+        if (!google && payload_lens && ix->any_hit_payloads) {
+                std::vector<LPayJob> pjobs;
+                uint32_t maxunits = 0;
+                for (size_t i = 0; i < n; ++i)
+                        if ((ix->terms[terms[i]].flags & TERM_HIT_PAYLOADS) && totals[i]) {
+                                pjobs.push_back({terms[i], (uint32_t)totals[i], offs[i]});
+                                maxunits = std::max(maxunits, (uint32_t)((totals[i] + 127) / 128));
+                        }
+                if (!pjobs.empty()) {
+                        HIP_TRY(d_pjobs.alloc(pjobs.size() * sizeof(LPayJob)));
+                        HIP_TRY(hipMemcpyAsync(d_pjobs, pjobs.data(), pjobs.size() * sizeof(LPayJob), hipMemcpyHostToDevice, dev->stream));
+                        const dim3 pgrid(std::min<uint32_t>((maxunits + 3) / 4, 4096), std::min<uint32_t>((uint32_t)pjobs.size(), 32768));
+                        hipLaunchKernelGGL(k_decode_hit_payloads, pgrid, dim3(256), 0, dev->stream, (const uint8_t *)ix->d_hits, (const uint32_t *)ix->d_hdir, (const uint32_t *)ix->d_pdir,
+                                           (const DevTerm *)ix->d_terms, (const LPayJob *)d_pjobs, (uint32_t)pjobs.size(), (uint8_t *)d_len, (uint64_t *)d_pay);
+                        HIP_TRY(hipStreamSynchronize(dev->stream)); // (pjobs is pageable host memory the copy above reads)
+                }
+        }
         return decode_hits_fetch(dev, tot, d_pos, d_len, d_pay, positions, payload_lens, payloads);
 }
 
@@ -919,7 +950,7 @@ extern "C" int tri_decode_hits_at(tri_index *ix, const uint32_t *terms, const ui
                 HIP_TRY(d_pay.alloc(tot * 8 + 64));
         }
         TRI_LAUNCH(k_hits_at_write, ix->codec, grid, dim3(256), dev->stream, (const uint8_t *)ix->d_index, (const uint8_t *)ix->d_hits, (const uint32_t *)ix->d_blk_off,
-                   (const uint32_t *)ix->d_blk_hits, (const uint32_t *)ix->d_hdir, (const DevTerm *)ix->d_terms, (const uint32_t *)d_terms, np,
+                   (const uint32_t *)ix->d_blk_hits, (const uint32_t *)ix->d_hdir, (const uint32_t *)ix->d_pdir, (const DevTerm *)ix->d_terms, (const uint32_t *)d_terms, np,
                    (const uint32_t *)d_freqs, (const uint32_t *)at_block, (const uint32_t *)at_slot, (const uint32_t *)at_before, (const uint64_t *)d_off,
                    d_pos, d_len, d_pay);
         return decode_hits_fetch(dev, tot, d_pos, d_len, d_pay, positions, payload_lens, payloads);
@@ -1682,7 +1713,7 @@ static int launch_rich(tri_batch *b) {
         const uint32_t *sched = n_wide ? b->dev_at(b->rich_sched) : b->dev_at(b->sched);
         const RichWideArgs wd{b->d_rich_present_hi, b->d_rich_allow_hi, b->d_rich_freq_wide, b->dev_opt(b->rich_wide)};
 #define RICH_ARGS(SCHED, N, TICKET)                                                                                                                                                        \
-        ix->d_index, ix->d_hits, ix->d_blk_hits, ix->d_hdir, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), SCHED, b->dev_at(b->sterms), N,         \
+        ix->d_index, ix->d_hits, ix->d_blk_hits, ix->d_hdir, ix->d_pdir, ix->d_blk_last, ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), SCHED, b->dev_at(b->sterms), N,         \
                 b->d_ticket + (WRITE ? TICKET_RICH_WRITE_WORD : TICKET_RICH_COUNT_WORD) + TICKET, b->d_out, b->d_counts, b->rich_R, b->d_rich_present, b->d_rich_freq, b->d_task_hits,     \
                 WRITE ? (const uint64_t *)b->d_task_pos_base : nullptr, WRITE ? (uint16_t *)b->d_rich_pool : nullptr, (const uint32_t *)b->d_rich_allow, WRITE ? (uint8_t *)b->d_rich_plen : nullptr,             \
                 WRITE ? (uint64_t *)b->d_rich_payload : nullptr

@@ -1,5 +1,5 @@
 // write_side.hpp — the write side on the device: the codecs' encoders, SegmentIndexSession::commit and the codecs' merge — tri_encode_google[_payloads],
-// tri_encode_lucene, tri_commit_google / _lucene, tri_merge_google / _lucene.  Host code only: the kernels are k_encode.hpp, k_lencode.hpp (lucene_enc_units.hpp),
+// tri_encode_lucene[_payloads], tri_commit_google / _lucene[_payloads], tri_merge_google / _lucene.  Host code only: the kernels are k_encode.hpp, k_lencode.hpp (lucene_enc_units.hpp),
 // k_commit.hpp and commit_sort.hip.  Part of libtrinity_hip.so (MI355X / gfx950); included by trinity_hip.hip after the kernels.  New code, no reference source.
 //
 // Every public call creates ONE WriteScratch and passes it down; every device buffer of the call comes from it and goes back to the device handle's pool when
@@ -39,7 +39,7 @@ struct WriteScratch {
 struct EncIn {
         const uint32_t *docs = nullptr, *freqs = nullptr;
         const uint16_t *pos = nullptr;
-        const uint8_t *plens = nullptr;     // (Google codec; nullptr: no hit has a payload)
+        const uint8_t *plens = nullptr;     // (nullptr: no hit has a payload)
         const uint64_t *payloads = nullptr;
         uint64_t np = 0, nhits = 0;
 };
@@ -163,7 +163,7 @@ int encode_google_device(WriteScratch &s, const EncIn &in, const uint64_t *term_
         return TRI_OK;
 }
 
-// ---- Codecs::Lucene::Encoder (lucene_codec.cpp:163-388) on the device, PFOR128 payload, payload-less hits (k_lencode.hpp, lucene_enc_units.hpp)
+// ---- Codecs::Lucene::Encoder (lucene_codec.cpp:163-388) on the device, PFOR128 payload (k_lencode.hpp, lucene_enc_units.hpp)
 int encode_lucene_device(WriteScratch &s, const EncIn &in, const uint64_t *term_first, const size_t nterms, const EncOut &out) {
         const hipStream_t stream = s.dev->stream;
         const uint64_t np = in.np;
@@ -187,7 +187,7 @@ int encode_lucene_device(WriteScratch &s, const EncIn &in, const uint64_t *term_
         if ((rcs = enc_scan(s, in.freqs, d_hit_off, np)))
                 return rcs;
         const dim3 block(256);
-        LencArgs a{in.docs, in.freqs, in.pos, d_hit_off, d_term_first, d_hdelta, d_dblk_first, d_hblk_first, (uint64_t)nterms};
+        LencArgs a{in.docs, in.freqs, in.pos, d_hit_off, d_term_first, d_hdelta, d_dblk_first, d_hblk_first, (uint64_t)nterms, in.plens, in.payloads};
         hipLaunchKernelGGL(k_lenc_hdelta, grid_for(np), block, 0, stream, a, d_hdelta, np);
         hipLaunchKernelGGL(k_lenc_term_counts, grid_for(nterms), block, 0, stream, d_term_first, d_hit_off, (uint64_t)nterms, d_dcnt, d_hcnt);
         if ((rcs = enc_scan(s, d_dcnt, d_dblk_first, nterms)) || (rcs = enc_scan(s, d_hcnt, d_hblk_first, nterms)))
@@ -246,7 +246,7 @@ int encode_device(const int codec, WriteScratch &s, const EncIn &in, const uint6
 }
 
 // ---- the encode entry points' host side: what the reference's encoders would refuse — term_first ascending; within a term, documents > 0 and strictly
-//      ascending; freqs[] within positions[]; a payload of at most 8 bytes (payload_lens: Google codec only); within a document, positions non-descending
+//      ascending; freqs[] within positions[]; a payload of at most 8 bytes (google_codec.cpp:46, lucene_codec.cpp:262); within a document, positions non-descending
 //      (google_codec.cpp:49: the encoder writes pos - lastPos) and > 0 for a hit without payload (new_hit drops such a hit, google_codec.cpp:42-45, as does
 //      lucene_encoder.hpp: refused here rather than dropped silently; a position-0 hit WITH a payload is a counted hit).  *nhits: the hits in all.
 int validate_postings(const char *fn, const uint32_t *docs, const uint32_t *freqs, const uint16_t *positions, const uint8_t *payload_lens, const size_t npositions,
@@ -269,7 +269,7 @@ int validate_postings(const char *fn, const uint32_t *docs, const uint32_t *freq
                         for (uint64_t h = nhits; h < nhits + freqs[p]; ++h) {
                                 const uint32_t plen = payload_lens ? payload_lens[h] : 0u;
                                 if (plen > 8)
-                                        return fail(TRI_ERR_INVALID, "term %zu, document %u: a payload of %u bytes (at most 8: google_codec.cpp:46)", t, docs[p], plen);
+                                        return fail(TRI_ERR_INVALID, "term %zu, document %u: a payload of %u bytes (at most 8: google_codec.cpp:46, lucene_codec.cpp:262)", t, docs[p], plen);
                                 if ((!positions[h] && !plen) || positions[h] < last_pos)
                                         return fail(TRI_ERR_INVALID, "term %zu, document %u: positions must be non-descending within a document, and > 0 for a hit without payload (google_codec.cpp:42-49)", t, docs[p]);
                                 last_pos = positions[h];
@@ -342,12 +342,18 @@ extern "C" int tri_encode_google_payloads(tri_dev *dev, const uint32_t *docs, co
 }
 extern "C" int tri_encode_lucene(tri_dev *dev, const uint32_t *docs, const uint32_t *freqs, const uint16_t *positions, size_t npositions, const uint64_t *term_first, size_t nterms,
                                  uint8_t *index_out, size_t index_cap, size_t *index_len, uint8_t *hits_out, size_t hits_cap, size_t *hits_len, tri_term *terms_out) {
-        return encode_postings("tri_encode_lucene", TRI_CODEC_LUCENE, dev, docs, freqs, positions, nullptr, nullptr, npositions, term_first, nterms,
+        return tri_encode_lucene_payloads(dev, docs, freqs, positions, nullptr, nullptr, npositions, term_first, nterms, index_out, index_cap, index_len, hits_out, hits_cap, hits_len,
+                                          terms_out);
+}
+extern "C" int tri_encode_lucene_payloads(tri_dev *dev, const uint32_t *docs, const uint32_t *freqs, const uint16_t *positions, const uint8_t *payload_lens, const uint64_t *payloads,
+                                          size_t npositions, const uint64_t *term_first, size_t nterms, uint8_t *index_out, size_t index_cap, size_t *index_len, uint8_t *hits_out,
+                                          size_t hits_cap, size_t *hits_len, tri_term *terms_out) {
+        return encode_postings("tri_encode_lucene", TRI_CODEC_LUCENE, dev, docs, freqs, positions, payload_lens, payloads, npositions, term_first, nterms,
                                EncOut{index_out, index_cap, index_len, hits_out, hits_cap, hits_len, terms_out});
 }
 
 // ---- SegmentIndexSession::commit (indexer.cpp:311-478) on the device: sort, gather, encode (k_commit.hpp, commit_sort.hip, the codec's encoder)
-// (codec: TRI_CODEC_GOOGLE — index_out only —, or TRI_CODEC_LUCENE — index_out + hits_out, payload-less hits)
+// (codec: TRI_CODEC_GOOGLE — index_out only —, or TRI_CODEC_LUCENE — index_out + hits_out)
 static int commit_device(tri_dev *dev, const int codec, const uint32_t *term_ids, const uint32_t *doc_ids, const uint32_t *freqs, const uint16_t *positions, const uint8_t *payload_lens,
                          const uint64_t *payloads, size_t npostings, size_t npositions, uint8_t *index_out, size_t cap, size_t *index_len, uint8_t *hits_out, size_t hits_cap,
                          size_t *hits_len, uint32_t *term_ids_out, tri_term *terms_out, size_t terms_cap, size_t *nterms, tri_commit_stats *stats) {
@@ -425,7 +431,7 @@ static int commit_device(tri_dev *dev, const int codec, const uint32_t *term_ids
         if (err != ~0ull) {
                 static const char *const why[] = {"", "document 0", "the same (term, document) twice (indexer.cpp:446: documentID > prevDID)",
                                                   "positions must be non-descending within a document, and > 0 for a hit without payload (google_codec.cpp:42-49)",
-                                                  "a payload of more than 8 bytes (google_codec.cpp:46)"};
+                                                  "a payload of more than 8 bytes (google_codec.cpp:46, lucene_codec.cpp:262)"};
                 return fail(TRI_ERR_INVALID, "%s: sorted posting %llu: %s", fn, (unsigned long long)(err >> 8) - 1, why[std::min<unsigned long long>(err & 0xff, 4)]);
         }
         *nterms = (size_t)nt;
@@ -467,11 +473,17 @@ extern "C" int tri_commit_google(tri_dev *dev, const uint32_t *term_ids, const u
 extern "C" int tri_commit_lucene(tri_dev *dev, const uint32_t *term_ids, const uint32_t *doc_ids, const uint32_t *freqs, const uint16_t *positions, size_t npostings, size_t npositions,
                                  uint8_t *index_out, size_t cap, size_t *index_len, uint8_t *hits_out, size_t hits_cap, size_t *hits_len, uint32_t *term_ids_out, tri_term *terms_out,
                                  size_t terms_cap, size_t *nterms, tri_commit_stats *stats) {
+        return tri_commit_lucene_payloads(dev, term_ids, doc_ids, freqs, positions, nullptr, nullptr, npostings, npositions, index_out, cap, index_len, hits_out, hits_cap, hits_len,
+                                          term_ids_out, terms_out, terms_cap, nterms, stats);
+}
+extern "C" int tri_commit_lucene_payloads(tri_dev *dev, const uint32_t *term_ids, const uint32_t *doc_ids, const uint32_t *freqs, const uint16_t *positions, const uint8_t *payload_lens,
+                                          const uint64_t *payloads, size_t npostings, size_t npositions, uint8_t *index_out, size_t cap, size_t *index_len, uint8_t *hits_out,
+                                          size_t hits_cap, size_t *hits_len, uint32_t *term_ids_out, tri_term *terms_out, size_t terms_cap, size_t *nterms, tri_commit_stats *stats) {
         if (!hits_len)
                 return fail(TRI_ERR_INVALID, "tri_commit_lucene: null argument");
         *hits_len = 0;
-        return commit_device(dev, TRI_CODEC_LUCENE, term_ids, doc_ids, freqs, positions, nullptr, nullptr, npostings, npositions, index_out, cap, index_len, hits_out, hits_cap, hits_len,
-                             term_ids_out, terms_out, terms_cap, nterms, stats);
+        return commit_device(dev, TRI_CODEC_LUCENE, term_ids, doc_ids, freqs, positions, payload_lens, payloads, npostings, npositions, index_out, cap, index_len, hits_out, hits_cap,
+                             hits_len, term_ids_out, terms_out, terms_cap, nterms, stats);
 }
 
 // ---- The codecs' merge for a whole dictionary, on the device (Codecs::Google::IndexSession::merge, google_codec.cpp:186-438; Codecs::Lucene::IndexSession::merge,
@@ -574,7 +586,7 @@ static int merge_device(tri_dev *dev, const int codec, tri_index *const *parts, 
                                 continue;
                         const tri_index *ix = parts[p];
                         if (codec == TRI_CODEC_LUCENE)
-                                hipLaunchKernelGGL(k_merge_hits_lucene, job_grid(dev, jobs[p].size()), dim3(256), 0, stream, ix->d_hits, ix->d_blk_hits, ix->d_hdir, ix->d_terms,
+                                hipLaunchKernelGGL(k_merge_hits_lucene, job_grid(dev, jobs[p].size()), dim3(256), 0, stream, ix->d_hits, ix->d_blk_hits, ix->d_hdir, ix->d_pdir, ix->d_terms,
                                                    d_jobs[p], (uint32_t)jobs[p].size(), d_freqs_all, d_hit_off_all, d_pos_all, d_plens_all, d_payloads_all);
                         else
                                 hipLaunchKernelGGL(k_merge_hits, job_grid(dev, jobs[p].size()), dim3(256), 0, stream, ix->d_index, ix->d_blk_off, ix->d_blk_hits, ix->d_terms,

@@ -144,7 +144,7 @@ ABI_SYMBOLS = [
     "tri_index_upload", "tri_index_destroy", "tri_index_get_info", "tri_index_term_docbytes", "tri_index_set_masked", "tri_decode_terms", "tri_decode_hits", "tri_decode_hits_at",
     "tri_batch_create", "tri_batch_query_status", "tri_batch_destroy", "tri_batch_run", "tri_batch_sync", "tri_batch_get_info",
     "tri_batch_match_counts", "tri_batch_docset", "tri_batch_docset_bitmap", "tri_batch_docsets", "tri_batch_docsets_mixed", "tri_batch_scores", "tri_batch_query_terms", "tri_batch_matched_terms", "tri_batch_query_terms_wide", "tri_batch_matched_terms_wide", "tri_batch_matched_payloads", "tri_batch_set_ranker", "tri_batch_ranked", "tri_batch_topk", "tri_batch_topk_device", "tri_batch_counts_device", "tri_batch_docset_hashes",
-    "tri_cbatch_create", "tri_cbatch_destroy", "tri_cbatch_query_status", "tri_cbatch_run", "tri_cbatch_sync", "tri_cbatch_match_counts", "tri_cbatch_topk", "tri_cbatch_docset", "tri_cbatch_ranked", "tri_cbatch_matched_terms", "tri_cbatch_matched_terms_wide", "tri_cbatch_matched_payloads", "tri_encode_google", "tri_encode_google_payloads", "tri_commit_google", "tri_commit_lucene", "tri_merge_google", "tri_merge_lucene", "tri_encode_lucene",
+    "tri_cbatch_create", "tri_cbatch_destroy", "tri_cbatch_query_status", "tri_cbatch_run", "tri_cbatch_sync", "tri_cbatch_match_counts", "tri_cbatch_topk", "tri_cbatch_docset", "tri_cbatch_ranked", "tri_cbatch_matched_terms", "tri_cbatch_matched_terms_wide", "tri_cbatch_matched_payloads", "tri_encode_google", "tri_encode_google_payloads", "tri_commit_google", "tri_commit_lucene", "tri_merge_google", "tri_merge_lucene", "tri_encode_lucene", "tri_encode_lucene_payloads", "tri_commit_lucene_payloads",
     "tri_comm_unique_id", "tri_comm_create", "tri_comm_create_custom", "tri_comm_destroy", "tri_gather_results",
     "tri_filter_create", "tri_filter_from_docset", "tri_filter_destroy", "tri_batch_set_filters",
     "tri_isect_run", "tri_isect_status", "tri_isect_results", "tri_isect_histogram", "tri_isect_get_info", "tri_isect_destroy",
@@ -221,6 +221,9 @@ def hip_lib():
     L.tri_encode_lucene.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
     L.tri_commit_lucene.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, C.c_size_t,
                                     C.POINTER(C.c_size_t), vp]
+    L.tri_encode_lucene_payloads.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
+    L.tri_commit_lucene_payloads.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp,
+                                             C.c_size_t, C.POINTER(C.c_size_t), vp]
     L.tri_merge_google.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp]
     L.tri_merge_lucene.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp]
     L.tri_commit_google.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp]
@@ -441,25 +444,34 @@ class Device:
         out, tids, terms = _size_then_fill(call, [ln], nt)
         return out, tids, terms, _commit_stats(stats)
 
-    def commit_lucene(self, term_ids, doc_ids, freqs, positions):
-        """tri_commit_lucene: a session's postings in insertion order -> (index bytes, hits.data bytes, committed termIDs, term table, stats)."""
+    def commit_lucene(self, term_ids, doc_ids, freqs, positions, payload_lens=None, payloads=None):
+        """tri_commit_lucene / tri_commit_lucene_payloads: a session's postings in insertion order -> (index bytes, hits.data bytes, committed termIDs, term table, stats).
+        payload_lens / payloads: per hit, its payload's length (0 .. 8) and bytes (u64, first byte low); None: the payload-less export."""
         t = np.ascontiguousarray(term_ids, dtype=np.uint32)
         d = np.ascontiguousarray(doc_ids, dtype=np.uint32)
         f = np.ascontiguousarray(freqs, dtype=np.uint32)
         p = np.ascontiguousarray(positions, dtype=np.uint16)
+        pl = None if payload_lens is None else np.ascontiguousarray(payload_lens, dtype=np.uint8)
+        pv = None if payloads is None else np.ascontiguousarray(payloads, dtype=np.uint64)
+        assert t.size == d.size == f.size and (pl is None or pl.size == p.size) and (pv is None or pv.size == p.size)
         il, hl, nt = C.c_size_t(), C.c_size_t(), C.c_size_t()
         stats = np.zeros(4, dtype=np.uint64)
         L = hip_lib()
 
         def call(io, ic, ho, hc, tids, terms, tcap):
-            return L.tri_commit_lucene(self.h, t.ctypes.data, d.ctypes.data, f.ctypes.data, p.ctypes.data, t.size, p.size, io, ic, C.byref(il), ho, hc, C.byref(hl), tids, terms, tcap,
-                                       C.byref(nt), stats.ctypes.data)  # fmt: skip
+            if pl is None and pv is None:
+                return L.tri_commit_lucene(self.h, t.ctypes.data, d.ctypes.data, f.ctypes.data, p.ctypes.data, t.size, p.size, io, ic, C.byref(il), ho, hc, C.byref(hl), tids, terms,
+                                           tcap, C.byref(nt), stats.ctypes.data)  # fmt: skip
+            return L.tri_commit_lucene_payloads(self.h, t.ctypes.data, d.ctypes.data, f.ctypes.data, p.ctypes.data, None if pl is None else pl.ctypes.data,
+                                                None if pv is None else pv.ctypes.data, t.size, p.size, io, ic, C.byref(il), ho, hc, C.byref(hl), tids, terms, tcap, C.byref(nt),
+                                                stats.ctypes.data)  # fmt: skip
 
         io, ho, tids, terms = _size_then_fill(call, [il, hl], nt)
         return io, ho, tids, terms, _commit_stats(stats)
 
-    def encode_lucene(self, docs, freqs, positions, term_first):
-        """The Lucene-shaped codec's encoder on the device (tri_encode_lucene, PFOR128 payload): -> (index bytes, hits.data bytes, term table u32[n, 3])."""
+    def encode_lucene(self, docs, freqs, positions, term_first, payload_lens=None, payloads=None):
+        """The Lucene-shaped codec's encoder on the device (tri_encode_lucene / tri_encode_lucene_payloads, PFOR128 payload): -> (index bytes, hits.data bytes, term table
+        u32[n, 3]).  payload_lens / payloads: per hit, its payload's length (0 .. 8) and bytes (u64, first byte low); None: the payload-less export."""
         d = np.ascontiguousarray(docs, dtype=np.uint32)
         f = np.ascontiguousarray(freqs, dtype=np.uint32)
         p = np.ascontiguousarray(positions, dtype=np.uint16)
@@ -468,7 +480,15 @@ class Device:
         terms = np.zeros((max(n, 1), 3), dtype=np.uint32)
         il, hl = C.c_size_t(), C.c_size_t()
         L = hip_lib()
-        call = lambda io, ic, ho, hc: L.tri_encode_lucene(self.h, d.ctypes.data, f.ctypes.data, p.ctypes.data, p.size, tf.ctypes.data, n, io, ic, C.byref(il), ho, hc, C.byref(hl), terms.ctypes.data)
+        if payload_lens is None and payloads is None:
+            call = lambda io, ic, ho, hc: L.tri_encode_lucene(self.h, d.ctypes.data, f.ctypes.data, p.ctypes.data, p.size, tf.ctypes.data, n, io, ic, C.byref(il), ho, hc, C.byref(hl), terms.ctypes.data)
+        else:
+            pl = None if payload_lens is None else np.ascontiguousarray(payload_lens, dtype=np.uint8)
+            pv = None if payloads is None else np.ascontiguousarray(payloads, dtype=np.uint64)
+            assert (pl is None or pl.size == p.size) and (pv is None or pv.size == p.size)
+            call = lambda io, ic, ho, hc: L.tri_encode_lucene_payloads(self.h, d.ctypes.data, f.ctypes.data, p.ctypes.data, None if pl is None else pl.ctypes.data,
+                                                                        None if pv is None else pv.ctypes.data, p.size, tf.ctypes.data, n, io, ic, C.byref(il), ho, hc, C.byref(hl),
+                                                                        terms.ctypes.data)  # fmt: skip
         io, ho = _size_then_fill(call, [il, hl])
         return io, ho, terms[:n]
 

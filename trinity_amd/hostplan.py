@@ -55,6 +55,8 @@ def _lib():
         L.tri_host_pfor128_group.restype = None
         for f in (L.tri_host_lucene_encode, L.tri_host_lucene_encode_units):
             f.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
+        for f in (L.tri_host_lucene_encode_payloads, L.tri_host_lucene_encode_units_payloads):
+            f.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
         L._plan_ready = True
     return L
 
@@ -85,6 +87,19 @@ class HostIndex:
         out = np.zeros(max(1, n), dtype=np.uint32)
         L.tri_host_index_hits_dir(self.h, term, out.ctypes.data, C.byref(nfull))
         return out[:n], nfull.value
+
+    def payload_dir(self, term):
+        """The term's payload directory (LUCENE with hits.data, index_host.hpp pdir[]): u32[nfull, 3] {length group offset, payload bytes offset, payload bytes
+        before quarters 1 | 2 << 10 | 3 << 20} and where the tail's payload bytes start — or None: no hit of the term carries a payload."""
+        L = _lib()
+        L.tri_host_index_payload_dir.restype = C.c_uint32
+        L.tri_host_index_payload_dir.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        n = L.tri_host_index_payload_dir(self.h, term, None, 0)
+        if not n:
+            return None
+        out = np.zeros(n, dtype=np.uint32)
+        L.tri_host_index_payload_dir(self.h, term, out.ctypes.data, n)
+        return out[:-1].reshape(-1, 3), int(out[-1])
 
     def close(self):
         if self.h:
@@ -241,20 +256,31 @@ def pfor128_group_pair(v):
     return a[: al.value] if al.value != 0xFFFFFFFF else None, b[: bl.value]
 
 
-def lucene_encode(docs, freqs, positions, term_first, units=False):
+def lucene_encode(docs, freqs, positions, term_first, units=False, payload_lens=None, payloads=None):
     """The Lucene-shaped encoder on the host: the sequential encoder (csrc/host/lucene_encoder.hpp), or — units=True — the device encoder's units
-    (csrc/lucene_enc_units.hpp) run in plain loops.  -> (index bytes, hits.data bytes, term table u32[n, 3])."""
+    (csrc/lucene_enc_units.hpp) run in plain loops.  payload_lens / payloads: per hit, parallel to positions, 0 .. 8 bytes and the word whose low bytes they
+    are (None: the payload-less exports).  -> (index bytes, hits.data bytes, term table u32[n, 3])."""
     d = np.ascontiguousarray(docs, dtype=np.uint32)
     f = np.ascontiguousarray(freqs, dtype=np.uint32)
     p = np.ascontiguousarray(positions, dtype=np.uint16)
     tf = np.ascontiguousarray(term_first, dtype=np.uint64)
     n = tf.size - 1
-    icap, hcap = 128 + 16 * n + 12 * d.size, 128 + 6 * p.size + 8 * n
+    icap, hcap = 128 + 16 * n + 12 * d.size, 128 + (6 if payload_lens is None else 16) * p.size + 8 * n
     io, ho, t3 = np.zeros(icap, dtype=np.uint8), np.zeros(hcap, dtype=np.uint8), np.zeros((max(n, 1), 3), dtype=np.uint32)
     il, hl = C.c_uint64(), C.c_uint64()
-    fn = _lib().tri_host_lucene_encode_units if units else _lib().tri_host_lucene_encode
-    if fn(d.ctypes.data, f.ctypes.data, p.ctypes.data, tf.ctypes.data, n, io.ctypes.data, icap, C.byref(il), ho.ctypes.data, hcap, C.byref(hl), t3.ctypes.data):
-        raise TrinityError("lucene_encode: buffer too small")
+    out = (tf.ctypes.data, n, io.ctypes.data, icap, C.byref(il), ho.ctypes.data, hcap, C.byref(hl), t3.ctypes.data)
+    if payload_lens is None:
+        fn = _lib().tri_host_lucene_encode_units if units else _lib().tri_host_lucene_encode
+        rc = fn(d.ctypes.data, f.ctypes.data, p.ctypes.data, *out)
+    else:
+        pl = np.ascontiguousarray(payload_lens, dtype=np.uint8)
+        pv = np.ascontiguousarray(payloads, dtype=np.uint64)
+        if pl.size != p.size or pv.size != p.size:
+            raise TrinityError("lucene_encode: payload_lens and payloads run parallel to positions")
+        fn = _lib().tri_host_lucene_encode_units_payloads if units else _lib().tri_host_lucene_encode_payloads
+        rc = fn(d.ctypes.data, f.ctypes.data, p.ctypes.data, pl.ctypes.data, pv.ctypes.data, *out)
+    if rc:
+        raise TrinityError("lucene_encode: buffer too small" if rc == -1 else "lucene_encode: the encoder refuses these postings (a payload of more than 8 bytes)")
     return io[: il.value], ho[: hl.value], t3[:n]
 
 
