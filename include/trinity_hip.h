@@ -41,7 +41,9 @@ extern "C" {
                                 within 9: tri_perc_create / _query_status / _set_enabled / _get_info / _destroy / _match, tri_perc_result_pairs / _doc_counts / _get_info / _destroy,
                                 options perc_max_bytes / perc_prune (the percolator: documents matched against a resident set of stored queries; no existing struct grew);
                                 within 9: tri_encode_lucene_payloads / tri_commit_lucene_payloads (the Lucene-shaped codec carries hit payloads: written, merged by
-                                tri_merge_lucene, read by tri_decode_hits[_at] and tri_batch_matched_payloads; no struct grew) */
+                                tri_merge_lucene, read by tri_decode_hits[_at] and tri_batch_matched_payloads; no struct grew);
+                                within 9: tri_column_create / tri_column_destroy / tri_batch_set_facets / tri_batch_facets / tri_cbatch_facets, read-only option facet_last_us
+                                (facet counts: per query a histogram of its docID set over per-document columns, counted on the device; no existing struct grew) */
 
 /* status codes */
 #define TRI_OK 0
@@ -286,6 +288,45 @@ int tri_filter_create(tri_index *, const uint32_t *docids, size_t n, int mode, t
 int tri_filter_from_docset(tri_batch *, size_t q, int mode, tri_filter **out);
 void tri_filter_destroy(tri_filter *);
 int tri_batch_set_filters(tri_batch *, tri_filter *const *filters, size_t nf, const uint32_t *filter_of_query /* [nq], 0xffffffff: none */);
+
+/* ---- facet counts ----------------------------------------------------------------------------------
+ * The third thing an application does in MatchedIndexDocumentsFilter::consider(id) / consider(ids, cnt) (exec.h:12-23: "just count or collect documents
+ * matching a query") besides collecting and ranking: COUNT the matches by a per-document attribute — category, brand, price band, tenant.  A column holds
+ * that attribute for every docID of a segment and stays resident in HBM; a batch that names columns (facets) counts, at the end of every run and on the
+ * device, each query's docID set into a row per facet: a few hundred bytes a query cross PCIe instead of the docID set.
+ *
+ * tri_column_create: values[d] is the attribute of docID d; n must equal the index's docs_cnt + 1 (values[0] is never read), and the index may hold no docID
+ * above docs_cnt.  The values are copied to HBM; the call returns once the column stands.  A column belongs to its index, is destroyed before it, and is kept
+ * alive while a batch that names it may run — the filters' rules.
+ * tri_batch_set_facets: after tri_batch_create, before a run, again between runs; n == 0 clears; columns are stored by reference.  Runs already queued keep the
+ * specs they were launched with (the call waits for them before the rows they count into are released).  The rows of ALL facets live in one block taken from the
+ * handle's buffer pool: nq x sum over the facets of (nbuckets + 1) x 4 bytes (+ 64 KB, the pool's smallest buffer), in caller query order (hidden phrase-leaf queries have no row) —
+ * TRI_ERR_NOMEM when it cannot be had.  TRI_ERR_INVALID, nothing changed: a null column, a column of another index, n > TRI_FACETS_MAX, nbuckets of 0 or
+ * above TRI_FACET_MAX_BUCKETS, reserved != 0, a batch created with TRI_FLAG_ACCUMULATED_SCORE (its one-pass queries keep no docID sets).  The parts of a
+ * tri_cbatch each carry their own facets.
+ * Every later tri_batch_run zeroes the block and counts again, on the engine stream behind the kernels that complete the docID sets (one more launch per run;
+ * a batch without facets launches nothing more); the rows stand after tri_batch_sync.
+ * tri_batch_facets: facet k's rows for the whole batch in one copy, counts[q * (nbuckets_k + 1) + v].  For every document d of query q's docID set — exactly what
+ * tri_batch_docset delivers: the index's masked set and q's filter are applied, there is no second rule — counter min(values[d], nbuckets_k) goes up by one; the
+ * last counter is the overflow bucket, so a row always sums to tri_batch_match_counts[q].  A query the planner left out, or one without matches, has an
+ * all-zero row.  TRI_ERR_INVALID, nothing written: no facets set, k out of range, cap (in counters) below nq * (nbuckets_k + 1), no tri_batch_sync since
+ * the last run, facets set or replaced since the last run.
+ * tri_cbatch_facets: after tri_cbatch_sync, the parts' rows widened and summed (a docID that several sources deliver counts once per source, as tri_cbatch_docset
+ * lists it).  TRI_ERR_INVALID, naming the part, when the parts disagree in the number of facets or in nbuckets_k.
+ * tri_dev_get_option "facet_last_us" (read-only): the device time of the last faceted run's zeroing and counting kernel, read at tri_batch_sync. */
+typedef struct tri_column tri_column;
+int tri_column_create(tri_index *, const uint32_t *values, size_t n /* docs_cnt + 1 */, tri_column **out);
+void tri_column_destroy(tri_column *);
+#define TRI_FACETS_MAX 4
+#define TRI_FACET_MAX_BUCKETS 65536u
+typedef struct tri_facet {
+        tri_column *column;
+        uint32_t nbuckets; /* 1 .. TRI_FACET_MAX_BUCKETS; the row has nbuckets + 1 counters */
+        uint32_t reserved; /* 0 */
+} tri_facet;
+int tri_batch_set_facets(tri_batch *, const tri_facet *facets, size_t n /* 0: clear */);
+int tri_batch_facets(tri_batch *, size_t k, uint32_t *counts /* [nq][nbuckets_k + 1], caller query order */, size_t cap);
+/* (tri_cbatch_facets is declared with the collection's calls below) */
 
 /* ---- postings decode (codec seam) -----------------------------------------------------------------
  * Replaces Codecs::PostingsListIterator::next() driven to exhaustion (google_codec.cpp:777-819,
@@ -613,6 +654,8 @@ int tri_cbatch_match_counts(tri_cbatch *, uint64_t *counts /* [nq] */);
 int tri_cbatch_topk(tri_cbatch *, uint32_t *docids, float *scores, uint32_t *counts);
 int tri_cbatch_docset(tri_cbatch *, size_t q, uint32_t *out, size_t cap, size_t *n);
 int tri_cbatch_ranked(tri_cbatch *, uint32_t *docids /* [nq][topk] */, double *scores /* [nq][topk] */, uint32_t *counts /* [nq] */);
+/* facet k's rows over the collection ("facet counts" above): the parts' rows widened and summed */
+int tri_cbatch_facets(tri_cbatch *, size_t k, uint64_t *counts /* [nq][nbuckets_k + 1]: the parts' rows summed */, size_t cap);
 int tri_cbatch_matched_terms(tri_cbatch *, size_t q, uint32_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos);
 int tri_cbatch_matched_terms_wide(tri_cbatch *, size_t q, uint64_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos);
 int tri_cbatch_matched_payloads(tri_cbatch *, size_t q, uint8_t *lens, uint64_t *payloads, size_t cap, size_t *n);

@@ -34,7 +34,7 @@ def hipcc():
 
 
 def build_hip(force=False):
-    if force or _newer(LIB_HIP, _deps(HIP_SRCS) + [os.path.join(PKG, "csrc", "host", n) for n in ("result_rows.hpp", "isect_rows.hpp", "perc_lower.hpp")]):  # (read_side.hpp's host transforms, isect_side.hpp's replay, perc_side.hpp's lowering)
+    if force or _newer(LIB_HIP, _deps(HIP_SRCS) + [os.path.join(PKG, "csrc", "host", n) for n in ("result_rows.hpp", "isect_rows.hpp", "perc_lower.hpp", "facet_rows.hpp")]):  # (read_side.hpp's host transforms, isect_side.hpp's replay, perc_side.hpp's lowering, read_side.hpp's sum of a collection's facet rows)
         cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-o", LIB_HIP] + HIP_SRCS + ["-ldl"]
         subprocess.run(cmd, check=True)
     return LIB_HIP
@@ -182,9 +182,25 @@ def build_mirror_perc_test(force=False):
     return MIRROR_PERC_BIN
 
 
+MIRROR_FACETS_SRC = os.path.join(ROOT, "tests", "cpp", "host_mirror_facets_test.cpp")
+MIRROR_FACETS_BIN = os.path.join(ROOT, "tests", "cpp", "host_mirror_facets_test")
+
+
+def build_mirror_facets_test(force=False):
+    """FacetCounter and DeviceColumn of the operator surface (csrc/host/trinity_gpu.hpp: counted on the device through tri_batch_set_facets / tri_batch_facets, and through
+    the replay) compiled into their driver; in-tree, so that it travels to the GPU box, where tests/test_host_mirror_facets.py runs it."""
+    deps = [MIRROR_FACETS_SRC, os.path.join(PKG, "csrc", "host", "trinity_gpu.hpp"), os.path.join(PKG, "csrc", "host", "facet_rows.hpp"), os.path.join(PKG, "csrc", "host", "google_encoder.hpp"),
+            os.path.join(ROOT, "include", "trinity_hip.h")]  # fmt: skip
+    if force or _newer(MIRROR_FACETS_BIN, deps):
+        build_hip()
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", MIRROR_FACETS_BIN, MIRROR_FACETS_SRC, "-L" + PKG, "-ltrinity_hip", "-Wl,-rpath,$ORIGIN/../../trinity_amd"]
+        subprocess.run(cmd, check=True)
+    return MIRROR_FACETS_BIN
+
+
 def build_all(force=False):
     return (build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force), build_mirror_wide_terms_test(force),
-            build_mirror_hits_test(force), build_mirror_rank_test(force), build_mirror_collection_test(force), build_mirror_isect_test(force), build_mirror_perc_test(force))
+            build_mirror_hits_test(force), build_mirror_rank_test(force), build_mirror_collection_test(force), build_mirror_isect_test(force), build_mirror_perc_test(force), build_mirror_facets_test(force))
 
 
 def kernels_stamp():

@@ -262,3 +262,22 @@ struct DevFused {
 constexpr uint32_t FUS_MODE_TT = 1;   // predicate = tt, scores through ctt
 constexpr uint32_t FUS_MODE_EMIT = 2; // DocumentsOnly: the window's matches are written to out[] (ascending), nothing is scored
 
+
+// ---- facet counts (k_facet.hpp; tri_batch_set_facets): per query and facet a row of nbuckets + 1 counters over a per-document column — for every document d of
+//      the query's docID set, counter min(values[d], nbuckets) goes up by one (the last counter is the overflow bucket).  The rows live in caller query order,
+//      facet after facet: facet k's rows start at counter rows_off[k] of the batch's row block, query q's row at rows_off[k] + q * (nb[k] + 1)
+constexpr uint32_t FACETS_MAX = 4;                 // == TRI_FACETS_MAX
+constexpr uint32_t FACET_MAX_BUCKETS = 65536;      // == TRI_FACET_MAX_BUCKETS
+constexpr uint32_t FACET_WG = 256;                 // threads of a workgroup of k_facet (a workgroup per task)
+constexpr uint32_t FACET_LDS_COUNTERS = 4096;      // the most counters per query (all facets: sum of nbuckets + 1) a workgroup sums in an LDS row of its own before
+                                                   // it touches the global row (16 KB: ten workgroups per CU keep theirs); wider rows take global atomics per match
+constexpr uint32_t FACET_SHORT_SEGMENT = 128;      // a task segment of fewer matches goes straight to the global row: zeroing and flushing an LDS row would cost a
+                                                   // workgroup more steps than the segment has documents per lane pair
+struct DevFacets { // passed to the kernel BY VALUE: a run already queued keeps the specs it was launched with
+        const uint32_t *values[FACETS_MAX]; // the columns (tri_column): values[k][d] = the attribute of docID d
+        uint64_t rows_off[FACETS_MAX];      // facet k's first counter in the row block
+        uint32_t ndocs[FACETS_MAX];         // entries of column k (docs_cnt + 1): a docID at or past it counts as overflow, never read
+        uint32_t nb[FACETS_MAX];            // nbuckets
+        uint32_t lds_off[FACETS_MAX + 1];   // facet k's first counter in a workgroup's LDS row; [n] = per_query
+        uint32_t n, per_query;              // facets; counters per query (all facets: sum of nb + 1)
+};

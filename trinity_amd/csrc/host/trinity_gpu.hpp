@@ -15,6 +15,7 @@
 #pragma once
 #include "../../../include/trinity_hip.h"
 #include "google_encoder.hpp"
+#include "facet_rows.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -429,6 +430,7 @@ namespace trinity_amd {
                 matched_query_term *matchedTerms{nullptr};
         };
 
+        struct FacetCounter;
         struct MatchedIndexDocumentsFilter { // matches.h:139-185
                 virtual void consider(const matched_document &) {} // default execution mode
                 virtual void consider(const docid_t) {}
@@ -441,6 +443,9 @@ namespace trinity_amd {
                 // tri_ranker and the weights of the query's terms (per matchedTerms[].queryCtx->term.id - 1) and returns where the ranked list goes; the default
                 // mode's exec_query then ranks on the device (tri_batch_set_ranker) and replays no match.  nullptr (every other filter): consider() per match.
                 virtual std::vector<std::pair<docid_t, double>> *device_ranker(tri_ranker *, std::vector<double> *) { return nullptr; }
+                // A filter that counts its documents by per-document columns (FacetCounter below) says so here: a DocumentsOnly exec_query binds it to the source it
+                // runs against and, unless the counter asks for the replay, has the device count (tri_batch_set_facets) and replays no match.  nullptr: every other filter.
+                virtual FacetCounter *facet_counter() { return nullptr; }
                 virtual ~MatchedIndexDocumentsFilter() = default;
         };
 
@@ -793,6 +798,103 @@ namespace trinity_amd {
                 tri_filter *device_filter() override { return h; }
         };
 
+        // ---- facet counts: "just count or collect documents matching a query" (exec.h:12-23), by a per-document attribute.  A DeviceColumn holds the attribute of
+        // every docID of ONE source, on the host (the replay path reads it) and on the device (tri_column_create); closed before its source.
+        class DeviceColumn final {
+                tri_column *h{nullptr};
+                IndexSource *const src;
+                std::vector<uint32_t> vals; // [docsCnt + 1]: vals[d] for docID d
+
+              public:
+                DeviceColumn(IndexSource *s, std::vector<uint32_t> values) : src{s}, vals(std::move(values)) { check(tri_column_create(src->handle(), vals.data(), vals.size(), &h)); }
+                template <class Fn, class = decltype(uint32_t(std::declval<Fn &>()(docid_t{})))>
+                DeviceColumn(IndexSource *s, Fn &&attribute) : src{s} { // attribute(docID) for 1 .. docsCnt
+                        const uint32_t n = src->default_field_stats().docsCnt;
+                        vals.assign(size_t(n) + 1, 0);
+                        for (docid_t d = 1; d <= n; ++d)
+                                vals[d] = attribute(d);
+                        check(tri_column_create(src->handle(), vals.data(), vals.size(), &h));
+                }
+                ~DeviceColumn() { tri_column_destroy(h); }
+                DeviceColumn(const DeviceColumn &) = delete;
+                tri_column *handle() const { return h; }
+                IndexSource *source() const { return src; }
+                const std::vector<uint32_t> &values() const { return vals; }
+        };
+
+        // The application's consider(id) / consider(ids, cnt) when it counts the matches by attributes — row k has facets[k].nbuckets + 1 counters, and for every
+        // considered document counter min(value, nbuckets) goes up by one (the last one is the overflow bucket; facet_rows.hpp) — and the device form of the same:
+        // a DocumentsOnly exec_query recognises the counter (facet_counter()) and, with device == true, sets the facets on its batch and reads the rows back
+        // (tri_batch_facets) instead of delivering the docID set; device = false keeps the replay through consider(), for comparison.  A facet lists one column per
+        // source the counter may run against (a collection: one per source); exec_query binds the counter to its source first.
+        struct FacetCounter : public MatchedIndexDocumentsFilter {
+                struct Facet {
+                        std::vector<const DeviceColumn *> columns; // one per source
+                        uint32_t nbuckets;
+                };
+                std::vector<Facet> facets;
+                bool device{true};
+                std::vector<std::vector<uint32_t>> rows; // [facet][nbuckets + 1]
+                std::vector<const DeviceColumn *> bound;   // per facet: the column of the source the counter runs against
+
+                explicit FacetCounter(std::vector<Facet> f, const bool onDevice = true) : facets(std::move(f)), device{onDevice} {
+                        if (facets.empty() || facets.size() > TRI_FACETS_MAX)
+                                throw invalid_argument("FacetCounter: 1 .. TRI_FACETS_MAX facets");
+                        for (const auto &x : facets) {
+                                if (x.nbuckets < 1 || x.nbuckets > TRI_FACET_MAX_BUCKETS)
+                                        throw invalid_argument("FacetCounter: nbuckets 1 .. TRI_FACET_MAX_BUCKETS");
+                                rows.emplace_back(size_t(x.nbuckets) + 1, 0u);
+                        }
+                }
+                FacetCounter *facet_counter() override { return this; }
+                void bind(IndexSource *src) {
+                        bound.assign(facets.size(), nullptr);
+                        for (size_t k = 0; k < facets.size(); ++k) {
+                                for (const DeviceColumn *c : facets[k].columns)
+                                        if (c && c->source() == src)
+                                                bound[k] = c;
+                                if (!bound[k])
+                                        throw invalid_argument("FacetCounter: a facet has no column of the source the query runs against");
+                        }
+                }
+                void consider(const docid_t id) override { consider(&id, 1); }
+                void consider(const docid_t *ids, const size_t cnt) override {
+                        if (bound.size() != facets.size())
+                                throw invalid_argument("FacetCounter: not bound to a source (exec_query binds it)");
+                        for (size_t k = 0; k < facets.size(); ++k)
+                                facet_rows::count(rows[k].data(), bound[k]->values().data(), bound[k]->values().size(), facets[k].nbuckets, ids, cnt);
+                }
+                // the device form: the specs for tri_batch_set_facets ...
+                std::vector<tri_facet> specs() const {
+                        std::vector<tri_facet> out;
+                        for (size_t k = 0; k < facets.size(); ++k)
+                                out.push_back(tri_facet{bound[k]->handle(), facets[k].nbuckets, 0});
+                        return out;
+                }
+                // ... and the rows of the batch's query q added to the counter's
+                void read(tri_batch *b, const size_t q, const size_t nq) {
+                        std::vector<uint32_t> all;
+                        for (size_t k = 0; k < facets.size(); ++k) {
+                                const size_t w = size_t(facets[k].nbuckets) + 1;
+                                all.resize(nq * w);
+                                check(tri_batch_facets(b, k, all.data(), all.size()));
+                                for (size_t i = 0; i < w; ++i)
+                                        rows[k][i] += all[q * w + i];
+                        }
+                }
+                // The counters of a collection's sources (exec_query's collection form, one FacetCounter per source) summed, widened: the host form of tri_cbatch_facets.
+                static std::vector<uint64_t> sum(const std::vector<std::unique_ptr<FacetCounter>> &parts, const size_t k) {
+                        std::vector<uint64_t> out;
+                        for (const auto &p : parts) {
+                                if (k >= p->rows.size() || (!out.empty() && out.size() != p->rows[k].size()))
+                                        throw invalid_argument("FacetCounter::sum: the parts disagree in their facets");
+                                out.resize(p->rows[k].size(), 0);
+                                facet_rows::add(out.data(), p->rows[k].data(), out.size());
+                        }
+                        return out;
+                }
+        };
+
         // ------------------------------------------------------------------ execution
         struct BatchDeleter {
                 void operator()(tri_batch *b) const { tri_batch_destroy(b); }
@@ -1075,6 +1177,18 @@ namespace trinity_amd {
                 // a filter the device holds (DeviceDocumentsFilter) is installed with the batch — tri_batch_set_filters — and asked nothing here; a plain host
                 // filter is asked per replayed document
                 tri_filter *const onDevice = f ? f->device_filter() : nullptr;
+                // a facet counter runs against this source; on the device when nothing but the device decides which documents count (DocumentsOnly, no host filter)
+                FacetCounter *const fc = matchesFilter ? matchesFilter->facet_counter() : nullptr;
+                if (fc) {
+                        fc->bind(src);
+                        if (fc->device && (flags & unsigned(ExecFlags::DocumentsOnly)) && (!f || onDevice)) {
+                                const auto specs = fc->specs();
+                                auto b = run_batch(src, {root}, flags, 0, nullptr, onDevice ? std::vector<tri_filter *>{onDevice} : std::vector<tri_filter *>{},
+                                                   [&](tri_batch *bt, const std::vector<uint32_t> &, const std::vector<tri_query> &) { check(tri_batch_set_facets(bt, specs.data(), specs.size())); });
+                                fc->read(b.get(), 0, 1);
+                                return;
+                        }
+                }
                 handler.mf = matchesFilter;
                 handler.df = onDevice ? nullptr : f;
                 handler.scored = flags & unsigned(ExecFlags::AccumulatedScoreScheme);

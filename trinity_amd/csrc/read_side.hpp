@@ -4,9 +4,11 @@
 //   read_check / query_view   the arguments, the mode, "tri_batch_sync first", and — per query — the plan slot, the DevQuery and the match count
 //   for_each_segment          a query's result is the in-order concatenation of its task segments
 //   ReadBack                  THE stream rule: a result copy is enqueued on the read-back stream under the handle's lock and awaited outside it
-// The transforms between the device's layout and the caller's (mask widening, frequency-row narrowing, bitmap expansion) are host/result_rows.hpp.
+// The transforms between the device's layout and the caller's (mask widening, frequency-row narrowing, bitmap expansion) are host/result_rows.hpp; a collection's
+// facet rows are summed by host/facet_rows.hpp.
 #pragma once
 #include "host/result_rows.hpp"
+#include "host/facet_rows.hpp"
 
 namespace {
         // what every result call opens with: its arguments, the flags the batch must have been created with, and (must_sync) that its results stand
@@ -436,6 +438,22 @@ extern "C" int tri_batch_topk_device(tri_batch *b, void **docids, void **scores,
         return TRI_OK;
 }
 
+// facet counts (tri_batch_set_facets; k_facet.hpp): one facet's rows of the whole batch: they lie in caller query order, one after the other — ONE read-back copy
+extern "C" int tri_batch_facets(tri_batch *b, size_t k, uint32_t *counts, size_t cap) {
+        if (const int rc = read_check(b, counts != nullptr, __func__, 0, false))
+                return rc;
+        if (!b->facets.n)
+                return fail(TRI_ERR_INVALID, "%s: no facets are set (tri_batch_set_facets)", __func__);
+        if (k >= b->facets.n)
+                return fail(TRI_ERR_INVALID, "%s: facet %zu of %u", __func__, k, b->facets.n);
+        if (!b->synced || !b->facet_done)
+                return fail(TRI_ERR_INVALID, "%s: tri_batch_sync first (a run that follows tri_batch_set_facets)", __func__);
+        const size_t need = b->nq * ((size_t)b->facets.nb[k] + 1);
+        if (cap < need)
+                return fail(TRI_ERR_INVALID, "%s: the rows need %zu counters, %zu given", __func__, need, cap);
+        return ReadBack(b->dev).copy(counts, b->d_facet_rows + b->facets.rows_off[k], need * 4).done();
+}
+
 // ---- a collection batch's results: merged on the device by tri_cbatch_run (match counts add up, top-K lists merge K-way)
 extern "C" int tri_cbatch_match_counts(tri_cbatch *c, uint64_t *counts) {
         if (const int rc = cbatch_check(c, counts != nullptr, __func__))
@@ -519,5 +537,35 @@ extern "C" int tri_cbatch_matched_payloads(tri_cbatch *c, size_t q, uint8_t *len
                         return rc;
                 w += m;
         }
+        return TRI_OK;
+}
+
+// facet k's rows over a collection (tri_batch_facets above): the parts' rows widened and summed (a document of several sources counts once per source that delivers it, as tri_cbatch_docset lists it)
+extern "C" int tri_cbatch_facets(tri_cbatch *c, size_t k, uint64_t *counts, size_t cap) {
+        if (const int rc = cbatch_check(c, counts != nullptr, __func__))
+                return rc;
+        const tri_batch *p0 = c->parts[0];
+        for (size_t i = 0; i < c->parts.size(); ++i) {
+                const tri_batch *p = c->parts[i];
+                if (p->facets.n != p0->facets.n)
+                        return fail(TRI_ERR_INVALID, "%s: part %zu carries %u facets, part 0 carries %u", __func__, i, p->facets.n, p0->facets.n);
+                if (k < p->facets.n && p->facets.nb[k] != p0->facets.nb[k])
+                        return fail(TRI_ERR_INVALID, "%s: facet %zu has %u buckets in part %zu and %u in part 0", __func__, k, p->facets.nb[k], i, p0->facets.nb[k]);
+        }
+        if (!p0->facets.n)
+                return fail(TRI_ERR_INVALID, "%s: no facets are set on the parts (tri_batch_set_facets)", __func__);
+        if (k >= p0->facets.n)
+                return fail(TRI_ERR_INVALID, "%s: facet %zu of %u", __func__, k, p0->facets.n);
+        const size_t need = p0->nq * ((size_t)p0->facets.nb[k] + 1);
+        if (cap < need)
+                return fail(TRI_ERR_INVALID, "%s: the rows need %zu counters, %zu given", __func__, need, cap);
+        std::vector<uint32_t> part(need);
+        std::vector<uint64_t> sum(need, 0); // (nothing is written to counts[] before every part has answered)
+        for (tri_batch *p : c->parts) {
+                if (const int rc = tri_batch_facets(p, k, part.data(), need))
+                        return rc;
+                facet_rows::add(sum.data(), part.data(), need);
+        }
+        std::copy(sum.begin(), sum.end(), counts);
         return TRI_OK;
 }

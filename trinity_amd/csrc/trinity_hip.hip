@@ -74,6 +74,7 @@ struct tri_dev {
         int cus;
         tri_options opt;
         uint64_t rich_write_last_us = 0, rank_last_us = 0; // the last ranked batch's WRITE pass and rank pass (tri_dev_get_option, read-only)
+        uint64_t facet_last_us = 0;                        // the last faceted run's row zeroing + k_facet (read at tri_batch_sync)
         uint64_t crank_merge_last_us = 0;                  // the last ranked collection's merge of its parts' lists (k_rank_merge_sources)
         int refs = 0;         // indexes and batches alive on this handle ...
         bool closing = false; // ... tri_dev_close with some left: the handle goes with the last of them
@@ -360,6 +361,18 @@ struct tri_filter {
                         hipSetDevice(dev->device);
         }
 };
+// A per-document attribute column (tri_column_create): values[d] for docID d = 0 .. docs_cnt, resident in HBM.  It belongs to its index — destroyed before it — and
+// is only read by the runs of the batches that name it (tri_batch_set_facets: k_facet.hpp)
+struct tri_column {
+        DevRef dev; // (first: released last)
+        tri_index *ix = nullptr;
+        DevMem<uint32_t> d_values; // an owning device buffer (hipFree waits for every run that may still read it)
+        uint32_t n = 0;
+        ~tri_column() {
+                if (dev)
+                        hipSetDevice(dev->device);
+        }
+};
 // whole docID windows (the bitmap kernels read a window's worth of words at a time), one spare window: the extent of d_masked and of every filter
 static size_t filter_words(const tri_index *ix) { return ((size_t)ix->max_doc / SPAN_BITS + 2) * SPAN_WORDS; }
 
@@ -407,6 +420,10 @@ struct tri_batch : BatchPlan {
         Pooled<uint8_t> d_filter_tab;
         Pooled<uint32_t> d_filter_rows;
         Pooled<uint8_t> d_rank_block; // tri_batch_set_ranker (k_rich_rank.hpp): ONE block, rank_block()'s sections
+        // tri_batch_set_facets (k_facet.hpp): the specs as the kernel takes them (the columns by reference), ONE pooled row block ([facet][caller query][nbuckets + 1]
+        // counters, zeroed and recounted by every run) and the events around the run's zeroing + kernel (option facet_last_us)
+        Pooled<uint32_t> d_facet_rows;
+        PooledEvent facet_ev[2];
         // ---- VIEWS: plain pointers into the buffers above, released with them
         // a section of the plan (a Span of BatchPlan: planner_types.hpp, for_each_section) on the device — the block's copy opens the arena
         template <class T>
@@ -450,6 +467,9 @@ struct tri_batch : BatchPlan {
         // tri_batch_set_ranker: the spec, and the caller's program (kept by default-mode batches: the ranker's weights come one per program token)
         bool rank_on = false, rank_done = false;
         tri_ranker rank{};
+        DevFacets facets{};                       // the specs; facets.n == 0: none
+        size_t facet_counters = 0;                // counters of d_facet_rows
+        bool facet_ran = false, facet_done = false; // the last run counted with the specs that stand; ... and tri_batch_sync has awaited it
         std::vector<uint32_t> h_prog;
         std::vector<tri_query> h_queries;
         tri_batch_info info{};
@@ -482,6 +502,7 @@ struct tri_batch : BatchPlan {
 #include "k_tree.hpp"
 #include "k_tree_wide.hpp"
 #include "k_perc.hpp"
+#include "k_facet.hpp"
 #include "k_commit.hpp"
 #include "k_lencode.hpp"
 #include "filtered_kernels.hpp"
@@ -583,6 +604,10 @@ extern "C" int tri_dev_get_option(tri_dev *d, const char *name, uint64_t *value)
         // (read-only: the device time of the last ranked batch's WRITE pass and rank pass — HIP events around them, tri_batch_sync)
         if (!strcmp(name, "rich_write_last_us") || !strcmp(name, "rank_last_us")) {
                 *value = !strcmp(name, "rich_write_last_us") ? d->rich_write_last_us : d->rank_last_us;
+                return TRI_OK;
+        }
+        if (!strcmp(name, "facet_last_us")) { // (... of the last faceted run's row zeroing and k_facet, tri_batch_sync)
+                *value = d->facet_last_us;
                 return TRI_OK;
         }
         if (!strcmp(name, "crank_merge_last_us")) { // (... and of the last ranked collection's merge kernel, tri_cbatch_sync)
@@ -1777,6 +1802,25 @@ static int run_query_counts(tri_batch *b) {
         return TRI_OK;
 }
 
+// tri_batch_set_facets: the rows zeroed and counted behind the kernels that complete the docID sets (every stage above; k_facet reads the device-side task
+// counts), ahead of the run's end event.  A batch without facets enqueues nothing
+static int run_facets(tri_batch *b) {
+        b->facet_ran = b->facet_done = false;
+        if (!b->facets.n)
+                return TRI_OK;
+        tri_dev *dev = b->dev;
+        HIP_TRY(hipEventRecord(b->facet_ev[0], dev->stream));
+        HIP_TRY(hipMemsetAsync(b->d_facet_rows, 0, b->facet_counters * 4, dev->stream));
+        if (!b->tasks.empty()) {
+                hipLaunchKernelGGL(k_facet, dim3((uint32_t)b->tasks.size()), dim3(FACET_WG), 0, dev->stream, (const DevQuery *)b->dev_at(b->plan), (const DevTask *)b->dev_at(b->tasks),
+                                   (const uint32_t *)b->d_counts, (const uint32_t *)b->d_out, b->facets, b->d_facet_rows.get());
+                HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(b->facet_ev[1], dev->stream));
+        b->facet_ran = true;
+        return TRI_OK;
+}
+
 extern "C" int tri_batch_run(tri_batch *b) {
         if (!b)
                 return fail(TRI_ERR_INVALID, "null batch");
@@ -1823,6 +1867,8 @@ extern "C" int tri_batch_run(tri_batch *b) {
                                 return rc;
         }
         if (const int rc = run_query_counts(b))
+                return rc;
+        if (const int rc = run_facets(b))
                 return rc;
         HIP_TRY(hipEventRecord(b->ev[EV_END], dev->stream));
         return TRI_OK;
@@ -2187,6 +2233,12 @@ extern "C" int tri_batch_sync(tri_batch *b) {
         report_tasktimes(b);
 #endif
         read_stage_times(b);
+        if (b->facet_ran) { // (both events precede EV_END)
+                float ms = 0;
+                if (hipEventElapsedTime(&ms, b->facet_ev[0], b->facet_ev[1]) == hipSuccess)
+                        dev->facet_last_us = (uint64_t)(ms * 1000.0f);
+                b->facet_done = true;
+        }
         int rc;
         if ((rc = account_matches(b)) || (rc = rich_write_pass(b)))
                 return rc;
@@ -2834,6 +2886,7 @@ extern "C" int tri_gather_results(tri_batch *b, tri_comm *c, void *counts_all, v
 // the encoders, commit and merge on the device: tri_encode_*, tri_commit_*, tri_merge_* and the scratch they allocate from
 #include "write_side.hpp"
 #include "isect_side.hpp"
+#include "facet_side.hpp"
 #include "perc_side.hpp"
 
 #ifdef TRI_PROF

@@ -42,6 +42,10 @@ class TriRanker(C.Structure):
 RANK_PROXIMITY = 1
 
 
+class TriFacet(C.Structure):
+    _fields_ = [("column", C.c_void_p), ("nbuckets", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class TriIsectRequest(C.Structure):
     _fields_ = [("ngroups", C.c_uint32), ("reserved", C.c_uint32), ("stopwords_mask", C.c_uint64)]
 
@@ -150,6 +154,7 @@ ABI_SYMBOLS = [
     "tri_isect_run", "tri_isect_status", "tri_isect_results", "tri_isect_histogram", "tri_isect_get_info", "tri_isect_destroy",
     "tri_perc_create", "tri_perc_query_status", "tri_perc_set_enabled", "tri_perc_get_info", "tri_perc_destroy", "tri_perc_match",
     "tri_perc_result_pairs", "tri_perc_result_doc_counts", "tri_perc_result_get_info", "tri_perc_result_destroy",
+    "tri_column_create", "tri_column_destroy", "tri_batch_set_facets", "tri_batch_facets", "tri_cbatch_facets",
 ]  # fmt: skip
 
 _hip = None
@@ -238,6 +243,12 @@ def hip_lib():
     L.tri_filter_destroy.restype = None
     L.tri_batch_set_filters.argtypes = [vp, vp, C.c_size_t, vp]
     L.tri_batch_set_ranker.argtypes = [vp, vp, vp]
+    L.tri_column_create.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
+    L.tri_column_destroy.argtypes = [vp]
+    L.tri_column_destroy.restype = None
+    L.tri_batch_set_facets.argtypes = [vp, C.POINTER(TriFacet), C.c_size_t]
+    L.tri_batch_facets.argtypes = [vp, C.c_size_t, vp, C.c_size_t]
+    L.tri_cbatch_facets.argtypes = [vp, C.c_size_t, vp, C.c_size_t]
     L.tri_isect_run.argtypes = [vp, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
     L.tri_isect_status.argtypes = [vp, vp]
     L.tri_isect_results.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -797,6 +808,26 @@ class Filter:
             self.h = C.c_void_p()
 
 
+FACETS_MAX = 4  # TRI_FACETS_MAX
+FACET_MAX_BUCKETS = 65536  # TRI_FACET_MAX_BUCKETS
+
+
+class Column:
+    """A per-document attribute column on the device (tri_column_create): values[d] = the attribute of docID d, docs_cnt + 1 entries (values[0] is never read).
+    Closed before its index; alive while a batch that names it may run."""
+
+    def __init__(self, index, values):
+        self.index = index
+        v = np.ascontiguousarray(values, dtype=np.uint32)
+        self.h = C.c_void_p()
+        _check(hip_lib().tri_column_create(index.h, v.ctypes.data if v.size else None, v.size, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            hip_lib().tri_column_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class Batch:
     """A compiled batch of postfix query programs."""
 
@@ -843,6 +874,25 @@ class Batch:
         arr = (C.c_void_p * max(1, len(filters)))(*[f.h for f in filters])
         _check(hip_lib().tri_batch_set_filters(self.h, arr if filters else None, len(filters), foq.ctypes.data if filters else None))
         self._filters = filters
+
+    def set_facets(self, facets):
+        """Facet counts for the runs that follow (tri_batch_set_facets): facets = [(Column, nbuckets), ...], at most FACETS_MAX; an empty list clears.  Every run then
+        counts each query's docID set by the columns' values on the device; results: facets(k).  The batch keeps the Column objects referenced."""
+        facets = list(facets)
+        arr = (TriFacet * max(1, len(facets)))()
+        for i, (col, nb) in enumerate(facets):
+            arr[i].column, arr[i].nbuckets, arr[i].reserved = (col.h if col is not None else None), int(nb), 0
+        _check(hip_lib().tri_batch_set_facets(self.h, arr if facets else None, len(facets)))
+        self._facets = facets
+
+    def facets(self, k):
+        """After sync(): facet k's rows, u32[nq, nbuckets + 1] in caller query order — row[q, v] = the documents of query q's docID set whose value is v; the last
+        counter takes every value >= nbuckets, so a row sums to counts()[q] (tri_batch_facets: one copy for the whole batch)."""
+        spec = getattr(self, "_facets", [])
+        nb = int(spec[k][1]) if 0 <= k < len(spec) else 0  # (out of range: the library refuses)
+        out = np.zeros((self.nq, nb + 1), dtype=np.uint32)
+        _check(hip_lib().tri_batch_facets(self.h, k, out.ctypes.data, out.size))
+        return out
 
     def set_ranker(self, topk, freq_cap=65535, adjacency=0.0, weights=None):
         """FLAG_MATCHED_TERMS batches: rank every query's matches on the device for the runs that follow (tri_batch_set_ranker, TRI_RANK_PROXIMITY):
@@ -1077,6 +1127,15 @@ class CollectionBatch:
         c = np.zeros(self.nq, dtype=np.uint32)
         _check(hip_lib().tri_cbatch_ranked(self.h, d.ctypes.data, s.ctypes.data, c.ctypes.data))
         return d, s, c
+
+    def facets(self, k):
+        """After sync(): facet k's rows over the collection, u64[nq, nbuckets + 1] — the parts' rows summed (tri_cbatch_facets); the parts must agree in the number
+        of facets and in facet k's nbuckets."""
+        spec = getattr(self.parts[0], "_facets", [])
+        nb = int(spec[k][1]) if 0 <= k < len(spec) else 0
+        out = np.zeros((self.nq, nb + 1), dtype=np.uint64)
+        _check(hip_lib().tri_cbatch_facets(self.h, k, out.ctypes.data, out.size))
+        return out
 
     def _query_width(self, q):
         """(terms, nterms) of query q: those of the first part that reports it (the parts agree, or the row calls refuse)."""
