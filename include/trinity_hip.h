@@ -43,7 +43,9 @@ extern "C" {
                                 within 9: tri_encode_lucene_payloads / tri_commit_lucene_payloads (the Lucene-shaped codec carries hit payloads: written, merged by
                                 tri_merge_lucene, read by tri_decode_hits[_at] and tri_batch_matched_payloads; no struct grew);
                                 within 9: tri_column_create / tri_column_destroy / tri_batch_set_facets / tri_batch_facets / tri_cbatch_facets, read-only option facet_last_us
-                                (facet counts: per query a histogram of its docID set over per-document columns, counted on the device; no existing struct grew) */
+                                (facet counts: per query a histogram of its docID set over per-document columns, counted on the device; no existing struct grew);
+                                within 9: tri_batch_set_order / tri_batch_ordered / tri_cbatch_ordered, read-only option order_last_us
+                                (order by a column: per query the first topk documents of its docID set by a column's value, selected on the device; no existing struct grew) */
 
 /* status codes */
 #define TRI_OK 0
@@ -327,6 +329,42 @@ typedef struct tri_facet {
 int tri_batch_set_facets(tri_batch *, const tri_facet *facets, size_t n /* 0: clear */);
 int tri_batch_facets(tri_batch *, size_t k, uint32_t *counts /* [nq][nbuckets_k + 1], caller query order */, size_t cap);
 /* (tri_cbatch_facets is declared with the collection's calls below) */
+
+/* ---- order by a column -----------------------------------------------------------------------------
+ * The last thing an application does in MatchedIndexDocumentsFilter::consider(id) / consider(ids, cnt) (exec.h:12-23: "just count or collect documents
+ * matching a query") besides counting and ranking: LIST the first K matches by a per-document attribute — newest first, cheapest first, highest rated first.
+ * A batch that names a column and a K (an order) selects, at the end of every run and on the device, each query's first K documents: K x 8 bytes a query
+ * cross PCIe instead of the docID set.
+ *
+ * tri_batch_set_order (exec.h:12-23): after tri_batch_create, before a run, again between runs; NULL removes; it holds for every later run until replaced or
+ * removed; the column is stored by reference (the filters' lifetime rules: tri_column_create above).  Runs already queued keep the spec and the blocks they were
+ * launched with (the call waits for them before it swaps).  The partial lists and the rows live in one block taken from the handle's buffer pool: (tasks + the
+ * merge's intermediate lists + nq) x (topk x 8 + 4) bytes (+ 64 KB, the pool's smallest buffer) — TRI_ERR_NOMEM when it cannot be had.  TRI_ERR_INVALID, nothing
+ * changed: a null batch, a null column, a column of another index, topk outside 1 .. TRI_ORDER_MAX_TOPK, reserved != 0, a batch created with
+ * TRI_FLAG_ACCUMULATED_SCORE (its one-pass queries keep no docID sets).  An order, facets and a ranker may stand on one batch together.  Every later tri_batch_run
+ * selects again, on the engine stream behind the kernels that complete the docID sets (one launch for the tasks and one per round of the merge: one round up to
+ * 32 tasks a query, two up to 1024; a batch without an order, or without tasks, launches nothing more); the rows stand after tri_batch_sync.
+ * tri_batch_ordered (exec.h:12-23): for every query q, in caller query order, the first counts[q] = min(|S|, topk) documents of its docID set S — exactly what
+ * tri_batch_docset delivers: the index's masked set and q's filter are applied, the default mode's sets are included — sorted by (values[d] ascending, docID
+ * ascending), or with descending != 0 by (values[d] descending, docID ASCENDING): ties go to the lower docID in both directions; values compare as unsigned
+ * 32-bit.  values[q][i] is the column's value of docids[q][i]; entries past counts[q] are zero in both arrays; a query the planner left out has count 0.
+ * Everything is integer: the same bits from run to run and under every option set.  TRI_ERR_INVALID, nothing written: no order set, no tri_batch_sync since
+ * the last run, an order set or replaced since the last run, a null output.
+ * tri_cbatch_ordered (exec.h:12-23): after tri_cbatch_sync, the parts' lists merged per query on the device by (value, docID, source ascending), the value
+ * reversed when descending; a docID that several sources deliver is listed once per source, older source first, as tri_cbatch_ranked treats equal scores;
+ * counts[q] = min(sum of the parts' counts, topk).  TRI_ERR_INVALID, naming the part, nothing written: a part has no order, the parts differ in topk or in
+ * descending (each part's column is its own).  A collection none of whose parts has an order runs as it always did.
+ * tri_dev_get_option "order_last_us" (read-only): the device time of the last ordered run's selection and merge kernels, read at tri_batch_sync. */
+#define TRI_ORDER_MAX_TOPK 256 /* == TOPK_MAX */
+typedef struct tri_order {
+        tri_column *column;
+        uint32_t topk;       /* 1 .. TRI_ORDER_MAX_TOPK */
+        uint32_t descending; /* != 0: highest value first (ties still go to the lower docID) */
+        uint32_t reserved;   /* 0 */
+} tri_order;
+int tri_batch_set_order(tri_batch *, const tri_order *spec /* NULL: remove */);
+int tri_batch_ordered(tri_batch *, uint32_t *docids /* [nq][topk] */, uint32_t *values /* [nq][topk] */, uint32_t *counts /* [nq] */);
+/* (tri_cbatch_ordered is declared with the collection's calls below) */
 
 /* ---- postings decode (codec seam) -----------------------------------------------------------------
  * Replaces Codecs::PostingsListIterator::next() driven to exhaustion (google_codec.cpp:777-819,
@@ -656,6 +694,8 @@ int tri_cbatch_docset(tri_cbatch *, size_t q, uint32_t *out, size_t cap, size_t 
 int tri_cbatch_ranked(tri_cbatch *, uint32_t *docids /* [nq][topk] */, double *scores /* [nq][topk] */, uint32_t *counts /* [nq] */);
 /* facet k's rows over the collection ("facet counts" above): the parts' rows widened and summed */
 int tri_cbatch_facets(tri_cbatch *, size_t k, uint64_t *counts /* [nq][nbuckets_k + 1]: the parts' rows summed */, size_t cap);
+/* the ordered rows over the collection ("order by a column" above; exec.h:12-23): the parts' lists merged on the device */
+int tri_cbatch_ordered(tri_cbatch *, uint32_t *docids /* [nq][topk] */, uint32_t *values /* [nq][topk] */, uint32_t *counts /* [nq] */);
 int tri_cbatch_matched_terms(tri_cbatch *, size_t q, uint32_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos);
 int tri_cbatch_matched_terms_wide(tri_cbatch *, size_t q, uint64_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos);
 int tri_cbatch_matched_payloads(tri_cbatch *, size_t q, uint8_t *lens, uint64_t *payloads, size_t cap, size_t *n);

@@ -281,3 +281,31 @@ struct DevFacets { // passed to the kernel BY VALUE: a run already queued keeps 
         uint32_t lds_off[FACETS_MAX + 1];   // facet k's first counter in a workgroup's LDS row; [n] = per_query
         uint32_t n, per_query;              // facets; counters per query (all facets: sum of nb + 1)
 };
+
+// ---- order by a column (k_order.hpp; tri_batch_set_order): per query the first topk documents of its docID set by (column value, docID).  One 64-bit key per
+//      match — (descending ? ~value : value) << 32 | docID, smaller is better, distinct within one source — so the selection is "the K smallest u64".  A task's
+//      best keys go ascending into its partial list (list t of the batch's list block: ORDER lists of topk keys and a length each); k_order_merge folds a query's
+//      lists into its row of the row block ([caller query][topk] keys and a count each), in rounds of at most ORDER_FANIN lists
+constexpr uint32_t ORDER_MAX_TOPK = TOPK_MAX;      // == TRI_ORDER_MAX_TOPK
+constexpr uint32_t ORDER_WG = 256;                 // threads of a workgroup of k_order (a workgroup per task) and of k_order_merge (a workgroup per group of lists)
+constexpr uint32_t ORDER_WAVES = ORDER_WG / 64;    // each wave of k_order selects on its own, in a candidate buffer of its own
+constexpr uint32_t ORDER_TILE = 64;                // documents a wave offers per step: one per lane
+constexpr uint32_t ORDER_BUF = 2 * ORDER_MAX_TOPK;  // keys of a wave's buffer: the best topk it held at the last prune and the newcomers since (4 waves: 16 KB of LDS)
+constexpr uint32_t ORDER_PRUNE_AT = ORDER_BUF - ORDER_TILE; // a buffer of more keys has no room for another step's newcomers: it is pruned to its best topk
+constexpr uint32_t ORDER_UNROLL = 4;               // steps whose gathers from the column are requested together (a wave's stride through a segment: ORDER_UNROLL tiles)
+constexpr uint32_t ORDER_FANIN = 32;               // lists one group of k_order_merge folds: a query of more tasks takes another round (rank counting is quadratic in the lists)
+struct DevOrder { // passed to the kernel BY VALUE: a run already queued keeps the spec it was launched with
+        const uint32_t *values; // the column (tri_column): values[d] = the attribute of docID d
+        uint32_t ndocs;         // entries of the column (docs_cnt + 1): a docID at or past it is never read
+        uint32_t topk;          // 1 .. ORDER_MAX_TOPK
+        uint32_t flip;          // descending ? 0xffffffff : 0 — XORed into the value on its way into and out of a key
+};
+// a group of k_order_merge: lists [first, first + n) of the source block folded into list / row `dst` of the destination block
+struct DevOrderGroup {
+        uint32_t first, n, dst, reserved;
+};
+// a source block of k_order_merge: lists of topk ascending keys and their lengths (a batch's partial lists; a collection's merge: one per part, its rows)
+struct DevOrderLists {
+        const uint64_t *keys;   // [list][topk]
+        const uint32_t *counts; // [list]
+};

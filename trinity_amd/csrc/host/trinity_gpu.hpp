@@ -16,6 +16,7 @@
 #include "../../../include/trinity_hip.h"
 #include "google_encoder.hpp"
 #include "facet_rows.hpp"
+#include "order_rows.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -431,6 +432,7 @@ namespace trinity_amd {
         };
 
         struct FacetCounter;
+        struct ColumnOrder;
         struct MatchedIndexDocumentsFilter { // matches.h:139-185
                 virtual void consider(const matched_document &) {} // default execution mode
                 virtual void consider(const docid_t) {}
@@ -446,6 +448,8 @@ namespace trinity_amd {
                 // A filter that counts its documents by per-document columns (FacetCounter below) says so here: a DocumentsOnly exec_query binds it to the source it
                 // runs against and, unless the counter asks for the replay, has the device count (tri_batch_set_facets) and replays no match.  nullptr: every other filter.
                 virtual FacetCounter *facet_counter() { return nullptr; }
+                // ... and one that lists its first K documents by a per-document column (ColumnOrder below): bound and run the same way (tri_batch_set_order)
+                virtual ColumnOrder *column_order() { return nullptr; }
                 virtual ~MatchedIndexDocumentsFilter() = default;
         };
 
@@ -895,6 +899,71 @@ namespace trinity_amd {
                 }
         };
 
+        // The application's consider(id) / consider(ids, cnt) when it lists the first K matches by an attribute — (value ascending, docID ascending), or descending:
+        // (value descending, docID ascending); order_rows.hpp — and the device form of the same: a DocumentsOnly exec_query recognises the filter (column_order())
+        // and, with device == true, sets the order on its batch and reads the row back (tri_batch_ordered) instead of delivering the docID set; device = false keeps
+        // the replay through consider(), for comparison.  columns: one per source the filter may run against (a collection: one per source); exec_query binds it first.
+        struct ColumnOrder : public MatchedIndexDocumentsFilter {
+                std::vector<const DeviceColumn *> columns; // one per source
+                uint32_t topk;
+                bool descending, device;
+                const DeviceColumn *bound{nullptr};
+                std::vector<uint64_t> keys; // the first topk so far, ascending (order_rows::key)
+
+                ColumnOrder(std::vector<const DeviceColumn *> cols, const uint32_t k, const bool desc = false, const bool onDevice = true)
+                    : columns(std::move(cols)), topk{k}, descending{desc}, device{onDevice} {
+                        if (topk < 1 || topk > TRI_ORDER_MAX_TOPK)
+                                throw invalid_argument("ColumnOrder: topk 1 .. TRI_ORDER_MAX_TOPK");
+                }
+                ColumnOrder *column_order() override { return this; }
+                void bind(IndexSource *src) {
+                        bound = nullptr;
+                        for (const DeviceColumn *c : columns)
+                                if (c && c->source() == src)
+                                        bound = c;
+                        if (!bound)
+                                throw invalid_argument("ColumnOrder: no column of the source the query runs against");
+                }
+                void consider(const docid_t id) override { consider(&id, 1); }
+                void consider(const docid_t *ids, const size_t cnt) override {
+                        if (!bound)
+                                throw invalid_argument("ColumnOrder: not bound to a source (exec_query binds it)");
+                        order_rows::offer(keys, bound->values().data(), bound->values().size(), topk, descending, ids, cnt);
+                }
+                // the device form: the spec for tri_batch_set_order ...
+                tri_order spec() const { return tri_order{bound->handle(), topk, descending ? 1u : 0u, 0u}; }
+                // ... and the row of the batch's query q merged into the list
+                void read(tri_batch *b, const size_t q, const size_t nq) {
+                        std::vector<uint32_t> d(nq * topk), v(nq * topk), c(nq);
+                        check(tri_batch_ordered(b, d.data(), v.data(), c.data()));
+                        std::vector<uint64_t> row;
+                        for (uint32_t i = 0; i < c[q]; ++i)
+                                row.push_back(uint64_t(descending ? ~v[q * topk + i] : v[q * topk + i]) << 32 | d[q * topk + i]);
+                        keys = order_rows::blend({keys, row}, topk);
+                }
+                std::vector<std::pair<docid_t, uint32_t>> list() const { // (docID, value), best first
+                        std::vector<std::pair<docid_t, uint32_t>> out;
+                        for (const uint64_t x : keys)
+                                out.emplace_back(order_rows::docid_of(x), order_rows::value_of(x, descending));
+                        return out;
+                }
+                // The lists of a collection's sources (exec_query's collection form, one ColumnOrder per source, oldest first) blended into one by (value, docID,
+                // source): a docID of several sources is listed once per source.  The host form of tri_cbatch_ordered.
+                static std::vector<std::pair<docid_t, uint32_t>> blend(const std::vector<std::unique_ptr<ColumnOrder>> &parts) {
+                        std::vector<std::vector<uint64_t>> lists;
+                        for (const auto &p : parts) {
+                                if (p->topk != parts[0]->topk || p->descending != parts[0]->descending)
+                                        throw invalid_argument("ColumnOrder::blend: the parts disagree in topk or direction");
+                                lists.push_back(p->keys);
+                        }
+                        std::vector<std::pair<docid_t, uint32_t>> out;
+                        if (!parts.empty())
+                                for (const uint64_t x : order_rows::blend(lists, parts[0]->topk))
+                                        out.emplace_back(order_rows::docid_of(x), order_rows::value_of(x, parts[0]->descending));
+                        return out;
+                }
+        };
+
         // ------------------------------------------------------------------ execution
         struct BatchDeleter {
                 void operator()(tri_batch *b) const { tri_batch_destroy(b); }
@@ -1186,6 +1255,18 @@ namespace trinity_amd {
                                 auto b = run_batch(src, {root}, flags, 0, nullptr, onDevice ? std::vector<tri_filter *>{onDevice} : std::vector<tri_filter *>{},
                                                    [&](tri_batch *bt, const std::vector<uint32_t> &, const std::vector<tri_query> &) { check(tri_batch_set_facets(bt, specs.data(), specs.size())); });
                                 fc->read(b.get(), 0, 1);
+                                return;
+                        }
+                }
+                // ... and so does a column order
+                ColumnOrder *const co = matchesFilter ? matchesFilter->column_order() : nullptr;
+                if (co) {
+                        co->bind(src);
+                        if (co->device && (flags & unsigned(ExecFlags::DocumentsOnly)) && (!f || onDevice)) {
+                                const tri_order spec = co->spec();
+                                auto b = run_batch(src, {root}, flags, 0, nullptr, onDevice ? std::vector<tri_filter *>{onDevice} : std::vector<tri_filter *>{},
+                                                   [&](tri_batch *bt, const std::vector<uint32_t> &, const std::vector<tri_query> &) { check(tri_batch_set_order(bt, &spec)); });
+                                co->read(b.get(), 0, 1);
                                 return;
                         }
                 }

@@ -5,10 +5,11 @@
 //   for_each_segment          a query's result is the in-order concatenation of its task segments
 //   ReadBack                  THE stream rule: a result copy is enqueued on the read-back stream under the handle's lock and awaited outside it
 // The transforms between the device's layout and the caller's (mask widening, frequency-row narrowing, bitmap expansion) are host/result_rows.hpp; a collection's
-// facet rows are summed by host/facet_rows.hpp.
+// facet rows are summed by host/facet_rows.hpp; an ordered row's keys are split into docIDs and values by host/order_rows.hpp.
 #pragma once
 #include "host/result_rows.hpp"
 #include "host/facet_rows.hpp"
+#include "host/order_rows.hpp"
 
 namespace {
         // what every result call opens with: its arguments, the flags the batch must have been created with, and (must_sync) that its results stand
@@ -454,6 +455,33 @@ extern "C" int tri_batch_facets(tri_batch *b, size_t k, uint32_t *counts, size_t
         return ReadBack(b->dev).copy(counts, b->d_facet_rows + b->facets.rows_off[k], need * 4).done();
 }
 
+namespace {
+        // rows of topk keys and their counts, read back in two copies and split into the caller's arrays
+        int ordered_rows(tri_dev *dev, const uint64_t *d_keys, const uint32_t *d_counts, const size_t nq, const size_t k, const bool descending, uint32_t *docids, uint32_t *values,
+                         uint32_t *counts) {
+                Pinned<uint64_t> pinned; // (the keys are staged in a pinned block of the handle's pool; pageable memory where none is to be had)
+                std::unique_ptr<uint64_t[]> pageable;
+                uint64_t *keys = pinned.alloc(dev, nq * k * 8 + 8);
+                if (!keys)
+                        keys = (pageable = std::make_unique<uint64_t[]>(nq * k + 1)).get();
+                if (const int rc = ReadBack(dev).copy(keys, d_keys, nq * k * 8).copy(counts, d_counts, nq * 4).done())
+                        return rc;
+                order_rows::split(keys, counts, nq, k, descending, docids, values);
+                return TRI_OK;
+        }
+} // namespace
+
+// order by a column (tri_batch_set_order; k_order.hpp): every query's first topk documents by (value, docID) — the rows lie in caller query order
+extern "C" int tri_batch_ordered(tri_batch *b, uint32_t *docids, uint32_t *values, uint32_t *counts) {
+        if (const int rc = read_check(b, docids && values && counts, __func__, 0, false))
+                return rc;
+        if (!b->order_on)
+                return fail(TRI_ERR_INVALID, "%s: no order is set (tri_batch_set_order)", __func__);
+        if (!b->synced || !b->order_done)
+                return fail(TRI_ERR_INVALID, "%s: tri_batch_sync first (a run that follows tri_batch_set_order)", __func__);
+        return ordered_rows(b->dev, b->order_keys(b->order_lists), b->order_counts(b->order_lists), b->nq, b->order.topk, b->order.flip != 0, docids, values, counts);
+}
+
 // ---- a collection batch's results: merged on the device by tri_cbatch_run (match counts add up, top-K lists merge K-way)
 extern "C" int tri_cbatch_match_counts(tri_cbatch *c, uint64_t *counts) {
         if (const int rc = cbatch_check(c, counts != nullptr, __func__))
@@ -568,4 +596,13 @@ extern "C" int tri_cbatch_facets(tri_cbatch *c, size_t k, uint64_t *counts, size
         }
         std::copy(sum.begin(), sum.end(), counts);
         return TRI_OK;
+}
+
+// a collection's ordered rows (k_order_merge<true>, queued by tri_cbatch_sync): the first topk (docID, value) pairs of every query over all parts
+extern "C" int tri_cbatch_ordered(tri_cbatch *c, uint32_t *docids, uint32_t *values, uint32_t *counts) {
+        if (const int rc = cbatch_check(c, docids && values && counts, __func__))
+                return rc;
+        if (!c->ordered)
+                return fail(TRI_ERR_INVALID, "%s: %s", __func__, c->order_why.c_str());
+        return ordered_rows(c->parts[0]->ix->dev, c->d_order_keys, c->d_order_counts, c->parts[0]->nq, c->order_k, c->parts[0]->order.flip != 0, docids, values, counts);
 }

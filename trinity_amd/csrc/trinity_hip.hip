@@ -75,6 +75,7 @@ struct tri_dev {
         tri_options opt;
         uint64_t rich_write_last_us = 0, rank_last_us = 0; // the last ranked batch's WRITE pass and rank pass (tri_dev_get_option, read-only)
         uint64_t facet_last_us = 0;                        // the last faceted run's row zeroing + k_facet (read at tri_batch_sync)
+        uint64_t order_last_us = 0;                        // the last ordered run's k_order + k_order_merge rounds (read at tri_batch_sync)
         uint64_t crank_merge_last_us = 0;                  // the last ranked collection's merge of its parts' lists (k_rank_merge_sources)
         int refs = 0;         // indexes and batches alive on this handle ...
         bool closing = false; // ... tri_dev_close with some left: the handle goes with the last of them
@@ -424,6 +425,12 @@ struct tri_batch : BatchPlan {
         // counters, zeroed and recounted by every run) and the events around the run's zeroing + kernel (option facet_last_us)
         Pooled<uint32_t> d_facet_rows;
         PooledEvent facet_ev[2];
+        // tri_batch_set_order (k_order.hpp): ONE pooled block — the tasks' partial lists, the merge's two intermediate levels and the rows ([caller query][topk] keys),
+        // then a length per list and row —, the merge's groups (they depend on the plan alone: laid out by the first setter) and the events around the run's kernels
+        // (option order_last_us)
+        Pooled<uint64_t> d_order_block;
+        DevMem<DevOrderGroup> d_order_groups;
+        PooledEvent order_ev[2];
         // ---- VIEWS: plain pointers into the buffers above, released with them
         // a section of the plan (a Span of BatchPlan: planner_types.hpp, for_each_section) on the device — the block's copy opens the arena
         template <class T>
@@ -470,6 +477,17 @@ struct tri_batch : BatchPlan {
         DevFacets facets{};                       // the specs; facets.n == 0: none
         size_t facet_counters = 0;                // counters of d_facet_rows
         bool facet_ran = false, facet_done = false; // the last run counted with the specs that stand; ... and tri_batch_sync has awaited it
+        struct OrderRound {
+                uint32_t first_group, ngroups; // of d_order_groups
+        };
+        DevOrder order{};                          // the spec as the kernel takes it (the column by reference); order_on: one stands
+        bool order_on = false, order_laid_out = false;
+        std::vector<OrderRound> order_rounds;      // round r reads the tasks' lists (r == 0) or level (r - 1) & 1, and writes rows and level r & 1
+        size_t order_level[2] = {0, 0};            // lists of the two intermediate levels
+        size_t order_lists = 0;                    // lists of d_order_block ahead of its rows: tasks + both levels
+        bool order_ran = false, order_done = false; // the last run selected with the spec that stands; ... and tri_batch_sync has awaited it
+        uint64_t *order_keys(const size_t list) const { return d_order_block.get() + list * order.topk; }
+        uint32_t *order_counts(const size_t list) const { return reinterpret_cast<uint32_t *>(d_order_block.get() + (order_lists + nq) * order.topk) + list; }
         std::vector<uint32_t> h_prog;
         std::vector<tri_query> h_queries;
         tri_batch_info info{};
@@ -503,6 +521,7 @@ struct tri_batch : BatchPlan {
 #include "k_tree_wide.hpp"
 #include "k_perc.hpp"
 #include "k_facet.hpp"
+#include "k_order.hpp"
 #include "k_commit.hpp"
 #include "k_lencode.hpp"
 #include "filtered_kernels.hpp"
@@ -608,6 +627,10 @@ extern "C" int tri_dev_get_option(tri_dev *d, const char *name, uint64_t *value)
         }
         if (!strcmp(name, "facet_last_us")) { // (... of the last faceted run's row zeroing and k_facet, tri_batch_sync)
                 *value = d->facet_last_us;
+                return TRI_OK;
+        }
+        if (!strcmp(name, "order_last_us")) { // (... of the last ordered run's k_order and k_order_merge rounds, tri_batch_sync)
+                *value = d->order_last_us;
                 return TRI_OK;
         }
         if (!strcmp(name, "crank_merge_last_us")) { // (... and of the last ranked collection's merge kernel, tri_cbatch_sync)
@@ -1821,6 +1844,38 @@ static int run_facets(tri_batch *b) {
         return TRI_OK;
 }
 
+// tri_batch_set_order: every task's best keys selected into its partial list, then a query's lists folded into its row, round after round — behind the kernels that
+// complete the docID sets (k_order reads the device-side task counts), ahead of the run's end event.  A batch without an order enqueues nothing
+static int run_order(tri_batch *b) {
+        b->order_ran = b->order_done = false;
+        if (!b->order_on)
+                return TRI_OK;
+        tri_dev *dev = b->dev;
+        const uint32_t k = b->order.topk;
+        const size_t ntasks = b->tasks.size(), rows = b->order_lists;
+        HIP_TRY(hipEventRecord(b->order_ev[0], dev->stream));
+        if (b->tasks.empty()) { // (no query has a task: every row is empty)
+                HIP_TRY(hipMemsetAsync(b->order_keys(rows), 0, b->nq * (size_t)k * 8, dev->stream));
+                HIP_TRY(hipMemsetAsync(b->order_counts(rows), 0, b->nq * 4, dev->stream));
+        } else {
+                hipLaunchKernelGGL(k_order, dim3((uint32_t)ntasks), dim3(ORDER_WG), 0, dev->stream, (const DevQuery *)b->dev_at(b->plan), (const DevTask *)b->dev_at(b->tasks),
+                                   (const uint32_t *)b->d_counts, (const uint32_t *)b->d_out, b->order, b->order_keys(0), b->order_counts(0));
+                HIP_TRY(hipGetLastError());
+                const size_t level_at[2] = {ntasks, ntasks + b->order_level[0]};
+                for (size_t r = 0; r < b->order_rounds.size(); ++r) {
+                        const tri_batch::OrderRound &round = b->order_rounds[r];
+                        const size_t from = r ? level_at[(r - 1) & 1] : 0, to = level_at[r & 1];
+                        hipLaunchKernelGGL(k_order_merge<false>, dim3(round.ngroups), dim3(ORDER_WG), 0, dev->stream, (const DevOrderLists *)nullptr,
+                                           DevOrderLists{b->order_keys(from), b->order_counts(from)}, (const DevOrderGroup *)b->d_order_groups + round.first_group, 0u, k, b->order_keys(to),
+                                           b->order_counts(to), b->order_keys(rows), b->order_counts(rows));
+                        HIP_TRY(hipGetLastError());
+                }
+        }
+        HIP_TRY(hipEventRecord(b->order_ev[1], dev->stream));
+        b->order_ran = true;
+        return TRI_OK;
+}
+
 extern "C" int tri_batch_run(tri_batch *b) {
         if (!b)
                 return fail(TRI_ERR_INVALID, "null batch");
@@ -1869,6 +1924,8 @@ extern "C" int tri_batch_run(tri_batch *b) {
         if (const int rc = run_query_counts(b))
                 return rc;
         if (const int rc = run_facets(b))
+                return rc;
+        if (const int rc = run_order(b))
                 return rc;
         HIP_TRY(hipEventRecord(b->ev[EV_END], dev->stream));
         return TRI_OK;
@@ -2239,6 +2296,12 @@ extern "C" int tri_batch_sync(tri_batch *b) {
                         dev->facet_last_us = (uint64_t)(ms * 1000.0f);
                 b->facet_done = true;
         }
+        if (b->order_ran) { // (both events precede EV_END)
+                float ms = 0;
+                if (hipEventElapsedTime(&ms, b->order_ev[0], b->order_ev[1]) == hipSuccess)
+                        dev->order_last_us = (uint64_t)(ms * 1000.0f);
+                b->order_done = true;
+        }
         int rc;
         if ((rc = account_matches(b)) || (rc = rich_write_pass(b)))
                 return rc;
@@ -2379,6 +2442,15 @@ struct tri_cbatch {
         std::string rank_why;
         PooledEvent rank_ev[2]; // around the merge kernel (option crank_merge_last_us)
         bool rank_timed = false;
+        // tri_cbatch_ordered (k_order_merge<true>): the merged [nq][order_k] keys and counts and the parts' {rows, counts} table, as the ranked blocks above — a run
+        // finds the collection ordered when every part carries an order of the same topk and direction; order_why: why a run was not
+        bool ordered = false;
+        uint32_t order_k = 0;
+        DevMem<uint64_t> d_order_keys;
+        DevMem<uint32_t> d_order_counts;
+        DevMem<DevOrderLists> d_order_src;
+        std::vector<DevOrderLists> order_src;
+        std::string order_why;
         bool ran = false, synced = false;
         ~tri_cbatch() {
                 if (dev)
@@ -2694,6 +2766,79 @@ static int cbatch_rank_merge(tri_cbatch *c) {
         return TRI_OK;
 }
 
+// tri_cbatch_ordered, at tri_cbatch_run: is the collection ordered for this run?  Every part carries an order, all of one topk and direction (each part's column
+// is its own).  If so the merged block exists at that topk and the parts' table goes to the device on the engine stream, ahead of the merge tri_cbatch_sync
+// queues.  If not — also: no part has an order — nothing is allocated, copied or launched.
+static int cbatch_order_prepare(tri_cbatch *c) {
+        c->ordered = false;
+        const tri_batch *p0 = c->parts[0];
+        bool any = false;
+        for (const tri_batch *p : c->parts)
+                any |= p->order_on;
+        if (!any) {
+                c->order_why = "no order is set on the parts (tri_batch_set_order)";
+                return TRI_OK;
+        }
+        char why[160];
+        for (size_t i = 0; i < c->parts.size(); ++i) {
+                const tri_batch *p = c->parts[i];
+                if (!p->order_on)
+                        snprintf(why, sizeof why, "part %zu has no order (tri_batch_set_order)", i);
+                else if (p->order.topk != p0->order.topk)
+                        snprintf(why, sizeof why, "part %zu's order has topk %u, part 0's has %u", i, p->order.topk, p0->order.topk);
+                else if (p->order.flip != p0->order.flip)
+                        snprintf(why, sizeof why, "part %zu's order is %s, part 0's is not", i, p->order.flip ? "descending" : "ascending");
+                else
+                        continue;
+                c->order_why = why;
+                return TRI_OK;
+        }
+        tri_dev *dev = p0->ix->dev;
+        const size_t nq = p0->nq, n = c->parts.size(), k = p0->order.topk;
+        DevLock dev_lock(dev->mu);
+        HIP_TRY(hipSetDevice(dev->device));
+        if (c->order_k != k) { // (no merge of an earlier run is in flight: tri_cbatch_sync waits for the one it queues)
+                c->d_order_keys.reset();
+                c->d_order_counts.reset();
+                c->order_k = 0;
+                HIP_TRY(c->d_order_keys.alloc((nq * k + 1) * 8));
+                HIP_TRY(c->d_order_counts.alloc((nq + 1) * 4));
+                c->order_k = (uint32_t)k;
+        }
+        if (!c->d_order_src)
+                HIP_TRY(c->d_order_src.alloc(n * sizeof(DevOrderLists)));
+        c->order_src.resize(n);
+        for (size_t i = 0; i < n; ++i)
+                c->order_src[i] = {c->parts[i]->order_keys(c->parts[i]->order_lists), c->parts[i]->order_counts(c->parts[i]->order_lists)};
+        HIP_TRY(hipMemcpyAsync(c->d_order_src, c->order_src.data(), n * sizeof(DevOrderLists), hipMemcpyHostToDevice, dev->stream));
+        c->ordered = true;
+        return TRI_OK;
+}
+
+// ... and at tri_cbatch_sync, behind the last part's own sync: a workgroup per query folds the parts' rows into the collection's
+static int cbatch_order_merge(tri_cbatch *c) {
+        if (!c->ordered)
+                return TRI_OK;
+        for (size_t i = 0; i < c->parts.size(); ++i) { // (an order replaced or removed between the run and the sync: the part selected nothing into the table's block)
+                const tri_batch *p = c->parts[i];
+                if (!p->order_on || !p->order_done || p->order_keys(p->order_lists) != c->order_src[i].keys) {
+                        c->ordered = false;
+                        c->order_why = "part " + std::to_string(i) + "'s order was replaced after tri_cbatch_run";
+                        return TRI_OK;
+                }
+        }
+        tri_dev *dev = c->parts[0]->ix->dev;
+        const uint32_t nq = (uint32_t)c->parts[0]->nq;
+        if (!nq)
+                return TRI_OK;
+        DevLock dev_lock(dev->mu);
+        HIP_TRY(hipSetDevice(dev->device));
+        hipLaunchKernelGGL(k_order_merge<true>, dim3(nq), dim3(ORDER_WG), 0, dev->stream, (const DevOrderLists *)c->d_order_src, DevOrderLists{nullptr, nullptr},
+                           (const DevOrderGroup *)nullptr, (uint32_t)c->parts.size(), c->order_k, (uint64_t *)nullptr, (uint32_t *)nullptr, c->d_order_keys.get(), c->d_order_counts.get());
+        HIP_TRY(hipGetLastError());
+        return TRI_OK;
+}
+
 extern "C" int tri_cbatch_run(tri_cbatch *c) {
         if (!c)
                 return fail(TRI_ERR_INVALID, "null collection batch");
@@ -2710,7 +2855,9 @@ extern "C" int tri_cbatch_run(tri_cbatch *c) {
         }
         c->ran = true;
         c->synced = false;
-        return cbatch_rank_prepare(c);
+        if (const int rc = cbatch_rank_prepare(c))
+                return rc;
+        return cbatch_order_prepare(c);
 }
 
 extern "C" int tri_cbatch_sync(tri_cbatch *c) {
@@ -2720,6 +2867,8 @@ extern "C" int tri_cbatch_sync(tri_cbatch *c) {
                 if (int rc = tri_batch_sync(p))
                         return rc;
         if (int rc = cbatch_rank_merge(c)) // (a part's list stands once its own sync has run the WRITE and rank passes: behind the last of them)
+                return rc;
+        if (int rc = cbatch_order_merge(c))
                 return rc;
         HIP_TRY(hipStreamSynchronize(c->parts[0]->ix->dev->stream));
         if (c->rank_timed) {
@@ -2887,6 +3036,7 @@ extern "C" int tri_gather_results(tri_batch *b, tri_comm *c, void *counts_all, v
 #include "write_side.hpp"
 #include "isect_side.hpp"
 #include "facet_side.hpp"
+#include "order_side.hpp"
 #include "perc_side.hpp"
 
 #ifdef TRI_PROF

@@ -46,6 +46,10 @@ class TriFacet(C.Structure):
     _fields_ = [("column", C.c_void_p), ("nbuckets", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TriOrder(C.Structure):
+    _fields_ = [("column", C.c_void_p), ("topk", C.c_uint32), ("descending", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class TriIsectRequest(C.Structure):
     _fields_ = [("ngroups", C.c_uint32), ("reserved", C.c_uint32), ("stopwords_mask", C.c_uint64)]
 
@@ -155,6 +159,7 @@ ABI_SYMBOLS = [
     "tri_perc_create", "tri_perc_query_status", "tri_perc_set_enabled", "tri_perc_get_info", "tri_perc_destroy", "tri_perc_match",
     "tri_perc_result_pairs", "tri_perc_result_doc_counts", "tri_perc_result_get_info", "tri_perc_result_destroy",
     "tri_column_create", "tri_column_destroy", "tri_batch_set_facets", "tri_batch_facets", "tri_cbatch_facets",
+    "tri_batch_set_order", "tri_batch_ordered", "tri_cbatch_ordered",
 ]  # fmt: skip
 
 _hip = None
@@ -249,6 +254,9 @@ def hip_lib():
     L.tri_batch_set_facets.argtypes = [vp, C.POINTER(TriFacet), C.c_size_t]
     L.tri_batch_facets.argtypes = [vp, C.c_size_t, vp, C.c_size_t]
     L.tri_cbatch_facets.argtypes = [vp, C.c_size_t, vp, C.c_size_t]
+    L.tri_batch_set_order.argtypes = [vp, C.POINTER(TriOrder)]
+    L.tri_batch_ordered.argtypes = [vp, vp, vp, vp]
+    L.tri_cbatch_ordered.argtypes = [vp, vp, vp, vp]
     L.tri_isect_run.argtypes = [vp, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
     L.tri_isect_status.argtypes = [vp, vp]
     L.tri_isect_results.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -810,6 +818,7 @@ class Filter:
 
 FACETS_MAX = 4  # TRI_FACETS_MAX
 FACET_MAX_BUCKETS = 65536  # TRI_FACET_MAX_BUCKETS
+ORDER_MAX_TOPK = 256  # TRI_ORDER_MAX_TOPK
 
 
 class Column:
@@ -893,6 +902,27 @@ class Batch:
         out = np.zeros((self.nq, nb + 1), dtype=np.uint32)
         _check(hip_lib().tri_batch_facets(self.h, k, out.ctypes.data, out.size))
         return out
+
+    def set_order(self, column, topk, descending=False):
+        """Order by a column for the runs that follow (tri_batch_set_order): every run then selects, on the device, each query's first topk documents by
+        (column value, docID) — descending: highest value first, ties still to the lower docID; results: ordered().  The batch keeps the Column referenced."""
+        spec = TriOrder(column.h if column is not None else None, int(topk), 1 if descending else 0, 0)
+        _check(hip_lib().tri_batch_set_order(self.h, C.byref(spec)))
+        self._order = (column, int(topk), bool(descending))
+
+    def clear_order(self):
+        """Remove the order (tri_batch_set_order with NULL): later runs launch what they did before one was set."""
+        _check(hip_lib().tri_batch_set_order(self.h, None))
+        self._order = None
+
+    def ordered(self):
+        """After sync(): (docids u32[nq, topk], values u32[nq, topk], counts u32[nq]) in caller query order — row q holds the first counts[q] = min(matches, topk)
+        documents of query q's docID set by (value, docID), values[q, i] the column's value of docids[q, i]; entries past counts[q] are zero (tri_batch_ordered)."""
+        spec = getattr(self, "_order", None)
+        k = spec[1] if spec else 1  # (no order: the library refuses)
+        d, v, c = np.zeros((self.nq, k), dtype=np.uint32), np.zeros((self.nq, k), dtype=np.uint32), np.zeros(self.nq, dtype=np.uint32)
+        _check(hip_lib().tri_batch_ordered(self.h, d.ctypes.data, v.ctypes.data, c.ctypes.data))
+        return d, v, c
 
     def set_ranker(self, topk, freq_cap=65535, adjacency=0.0, weights=None):
         """FLAG_MATCHED_TERMS batches: rank every query's matches on the device for the runs that follow (tri_batch_set_ranker, TRI_RANK_PROXIMITY):
@@ -1136,6 +1166,15 @@ class CollectionBatch:
         out = np.zeros((self.nq, nb + 1), dtype=np.uint64)
         _check(hip_lib().tri_cbatch_facets(self.h, k, out.ctypes.data, out.size))
         return out
+
+    def ordered(self):
+        """After sync(): (docids, values, counts) over the collection — the parts' ordered lists merged per query by (value, docID, source), cut at topk
+        (tri_cbatch_ordered); every part must carry an order of the same topk and direction."""
+        ks = [getattr(p, "_order", None) for p in self.parts]
+        k = max([o[1] for o in ks if o] or [1])  # (parts that disagree, or none ordered: the library refuses)
+        d, v, c = np.zeros((self.nq, k), dtype=np.uint32), np.zeros((self.nq, k), dtype=np.uint32), np.zeros(self.nq, dtype=np.uint32)
+        _check(hip_lib().tri_cbatch_ordered(self.h, d.ctypes.data, v.ctypes.data, c.ctypes.data))
+        return d, v, c
 
     def _query_width(self, q):
         """(terms, nterms) of query q: those of the first part that reports it (the parts agree, or the row calls refuse)."""
