@@ -45,7 +45,10 @@ extern "C" {
                                 within 9: tri_column_create / tri_column_destroy / tri_batch_set_facets / tri_batch_facets / tri_cbatch_facets, read-only option facet_last_us
                                 (facet counts: per query a histogram of its docID set over per-document columns, counted on the device; no existing struct grew);
                                 within 9: tri_batch_set_order / tri_batch_ordered / tri_cbatch_ordered, read-only option order_last_us
-                                (order by a column: per query the first topk documents of its docID set by a column's value, selected on the device; no existing struct grew) */
+                                (order by a column: per query the first topk documents of its docID set by a column's value, selected on the device; no existing struct grew);
+                                within 9: tri_batch_set_stats / tri_batch_stats / tri_cbatch_stats, read-only option stats_last_us
+                                (stats of a column: per query and bucket the count, sum, min and max of a value column over the docID set, aggregated on the device; no existing
+                                struct grew) */
 
 /* status codes */
 #define TRI_OK 0
@@ -365,6 +368,48 @@ typedef struct tri_order {
 int tri_batch_set_order(tri_batch *, const tri_order *spec /* NULL: remove */);
 int tri_batch_ordered(tri_batch *, uint32_t *docids /* [nq][topk] */, uint32_t *values /* [nq][topk] */, uint32_t *counts /* [nq] */);
 /* (tri_cbatch_ordered is declared with the collection's calls below) */
+
+/* ---- stats of a column per query and bucket ---------------------------------------------------------
+ * What an application adds up in MatchedIndexDocumentsFilter::consider(id) / consider(ids, cnt) (exec.h:12-23: "just count or collect documents matching a
+ * query") beside the facet counts: the price range of the matches, the average rating per category, revenue per brand, the newest timestamp per tenant.  A
+ * stat names a VALUE column and, optionally, a GROUP column of nbuckets (tri_column_create above: both belong to the batch's index); a batch that names stats
+ * aggregates, at the end of every run and on the device, each query's docID set into a row of records per stat: 20 bytes a (query, bucket) cross PCIe instead
+ * of the docID set.
+ *
+ * The contract (exec.h:12-23 is the consumer it stands for): for every document d of query q's docID set — exactly what tri_batch_docset delivers: the index's
+ * masked set and q's filter are applied, there is no second rule — the record of bucket g = min(group[d], nbuckets) takes the document: count += 1,
+ * sum += value[d] (an exact u64: one source cannot overflow it), min = min(min, value[d]), max = max(max, value[d]); values compare UNSIGNED.  A grouped row has
+ * nbuckets + 1 records, the last is the overflow bucket, as in tri_batch_facets — its counts equal tri_batch_facets of the same column and nbuckets, integer for
+ * integer.  Without a group column (group NULL, nbuckets 0) the row is the single record 0.  An empty bucket reads count 0, sum 0, min 0xffffffff, max 0.  A docID
+ * at or past a column's end is never read (group: overflow, value: 0xffffffff); tri_column_create makes it unreachable.
+ * tri_batch_set_stats (exec.h:12-23): after tri_batch_create, before a run, again between runs; n == 0 clears; columns are stored by reference and kept alive
+ * while the batch may run.  Runs already queued keep the specs they were launched with (the call waits for them before the rows they aggregate into are
+ * released).  The rows of ALL stats live in one block taken from the handle's buffer pool: nq x sum over the stats of (nbuckets + 1) x 20 bytes (+ 64 KB, the
+ * pool's smallest buffer), per stat four planes — sums, counts, mins, maxs — in caller query order: TRI_ERR_NOMEM when it cannot be had.  TRI_ERR_INVALID,
+ * nothing changed: a null value column, a column of another index, n > TRI_STATS_MAX, a group with nbuckets of 0 or above TRI_FACET_MAX_BUCKETS, no group with
+ * nbuckets != 0, reserved != 0, a batch created with TRI_FLAG_ACCUMULATED_SCORE (its one-pass queries keep no docID sets).  Stats, facets, an order and a ranker
+ * stand on one batch independently; the parts of a tri_cbatch each carry their own stats.
+ * Every later tri_batch_run initialises the block and aggregates again, on the engine stream behind the kernels that complete the docID sets (one more launch
+ * per run; a batch without stats launches nothing more); the rows stand after tri_batch_sync.
+ * tri_batch_stats (exec.h:12-23): stat k's rows for the whole batch, each output [nq][nbuckets_k + 1] in caller query order, one copy per output; a NULL output
+ * is skipped, all four NULL is invalid.  A query the planner left out, or one without matches, reads as empty records.  TRI_ERR_INVALID, nothing written: no
+ * stats set, k out of range, cap (in records) below nq * (nbuckets_k + 1), no tri_batch_sync since the last run, stats set or replaced since the last run.
+ * tri_cbatch_stats (exec.h:12-23): after tri_cbatch_sync, the parts' rows combined on the host — counts and sums added, mins and maxs folded (a docID that
+ * several sources deliver counts once per source, as tri_cbatch_docset lists it).  TRI_ERR_INVALID, naming the part, when the parts disagree in the number of
+ * stats, in stat k's nbuckets or in whether it is grouped; TRI_ERR_INVALID, naming the query and the bucket, nothing written, when a summed sum would wrap u64.
+ * tri_dev_get_option "stats_last_us" (read-only; exec.h:12-23): the device time of the last run's initialisation of the rows and aggregating kernel, read at
+ * tri_batch_sync. */
+#define TRI_STATS_MAX 4
+typedef struct tri_stat {
+        tri_column *group; /* NULL: one bucket */
+        tri_column *value;
+        uint32_t nbuckets; /* grouped: 1 .. TRI_FACET_MAX_BUCKETS, the row has nbuckets + 1 records; ungrouped: 0 */
+        uint32_t reserved; /* 0 */
+} tri_stat;
+int tri_batch_set_stats(tri_batch *, const tri_stat *stats, size_t n /* 0: clear */);
+int tri_batch_stats(tri_batch *, size_t k, uint64_t *sums, uint32_t *counts, uint32_t *mins, uint32_t *maxs /* each [nq][nbuckets_k + 1], caller query order; NULL: skipped */,
+                    size_t cap /* records */);
+/* (tri_cbatch_stats is declared with the collection's calls below) */
 
 /* ---- postings decode (codec seam) -----------------------------------------------------------------
  * Replaces Codecs::PostingsListIterator::next() driven to exhaustion (google_codec.cpp:777-819,
@@ -696,6 +741,8 @@ int tri_cbatch_ranked(tri_cbatch *, uint32_t *docids /* [nq][topk] */, double *s
 int tri_cbatch_facets(tri_cbatch *, size_t k, uint64_t *counts /* [nq][nbuckets_k + 1]: the parts' rows summed */, size_t cap);
 /* the ordered rows over the collection ("order by a column" above; exec.h:12-23): the parts' lists merged on the device */
 int tri_cbatch_ordered(tri_cbatch *, uint32_t *docids /* [nq][topk] */, uint32_t *values /* [nq][topk] */, uint32_t *counts /* [nq] */);
+/* stat k's rows over the collection ("stats of a column" above; exec.h:12-23): the parts' rows combined on the host */
+int tri_cbatch_stats(tri_cbatch *, size_t k, uint64_t *sums, uint64_t *counts, uint32_t *mins, uint32_t *maxs /* each [nq][nbuckets_k + 1]; NULL: skipped */, size_t cap /* records */);
 int tri_cbatch_matched_terms(tri_cbatch *, size_t q, uint32_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos);
 int tri_cbatch_matched_terms_wide(tri_cbatch *, size_t q, uint64_t *present, uint16_t *freq, uint16_t *positions, size_t pos_cap, size_t *npos);
 int tri_cbatch_matched_payloads(tri_cbatch *, size_t q, uint8_t *lens, uint64_t *payloads, size_t cap, size_t *n);

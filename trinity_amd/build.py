@@ -34,7 +34,7 @@ def hipcc():
 
 
 def build_hip(force=False):
-    if force or _newer(LIB_HIP, _deps(HIP_SRCS) + [os.path.join(PKG, "csrc", "host", n) for n in ("result_rows.hpp", "isect_rows.hpp", "perc_lower.hpp", "facet_rows.hpp", "order_rows.hpp")]):  # (read_side.hpp's host transforms, isect_side.hpp's replay, perc_side.hpp's lowering, read_side.hpp's sum of a collection's facet rows and split of an ordered row's keys)
+    if force or _newer(LIB_HIP, _deps(HIP_SRCS) + [os.path.join(PKG, "csrc", "host", n) for n in ("result_rows.hpp", "isect_rows.hpp", "perc_lower.hpp", "facet_rows.hpp", "order_rows.hpp", "stats_rows.hpp")]):  # (read_side.hpp's host transforms, isect_side.hpp's replay, perc_side.hpp's lowering, read_side.hpp's sum of a collection's facet rows, split of an ordered row's keys and combine of a collection's stats rows)
         cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-o", LIB_HIP] + HIP_SRCS + ["-ldl"]
         subprocess.run(cmd, check=True)
     return LIB_HIP
@@ -214,9 +214,26 @@ def build_mirror_order_test(force=False):
     return MIRROR_ORDER_BIN
 
 
+MIRROR_STATS_SRC = os.path.join(ROOT, "tests", "cpp", "host_mirror_stats_test.cpp")
+MIRROR_STATS_BIN = os.path.join(ROOT, "tests", "cpp", "host_mirror_stats_test")
+
+
+def build_mirror_stats_test(force=False):
+    """StatsCounter of the operator surface (csrc/host/trinity_gpu.hpp: aggregated on the device through tri_batch_set_stats / tri_batch_stats, and through the replay)
+    compiled into its driver; in-tree, so that it travels to the GPU box, where tests/test_host_mirror_stats.py runs it."""
+    deps = [MIRROR_STATS_SRC, os.path.join(PKG, "csrc", "host", "trinity_gpu.hpp"), os.path.join(PKG, "csrc", "host", "stats_rows.hpp"), os.path.join(PKG, "csrc", "host", "google_encoder.hpp"),
+            os.path.join(ROOT, "include", "trinity_hip.h")]  # fmt: skip
+    if force or _newer(MIRROR_STATS_BIN, deps):
+        build_hip()
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", MIRROR_STATS_BIN, MIRROR_STATS_SRC, "-L" + PKG, "-ltrinity_hip", "-Wl,-rpath,$ORIGIN/../../trinity_amd"]
+        subprocess.run(cmd, check=True)
+    return MIRROR_STATS_BIN
+
+
 def build_all(force=False):
     return (build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force), build_mirror_wide_terms_test(force),
-            build_mirror_hits_test(force), build_mirror_rank_test(force), build_mirror_collection_test(force), build_mirror_isect_test(force), build_mirror_perc_test(force), build_mirror_facets_test(force), build_mirror_order_test(force))
+            build_mirror_hits_test(force), build_mirror_rank_test(force), build_mirror_collection_test(force), build_mirror_isect_test(force), build_mirror_perc_test(force), build_mirror_facets_test(force), build_mirror_order_test(force),
+            build_mirror_stats_test(force))
 
 
 def kernels_stamp():

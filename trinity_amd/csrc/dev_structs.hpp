@@ -309,3 +309,25 @@ struct DevOrderLists {
         const uint64_t *keys;   // [list][topk]
         const uint32_t *counts; // [list]
 };
+
+// ---- stats of a column per query and bucket (k_stats.hpp; tri_batch_set_stats): a stat names a value column and, optionally, a group column of nbuckets.  For
+//      every document d of the query's docID set the record of bucket min(group[d], nbuckets) — the last is the overflow bucket; no group column: the one record 0 —
+//      takes the document: count += 1, sum += value[d] (u64), min and max folded (unsigned).  The batch's row block holds, stat after stat, four PLANES — sums u64,
+//      counts u32, mins u32, maxs u32 —, each [caller query][nbuckets + 1]: stat k starts at 32-bit word off[k] (even: the sums are 8-byte aligned) and, with
+//      R = nq * (nb[k] + 1) records, its counts lie at word off[k] + 2 R, its mins at + 3 R, its maxs at + 4 R
+constexpr uint32_t STATS_MAX = 4;                  // == TRI_STATS_MAX
+constexpr uint32_t STATS_WG = 256;                 // threads of a workgroup of k_stats (a workgroup per task)
+constexpr uint32_t STATS_LDS_BUCKETS = 800;        // the most records per query (all GROUPED stats: sum of nbuckets + 1) a workgroup keeps in LDS before it touches the
+                                                   // global rows: (800 + STATS_MAX) records of 20 bytes = 16 080 bytes, under 16 KB (k_facet.hpp's comment: past 20 KB LDS
+                                                   // would set the occupancy of the direct path too); wider rows take global atomics per match
+constexpr uint32_t STATS_SHORT_SEGMENT = 128;      // a task segment of fewer matches sends its grouped stats straight to the global rows.  The value is the facets'
+                                                   // (FACET_SHORT_SEGMENT), taken over; no probe leg runs near it: unmeasured for this kernel
+struct DevStats { // passed to the kernel BY VALUE: a run already queued keeps the specs it was launched with
+        const uint32_t *group[STATS_MAX]; // the group columns (tri_column); nullptr: an ungrouped stat, one record per query
+        const uint32_t *value[STATS_MAX]; // the value columns
+        uint64_t off[STATS_MAX];          // stat k's first 32-bit word in the row block
+        uint32_t nb[STATS_MAX];           // nbuckets (0: ungrouped)
+        uint32_t lds_off[STATS_MAX + 1];  // a grouped stat's first record in a workgroup's LDS planes (an ungrouped one takes none); [n] = lds_records
+        uint32_t n, lds_records;          // stats; records per query of all grouped stats
+        uint32_t ndocs, nq;               // entries of every column of the index (docs_cnt + 1): a docID at or past it is never read; caller queries
+};

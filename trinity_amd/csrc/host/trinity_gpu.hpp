@@ -17,6 +17,7 @@
 #include "google_encoder.hpp"
 #include "facet_rows.hpp"
 #include "order_rows.hpp"
+#include "stats_rows.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -433,6 +434,7 @@ namespace trinity_amd {
 
         struct FacetCounter;
         struct ColumnOrder;
+        struct StatsCounter;
         struct MatchedIndexDocumentsFilter { // matches.h:139-185
                 virtual void consider(const matched_document &) {} // default execution mode
                 virtual void consider(const docid_t) {}
@@ -450,6 +452,8 @@ namespace trinity_amd {
                 virtual FacetCounter *facet_counter() { return nullptr; }
                 // ... and one that lists its first K documents by a per-document column (ColumnOrder below): bound and run the same way (tri_batch_set_order)
                 virtual ColumnOrder *column_order() { return nullptr; }
+                // ... and one that aggregates a value column per bucket of a group column (StatsCounter below): bound and run the same way (tri_batch_set_stats)
+                virtual StatsCounter *stats_counter() { return nullptr; }
                 virtual ~MatchedIndexDocumentsFilter() = default;
         };
 
@@ -964,6 +968,90 @@ namespace trinity_amd {
                 }
         };
 
+        // The application's consider(id) / consider(ids, cnt) when it adds up an attribute of the matches — the price range, the average rating per category, revenue
+        // per brand: row k has stats[k].nbuckets + 1 records (one without a group column), and the record of bucket min(group, nbuckets) takes every considered
+        // document's value: count, sum, min, max (stats_rows.hpp) — and the device form of the same: a DocumentsOnly exec_query recognises the counter
+        // (stats_counter()) and, with device == true, sets the stats on its batch and reads the rows back (tri_batch_stats) instead of delivering the docID set;
+        // device = false keeps the replay through consider(), for comparison.  A stat lists one column per source the counter may run against (a collection: one
+        // per source); exec_query binds the counter to its source first.
+        struct StatsCounter : public MatchedIndexDocumentsFilter {
+                struct Stat {
+                        std::vector<const DeviceColumn *> groups; // one per source; empty: ungrouped, one bucket (nbuckets 0)
+                        uint32_t nbuckets;
+                        std::vector<const DeviceColumn *> values; // one per source
+                };
+                std::vector<Stat> stats;
+                bool device{true};
+                std::vector<std::vector<stats_rows::Record>> rows; // [stat][nbuckets + 1]
+                std::vector<const DeviceColumn *> bound_group, bound_value; // per stat: the columns of the source the counter runs against (group: nullptr when ungrouped)
+
+                explicit StatsCounter(std::vector<Stat> st, const bool onDevice = true) : stats(std::move(st)), device{onDevice} {
+                        if (stats.empty() || stats.size() > TRI_STATS_MAX)
+                                throw invalid_argument("StatsCounter: 1 .. TRI_STATS_MAX stats");
+                        for (const auto &x : stats) {
+                                if (x.groups.empty() ? x.nbuckets != 0 : (x.nbuckets < 1 || x.nbuckets > TRI_FACET_MAX_BUCKETS))
+                                        throw invalid_argument("StatsCounter: nbuckets 1 .. TRI_FACET_MAX_BUCKETS with a group column, 0 without");
+                                rows.emplace_back(size_t(x.nbuckets) + 1);
+                        }
+                }
+                StatsCounter *stats_counter() override { return this; }
+                void bind(IndexSource *src) {
+                        const auto of = [src](const std::vector<const DeviceColumn *> &cols) {
+                                const DeviceColumn *out = nullptr;
+                                for (const DeviceColumn *c : cols)
+                                        if (c && c->source() == src)
+                                                out = c;
+                                return out;
+                        };
+                        bound_group.assign(stats.size(), nullptr);
+                        bound_value.assign(stats.size(), nullptr);
+                        for (size_t k = 0; k < stats.size(); ++k) {
+                                bound_group[k] = of(stats[k].groups);
+                                bound_value[k] = of(stats[k].values);
+                                if (!bound_value[k] || (!stats[k].groups.empty() && !bound_group[k]))
+                                        throw invalid_argument("StatsCounter: a stat has no column of the source the query runs against");
+                        }
+                }
+                void consider(const docid_t id) override { consider(&id, 1); }
+                void consider(const docid_t *ids, const size_t cnt) override {
+                        if (bound_value.size() != stats.size())
+                                throw invalid_argument("StatsCounter: not bound to a source (exec_query binds it)");
+                        for (size_t k = 0; k < stats.size(); ++k)
+                                stats_rows::count(rows[k].data(), bound_group[k] ? bound_group[k]->values().data() : nullptr, bound_value[k]->values().data(), bound_value[k]->values().size(),
+                                                  stats[k].nbuckets, ids, cnt);
+                }
+                // the device form: the specs for tri_batch_set_stats ...
+                std::vector<tri_stat> specs() const {
+                        std::vector<tri_stat> out;
+                        for (size_t k = 0; k < stats.size(); ++k)
+                                out.push_back(tri_stat{bound_group[k] ? bound_group[k]->handle() : nullptr, bound_value[k]->handle(), stats[k].nbuckets, 0});
+                        return out;
+                }
+                // ... and the rows of the batch's query q combined into the counter's
+                void read(tri_batch *b, const size_t q, const size_t nq) {
+                        for (size_t k = 0; k < stats.size(); ++k) {
+                                const size_t w = size_t(stats[k].nbuckets) + 1;
+                                std::vector<uint64_t> sums(nq * w);
+                                std::vector<uint32_t> counts(nq * w), mins(nq * w), maxs(nq * w);
+                                check(tri_batch_stats(b, k, sums.data(), counts.data(), mins.data(), maxs.data(), nq * w));
+                                if (stats_rows::add(rows[k].data(), sums.data() + q * w, counts.data() + q * w, mins.data() + q * w, maxs.data() + q * w, w) != w)
+                                        throw invalid_argument("StatsCounter: a sum wraps 64 bits");
+                        }
+                }
+                // The records of a collection's sources (exec_query's collection form, one StatsCounter per source) combined: the host form of tri_cbatch_stats.
+                static std::vector<stats_rows::Record> combine(const std::vector<std::unique_ptr<StatsCounter>> &parts, const size_t k) {
+                        std::vector<stats_rows::Record> out;
+                        for (const auto &p : parts) {
+                                if (k >= p->rows.size() || (!out.empty() && out.size() != p->rows[k].size()))
+                                        throw invalid_argument("StatsCounter::combine: the parts disagree in their stats");
+                                out.resize(p->rows[k].size());
+                                if (stats_rows::add(out.data(), p->rows[k].data(), out.size()) != out.size())
+                                        throw invalid_argument("StatsCounter::combine: a sum wraps 64 bits");
+                        }
+                        return out;
+                }
+        };
+
         // ------------------------------------------------------------------ execution
         struct BatchDeleter {
                 void operator()(tri_batch *b) const { tri_batch_destroy(b); }
@@ -1267,6 +1355,18 @@ namespace trinity_amd {
                                 auto b = run_batch(src, {root}, flags, 0, nullptr, onDevice ? std::vector<tri_filter *>{onDevice} : std::vector<tri_filter *>{},
                                                    [&](tri_batch *bt, const std::vector<uint32_t> &, const std::vector<tri_query> &) { check(tri_batch_set_order(bt, &spec)); });
                                 co->read(b.get(), 0, 1);
+                                return;
+                        }
+                }
+                // ... and so does a stats counter
+                StatsCounter *const sc = matchesFilter ? matchesFilter->stats_counter() : nullptr;
+                if (sc) {
+                        sc->bind(src);
+                        if (sc->device && (flags & unsigned(ExecFlags::DocumentsOnly)) && (!f || onDevice)) {
+                                const auto specs = sc->specs();
+                                auto b = run_batch(src, {root}, flags, 0, nullptr, onDevice ? std::vector<tri_filter *>{onDevice} : std::vector<tri_filter *>{},
+                                                   [&](tri_batch *bt, const std::vector<uint32_t> &, const std::vector<tri_query> &) { check(tri_batch_set_stats(bt, specs.data(), specs.size())); });
+                                sc->read(b.get(), 0, 1);
                                 return;
                         }
                 }

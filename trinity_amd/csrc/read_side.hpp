@@ -5,11 +5,13 @@
 //   for_each_segment          a query's result is the in-order concatenation of its task segments
 //   ReadBack                  THE stream rule: a result copy is enqueued on the read-back stream under the handle's lock and awaited outside it
 // The transforms between the device's layout and the caller's (mask widening, frequency-row narrowing, bitmap expansion) are host/result_rows.hpp; a collection's
-// facet rows are summed by host/facet_rows.hpp; an ordered row's keys are split into docIDs and values by host/order_rows.hpp.
+// facet rows are summed by host/facet_rows.hpp; an ordered row's keys are split into docIDs and values by host/order_rows.hpp; a collection's
+// stats rows are combined by host/stats_rows.hpp.
 #pragma once
 #include "host/result_rows.hpp"
 #include "host/facet_rows.hpp"
 #include "host/order_rows.hpp"
+#include "host/stats_rows.hpp"
 
 namespace {
         // what every result call opens with: its arguments, the flags the batch must have been created with, and (must_sync) that its results stand
@@ -455,6 +457,23 @@ extern "C" int tri_batch_facets(tri_batch *b, size_t k, uint32_t *counts, size_t
         return ReadBack(b->dev).copy(counts, b->d_facet_rows + b->facets.rows_off[k], need * 4).done();
 }
 
+// stats of a column (tri_batch_set_stats; k_stats.hpp): one stat's four planes of the whole batch: each lies in caller query order — ONE read-back copy per plane asked for
+extern "C" int tri_batch_stats(tri_batch *b, size_t k, uint64_t *sums, uint32_t *counts, uint32_t *mins, uint32_t *maxs, size_t cap) {
+        if (const int rc = read_check(b, sums || counts || mins || maxs, __func__, 0, false))
+                return rc;
+        if (!b->stats.n)
+                return fail(TRI_ERR_INVALID, "%s: no stats are set (tri_batch_set_stats)", __func__);
+        if (k >= b->stats.n)
+                return fail(TRI_ERR_INVALID, "%s: stat %zu of %u", __func__, k, b->stats.n);
+        if (!b->synced || !b->stats_done)
+                return fail(TRI_ERR_INVALID, "%s: tri_batch_sync first (a run that follows tri_batch_set_stats)", __func__);
+        const size_t need = b->nq * ((size_t)b->stats.nb[k] + 1);
+        if (cap < need)
+                return fail(TRI_ERR_INVALID, "%s: the rows need %zu records, %zu given", __func__, need, cap);
+        const uint32_t *base = b->d_stats_rows.get() + b->stats.off[k];
+        return ReadBack(b->dev).copy(sums, base, need * 8).copy(counts, base + 2 * need, need * 4).copy(mins, base + 3 * need, need * 4).copy(maxs, base + 4 * need, need * 4).done();
+}
+
 namespace {
         // rows of topk keys and their counts, read back in two copies and split into the caller's arrays
         int ordered_rows(tri_dev *dev, const uint64_t *d_keys, const uint32_t *d_counts, const size_t nq, const size_t k, const bool descending, uint32_t *docids, uint32_t *values,
@@ -605,4 +624,50 @@ extern "C" int tri_cbatch_ordered(tri_cbatch *c, uint32_t *docids, uint32_t *val
         if (!c->ordered)
                 return fail(TRI_ERR_INVALID, "%s: %s", __func__, c->order_why.c_str());
         return ordered_rows(c->parts[0]->ix->dev, c->d_order_keys, c->d_order_counts, c->parts[0]->nq, c->order_k, c->parts[0]->order.flip != 0, docids, values, counts);
+}
+
+// stat k's rows over a collection (tri_batch_stats above; exec.h:12-23): the parts' rows combined on the host — counts and sums added, mins and maxs folded (a document
+// of several sources counts once per source that delivers it, as tri_cbatch_docset lists it)
+extern "C" int tri_cbatch_stats(tri_cbatch *c, size_t k, uint64_t *sums, uint64_t *counts, uint32_t *mins, uint32_t *maxs, size_t cap) {
+        if (const int rc = cbatch_check(c, sums || counts || mins || maxs, __func__))
+                return rc;
+        const tri_batch *p0 = c->parts[0];
+        for (size_t i = 0; i < c->parts.size(); ++i) {
+                const tri_batch *p = c->parts[i];
+                if (p->stats.n != p0->stats.n)
+                        return fail(TRI_ERR_INVALID, "%s: part %zu carries %u stats, part 0 carries %u", __func__, i, p->stats.n, p0->stats.n);
+                if (k < p->stats.n && !p->stats.group[k] != !p0->stats.group[k])
+                        return fail(TRI_ERR_INVALID, "%s: stat %zu is %s in part %zu and %s in part 0", __func__, k, p->stats.group[k] ? "grouped" : "ungrouped", i,
+                                    p0->stats.group[k] ? "grouped" : "ungrouped");
+                if (k < p->stats.n && p->stats.nb[k] != p0->stats.nb[k])
+                        return fail(TRI_ERR_INVALID, "%s: stat %zu has %u buckets in part %zu and %u in part 0", __func__, k, p->stats.nb[k], i, p0->stats.nb[k]);
+        }
+        if (!p0->stats.n)
+                return fail(TRI_ERR_INVALID, "%s: no stats are set on the parts (tri_batch_set_stats)", __func__);
+        if (k >= p0->stats.n)
+                return fail(TRI_ERR_INVALID, "%s: stat %zu of %u", __func__, k, p0->stats.n);
+        const size_t row = (size_t)p0->stats.nb[k] + 1, need = p0->nq * row;
+        if (cap < need)
+                return fail(TRI_ERR_INVALID, "%s: the rows need %zu records, %zu given", __func__, need, cap);
+        std::vector<uint64_t> psums(need);
+        std::vector<uint32_t> pcounts(need), pmins(need), pmaxs(need);
+        std::vector<stats_rows::Record> total(need); // (nothing is written to the outputs before every part has answered)
+        for (size_t i = 0; i < c->parts.size(); ++i) {
+                if (const int rc = tri_batch_stats(c->parts[i], k, psums.data(), pcounts.data(), pmins.data(), pmaxs.data(), need))
+                        return rc;
+                const size_t at = stats_rows::add(total.data(), psums.data(), pcounts.data(), pmins.data(), pmaxs.data(), need);
+                if (at != need)
+                        return fail(TRI_ERR_INVALID, "%s: stat %zu: the sum of query %zu, bucket %zu wraps 64 bits at part %zu", __func__, k, at / row, at % row, i);
+        }
+        for (size_t i = 0; i < need; ++i) {
+                if (sums)
+                        sums[i] = total[i].sum;
+                if (counts)
+                        counts[i] = total[i].count;
+                if (mins)
+                        mins[i] = total[i].min;
+                if (maxs)
+                        maxs[i] = total[i].max;
+        }
+        return TRI_OK;
 }

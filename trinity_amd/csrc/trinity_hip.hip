@@ -75,6 +75,7 @@ struct tri_dev {
         tri_options opt;
         uint64_t rich_write_last_us = 0, rank_last_us = 0; // the last ranked batch's WRITE pass and rank pass (tri_dev_get_option, read-only)
         uint64_t facet_last_us = 0;                        // the last faceted run's row zeroing + k_facet (read at tri_batch_sync)
+        uint64_t stats_last_us = 0;                        // the last run with stats: the rows' initialisation + k_stats (read at tri_batch_sync)
         uint64_t order_last_us = 0;                        // the last ordered run's k_order + k_order_merge rounds (read at tri_batch_sync)
         uint64_t crank_merge_last_us = 0;                  // the last ranked collection's merge of its parts' lists (k_rank_merge_sources)
         int refs = 0;         // indexes and batches alive on this handle ...
@@ -429,6 +430,10 @@ struct tri_batch : BatchPlan {
         // then a length per list and row —, the merge's groups (they depend on the plan alone: laid out by the first setter) and the events around the run's kernels
         // (option order_last_us)
         Pooled<uint64_t> d_order_block;
+        // tri_batch_set_stats (k_stats.hpp): ONE pooled row block — per stat four planes (sums u64, counts, mins, maxs u32), each [caller query][nbuckets + 1], initialised
+        // and aggregated again by every run — and the events around the run's initialisation + kernel (option stats_last_us)
+        Pooled<uint32_t> d_stats_rows;
+        PooledEvent stats_ev[2];
         DevMem<DevOrderGroup> d_order_groups;
         PooledEvent order_ev[2];
         // ---- VIEWS: plain pointers into the buffers above, released with them
@@ -477,6 +482,9 @@ struct tri_batch : BatchPlan {
         DevFacets facets{};                       // the specs; facets.n == 0: none
         size_t facet_counters = 0;                // counters of d_facet_rows
         bool facet_ran = false, facet_done = false; // the last run counted with the specs that stand; ... and tri_batch_sync has awaited it
+        DevStats stats{};                         // tri_batch_set_stats: the specs as the kernel takes them (the columns by reference); stats.n == 0: none
+        size_t stats_words = 0;                   // 32-bit words of d_stats_rows
+        bool stats_ran = false, stats_done = false; // the last run aggregated with the specs that stand; ... and tri_batch_sync has awaited it
         struct OrderRound {
                 uint32_t first_group, ngroups; // of d_order_groups
         };
@@ -522,6 +530,7 @@ struct tri_batch : BatchPlan {
 #include "k_perc.hpp"
 #include "k_facet.hpp"
 #include "k_order.hpp"
+#include "k_stats.hpp"
 #include "k_commit.hpp"
 #include "k_lencode.hpp"
 #include "filtered_kernels.hpp"
@@ -627,6 +636,10 @@ extern "C" int tri_dev_get_option(tri_dev *d, const char *name, uint64_t *value)
         }
         if (!strcmp(name, "facet_last_us")) { // (... of the last faceted run's row zeroing and k_facet, tri_batch_sync)
                 *value = d->facet_last_us;
+                return TRI_OK;
+        }
+        if (!strcmp(name, "stats_last_us")) { // (... of the last run's stats: the rows' initialisation and k_stats, tri_batch_sync)
+                *value = d->stats_last_us;
                 return TRI_OK;
         }
         if (!strcmp(name, "order_last_us")) { // (... of the last ordered run's k_order and k_order_merge rounds, tri_batch_sync)
@@ -1876,6 +1889,29 @@ static int run_order(tri_batch *b) {
         return TRI_OK;
 }
 
+// tri_batch_set_stats: the rows initialised (the mins planes to 0xffffffff, everything else to 0) and aggregated behind the kernels that complete the docID sets
+// (k_stats reads the device-side task counts), ahead of the run's end event.  A batch without stats enqueues nothing
+static int run_stats(tri_batch *b) {
+        b->stats_ran = b->stats_done = false;
+        if (!b->stats.n)
+                return TRI_OK;
+        tri_dev *dev = b->dev;
+        HIP_TRY(hipEventRecord(b->stats_ev[0], dev->stream));
+        HIP_TRY(hipMemsetAsync(b->d_stats_rows, 0, b->stats_words * 4, dev->stream));
+        for (uint32_t k = 0; k < b->stats.n; ++k) {
+                const size_t records = b->nq * ((size_t)b->stats.nb[k] + 1);
+                HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(b->d_stats_rows.get() + b->stats.off[k] + 3 * records), (int)0xffffffffu, records, dev->stream));
+        }
+        if (!b->tasks.empty()) {
+                hipLaunchKernelGGL(k_stats, dim3((uint32_t)b->tasks.size()), dim3(STATS_WG), 0, dev->stream, (const DevQuery *)b->dev_at(b->plan), (const DevTask *)b->dev_at(b->tasks),
+                                   (const uint32_t *)b->d_counts, (const uint32_t *)b->d_out, b->stats, b->d_stats_rows.get());
+                HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(b->stats_ev[1], dev->stream));
+        b->stats_ran = true;
+        return TRI_OK;
+}
+
 extern "C" int tri_batch_run(tri_batch *b) {
         if (!b)
                 return fail(TRI_ERR_INVALID, "null batch");
@@ -1926,6 +1962,8 @@ extern "C" int tri_batch_run(tri_batch *b) {
         if (const int rc = run_facets(b))
                 return rc;
         if (const int rc = run_order(b))
+                return rc;
+        if (const int rc = run_stats(b))
                 return rc;
         HIP_TRY(hipEventRecord(b->ev[EV_END], dev->stream));
         return TRI_OK;
@@ -2295,6 +2333,12 @@ extern "C" int tri_batch_sync(tri_batch *b) {
                 if (hipEventElapsedTime(&ms, b->facet_ev[0], b->facet_ev[1]) == hipSuccess)
                         dev->facet_last_us = (uint64_t)(ms * 1000.0f);
                 b->facet_done = true;
+        }
+        if (b->stats_ran) { // (both events precede EV_END)
+                float ms = 0;
+                if (hipEventElapsedTime(&ms, b->stats_ev[0], b->stats_ev[1]) == hipSuccess)
+                        dev->stats_last_us = (uint64_t)(ms * 1000.0f);
+                b->stats_done = true;
         }
         if (b->order_ran) { // (both events precede EV_END)
                 float ms = 0;
@@ -3036,6 +3080,7 @@ extern "C" int tri_gather_results(tri_batch *b, tri_comm *c, void *counts_all, v
 #include "write_side.hpp"
 #include "isect_side.hpp"
 #include "facet_side.hpp"
+#include "stats_side.hpp"
 #include "order_side.hpp"
 #include "perc_side.hpp"
 

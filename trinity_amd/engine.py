@@ -1,6 +1,7 @@
 """ctypes harness over the C-ABI (include/trinity_hip.h) and the host tools (csrc/host/synth.cpp).
 
 No fallbacks: a missing libtrinity_hip.so, a missing GPU or a failing call raises TrinityError."""
+import collections
 import ctypes as C
 import os
 
@@ -48,6 +49,10 @@ class TriFacet(C.Structure):
 
 class TriOrder(C.Structure):
     _fields_ = [("column", C.c_void_p), ("topk", C.c_uint32), ("descending", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TriStat(C.Structure):
+    _fields_ = [("group", C.c_void_p), ("value", C.c_void_p), ("nbuckets", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class TriIsectRequest(C.Structure):
@@ -160,6 +165,7 @@ ABI_SYMBOLS = [
     "tri_perc_result_pairs", "tri_perc_result_doc_counts", "tri_perc_result_get_info", "tri_perc_result_destroy",
     "tri_column_create", "tri_column_destroy", "tri_batch_set_facets", "tri_batch_facets", "tri_cbatch_facets",
     "tri_batch_set_order", "tri_batch_ordered", "tri_cbatch_ordered",
+    "tri_batch_set_stats", "tri_batch_stats", "tri_cbatch_stats",
 ]  # fmt: skip
 
 _hip = None
@@ -257,6 +263,9 @@ def hip_lib():
     L.tri_batch_set_order.argtypes = [vp, C.POINTER(TriOrder)]
     L.tri_batch_ordered.argtypes = [vp, vp, vp, vp]
     L.tri_cbatch_ordered.argtypes = [vp, vp, vp, vp]
+    L.tri_batch_set_stats.argtypes = [vp, C.POINTER(TriStat), C.c_size_t]
+    L.tri_batch_stats.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t]
+    L.tri_cbatch_stats.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t]
     L.tri_isect_run.argtypes = [vp, vp, C.c_size_t, vp, vp, C.POINTER(vp)]
     L.tri_isect_status.argtypes = [vp, vp]
     L.tri_isect_results.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -821,6 +830,10 @@ FACET_MAX_BUCKETS = 65536  # TRI_FACET_MAX_BUCKETS
 ORDER_MAX_TOPK = 256  # TRI_ORDER_MAX_TOPK
 
 
+STATS_MAX = 4  # TRI_STATS_MAX
+Stats = collections.namedtuple("Stats", "sums counts mins maxs")  # what Batch.stats / CollectionBatch.stats return: one array per plane, [nq, nbuckets + 1]
+
+
 class Column:
     """A per-document attribute column on the device (tri_column_create): values[d] = the attribute of docID d, docs_cnt + 1 entries (values[0] is never read).
     Closed before its index; alive while a batch that names it may run."""
@@ -923,6 +936,28 @@ class Batch:
         d, v, c = np.zeros((self.nq, k), dtype=np.uint32), np.zeros((self.nq, k), dtype=np.uint32), np.zeros(self.nq, dtype=np.uint32)
         _check(hip_lib().tri_batch_ordered(self.h, d.ctypes.data, v.ctypes.data, c.ctypes.data))
         return d, v, c
+
+    def set_stats(self, stats):
+        """Stats of a column for the runs that follow (tri_batch_set_stats): stats = [(group Column or None, nbuckets, value Column), ...], at most STATS_MAX; an empty
+        list clears.  nbuckets is 0 without a group column.  Every run then aggregates each query's docID set on the device; results: stats(k).  The batch keeps the
+        Column objects referenced."""
+        stats = list(stats)
+        arr = (TriStat * max(1, len(stats)))()
+        for i, (group, nb, value) in enumerate(stats):
+            arr[i].group, arr[i].value = (group.h if group is not None else None), (value.h if value is not None else None)
+            arr[i].nbuckets, arr[i].reserved = int(nb), 0
+        _check(hip_lib().tri_batch_set_stats(self.h, arr if stats else None, len(stats)))
+        self._stats = stats
+
+    def stats(self, k):
+        """After sync(): stat k's rows as Stats(sums u64, counts u32, mins u32, maxs u32), each [nq, nbuckets + 1] in caller query order — the record of bucket
+        min(group[d], nbuckets) over the documents d of query q's docID set; the last is the overflow bucket; an empty record reads 0, 0, 0xffffffff, 0
+        (tri_batch_stats: one copy per plane for the whole batch)."""
+        spec = getattr(self, "_stats", [])
+        nb = int(spec[k][1]) if 0 <= k < len(spec) else 0  # (out of range: the library refuses)
+        out = Stats(np.zeros((self.nq, nb + 1), np.uint64), np.zeros((self.nq, nb + 1), np.uint32), np.zeros((self.nq, nb + 1), np.uint32), np.zeros((self.nq, nb + 1), np.uint32))
+        _check(hip_lib().tri_batch_stats(self.h, k, out.sums.ctypes.data, out.counts.ctypes.data, out.mins.ctypes.data, out.maxs.ctypes.data, out.sums.size))
+        return out
 
     def set_ranker(self, topk, freq_cap=65535, adjacency=0.0, weights=None):
         """FLAG_MATCHED_TERMS batches: rank every query's matches on the device for the runs that follow (tri_batch_set_ranker, TRI_RANK_PROXIMITY):
@@ -1175,6 +1210,15 @@ class CollectionBatch:
         d, v, c = np.zeros((self.nq, k), dtype=np.uint32), np.zeros((self.nq, k), dtype=np.uint32), np.zeros(self.nq, dtype=np.uint32)
         _check(hip_lib().tri_cbatch_ordered(self.h, d.ctypes.data, v.ctypes.data, c.ctypes.data))
         return d, v, c
+
+    def stats(self, k):
+        """After sync(): stat k's rows over the collection as Stats(sums u64, counts u64, mins u32, maxs u32), each [nq, nbuckets + 1] — the parts' rows combined
+        (tri_cbatch_stats); the parts must agree in the number of stats, in stat k's nbuckets and in whether it is grouped."""
+        spec = getattr(self.parts[0], "_stats", [])
+        nb = int(spec[k][1]) if 0 <= k < len(spec) else 0
+        out = Stats(np.zeros((self.nq, nb + 1), np.uint64), np.zeros((self.nq, nb + 1), np.uint64), np.zeros((self.nq, nb + 1), np.uint32), np.zeros((self.nq, nb + 1), np.uint32))
+        _check(hip_lib().tri_cbatch_stats(self.h, k, out.sums.ctypes.data, out.counts.ctypes.data, out.mins.ctypes.data, out.maxs.ctypes.data, out.sums.size))
+        return out
 
     def _query_width(self, q):
         """(terms, nterms) of query q: those of the first part that reports it (the parts agree, or the row calls refuse)."""
