@@ -235,8 +235,24 @@ void *tri_dev_stream(tri_dev *);
  *                         create that cannot get the memory fails with TRI_ERR_NOMEM.  Batches whose queries all report at most 16 terms are unaffected
  *   "tree_wide_min_nodes" a tree query of at least this many nodes runs in the wide kernels (default 65: only the trees the narrow ones cannot hold; 0: every
  *                         tree query).  Results do not depend on it; it is there so that the wide kernels can be checked on trees with pinned answers
- * ("fused" also takes 2: only pure unions run in one pass.)  The options are read when a batch is CREATED, except the two overlap_* ones and planes_rebuild,
- * which tri_batch_run reads (they change how existing batches are launched).  Unknown names fail with TRI_ERR_INVALID. */
+ *   "phrase_task_div"     the tasks of a query with phrases are cut this many times finer than a phrase-less query's: window tasks, plane-set tasks (at
+ *                         least one window each) and candidate-tile tasks — they are the phrase kernel's tasks too, and its span is its longest task.
+ *                         Default 0: by the batch's phrase queries per compute unit — 4 up to 8 a unit, 2 up to 16, else 1.  Results do not depend on it
+ *   "dense_window_cost"   a docID window of a bitmap-window task counts this many postings whatever it holds, which bounds the windows per task of
+ *                         queries over rare lists (default 16384; 0: such a task takes as many windows as dense_task_cost allows).  Results do not depend on it
+ *   "scatter_bitmap_slack" a DocumentsOnly union of head terms with terms that have no plane runs over the planes — the other terms' documents set bit by
+ *                         bit, the result a bitmap — when min(docs_cnt, its head terms' documents) x this value >= the 32-bit words of a bitmap over the
+ *                         query's docID windows (default 4; 1: only where the bitmap is no larger than the docID list; 0 reads as 1).  The other such unions run
+ *                         in the bitmap-window kernel and deliver ascending docIDs.  The docID sets do not depend on it; a result's FORM does
+ *   "pset_order"          1 (default): the plane-set kernel's tasks run docID range by range, within a range by the query's heaviest term; 0: in batch order
+ *                         within a range.  Results do not depend on it
+ *   "planes_order"        the bit-plane kernel's (k_planes) tasks: 1 (default) docID range by range, within a range by the heaviest plane row; 2: row by row,
+ *                         a query's ranges side by side; 0: heaviest task first.  A query's ranges share one threshold; results do not depend on the order
+ *   "tree_max_bytes"      scratch budget of a batch's tree queries (default 16 GiB).  A batch needs (distinct term leaves x PL_PLANES + phrase leaves + tree
+ *                         queries) x plane words x 4 bytes (tri_batch_info.tree_scratch_bytes); a batch that needs more fails tri_batch_create with
+ *                         TRI_ERR_NOMEM and takes nothing from the handle's pool; one that needs exactly the budget is created
+ * ("fused" also takes 2: only pure unions run in one pass.)  The options are read when a batch is CREATED, except "overlap", the two overlap_*_wgs ones and
+ * planes_rebuild, which tri_batch_run reads (they change how existing batches are launched).  Unknown names fail with TRI_ERR_INVALID. */
 int tri_dev_set_option(tri_dev *, const char *name, uint64_t value);
 int tri_dev_get_option(tri_dev *, const char *name, uint64_t *value);
 
