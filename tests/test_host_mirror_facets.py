@@ -1,4 +1,4 @@
-"""FacetCounter on the C++ operator surface (trinity_amd/csrc/host/trinity_gpu.hpp: DeviceColumn, FacetCounter, MatchedIndexDocumentsFilter::facet_counter).  The driver
+"""FacetCounter on the C++ operator surface (trinity_amd/csrc/host/trinity_gpu.hpp: DeviceColumn, FacetCounter, MatchedIndexDocumentsFilter::device_consumer).  The driver
 tests/cpp/host_mirror_facets_test.cpp counts three queries by four facets over the three sources of tests/crank_cases.py — on the device (exec_query sets the facets and
 reads tri_batch_facets) and through the replay (consider(ids, cnt) on the host), under a device filter, under a host filter, and over the collection (each source under
 the registry of the newer ones, the counters summed).  Device, replay and tests/facet_cases.py::facet_rows over the CPU oracle's sets must agree, integer for integer."""

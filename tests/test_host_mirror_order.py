@@ -1,4 +1,4 @@
-"""ColumnOrder on the C++ operator surface (trinity_amd/csrc/host/trinity_gpu.hpp: ColumnOrder, MatchedIndexDocumentsFilter::column_order).  The driver
+"""ColumnOrder on the C++ operator surface (trinity_amd/csrc/host/trinity_gpu.hpp: ColumnOrder, MatchedIndexDocumentsFilter::device_consumer).  The driver
 tests/cpp/host_mirror_order_test.cpp lists three queries' first K by two columns over the three sources of tests/crank_cases.py — on the device (exec_query sets the
 order and reads tri_batch_ordered) and through the replay (consider(ids, cnt) on the host), under a device filter, under a host filter, and over the collection (each
 source under the registry of the newer ones, the lists blended).  Device, replay and tests/order_cases.py::first_k / blend over the CPU oracle's sets must agree,

@@ -1,4 +1,4 @@
-"""StatsCounter on the C++ operator surface (trinity_amd/csrc/host/trinity_gpu.hpp: StatsCounter, MatchedIndexDocumentsFilter::stats_counter).  The driver
+"""StatsCounter on the C++ operator surface (trinity_amd/csrc/host/trinity_gpu.hpp: StatsCounter, MatchedIndexDocumentsFilter::device_consumer).  The driver
 tests/cpp/host_mirror_stats_test.cpp aggregates three queries by four stats — one ungrouped — over the three sources of tests/crank_cases.py: on the device (exec_query
 sets the stats and reads tri_batch_stats) and through the replay (consider(ids, cnt) on the host), under a device filter, under a host filter, and over the collection
 (each source under the registry of the newer ones, the records combined).  Device, replay and tests/stats_cases.py::stats_rows over the CPU oracle's sets must agree,

@@ -432,9 +432,16 @@ namespace trinity_amd {
                 matched_query_term *matchedTerms{nullptr};
         };
 
-        struct FacetCounter;
-        struct ColumnOrder;
-        struct StatsCounter;
+        // The device form of a MatchedIndexDocumentsFilter that consumes a query's docID set (FacetCounter, ColumnOrder, StatsCounter below): a DocumentsOnly exec_query
+        // binds it to the source it runs against and, when on_device() — and nothing but the device decides which documents count —, installs its spec on the batch
+        // (tri_batch_set_facets / _order / _stats) and reads query q's rows of the nq back, instead of delivering the docID set and replaying consider().
+        struct DeviceConsumer {
+                virtual void bind(IndexSource *) = 0;
+                virtual bool on_device() const = 0;
+                virtual void install(tri_batch *) = 0;
+                virtual void read(tri_batch *, size_t q, size_t nq) = 0;
+                virtual ~DeviceConsumer() = default;
+        };
         struct MatchedIndexDocumentsFilter { // matches.h:139-185
                 virtual void consider(const matched_document &) {} // default execution mode
                 virtual void consider(const docid_t) {}
@@ -447,13 +454,10 @@ namespace trinity_amd {
                 // tri_ranker and the weights of the query's terms (per matchedTerms[].queryCtx->term.id - 1) and returns where the ranked list goes; the default
                 // mode's exec_query then ranks on the device (tri_batch_set_ranker) and replays no match.  nullptr (every other filter): consider() per match.
                 virtual std::vector<std::pair<docid_t, double>> *device_ranker(tri_ranker *, std::vector<double> *) { return nullptr; }
-                // A filter that counts its documents by per-document columns (FacetCounter below) says so here: a DocumentsOnly exec_query binds it to the source it
-                // runs against and, unless the counter asks for the replay, has the device count (tri_batch_set_facets) and replays no match.  nullptr: every other filter.
-                virtual FacetCounter *facet_counter() { return nullptr; }
-                // ... and one that lists its first K documents by a per-document column (ColumnOrder below): bound and run the same way (tri_batch_set_order)
-                virtual ColumnOrder *column_order() { return nullptr; }
-                // ... and one that aggregates a value column per bucket of a group column (StatsCounter below): bound and run the same way (tri_batch_set_stats)
-                virtual StatsCounter *stats_counter() { return nullptr; }
+                // A filter that counts, orders or aggregates its documents by per-document columns (FacetCounter, ColumnOrder, StatsCounter below) says so here: a
+                // DocumentsOnly exec_query binds it to the source it runs against and, unless it asks for the replay, has the device consume the set and replays no
+                // match.  nullptr: every other filter.
+                virtual DeviceConsumer *device_consumer() { return nullptr; }
                 virtual ~MatchedIndexDocumentsFilter() = default;
         };
 
@@ -832,10 +836,10 @@ namespace trinity_amd {
 
         // The application's consider(id) / consider(ids, cnt) when it counts the matches by attributes — row k has facets[k].nbuckets + 1 counters, and for every
         // considered document counter min(value, nbuckets) goes up by one (the last one is the overflow bucket; facet_rows.hpp) — and the device form of the same:
-        // a DocumentsOnly exec_query recognises the counter (facet_counter()) and, with device == true, sets the facets on its batch and reads the rows back
+        // a DocumentsOnly exec_query recognises the counter (device_consumer()) and, with device == true, sets the facets on its batch and reads the rows back
         // (tri_batch_facets) instead of delivering the docID set; device = false keeps the replay through consider(), for comparison.  A facet lists one column per
         // source the counter may run against (a collection: one per source); exec_query binds the counter to its source first.
-        struct FacetCounter : public MatchedIndexDocumentsFilter {
+        struct FacetCounter : public MatchedIndexDocumentsFilter, public DeviceConsumer {
                 struct Facet {
                         std::vector<const DeviceColumn *> columns; // one per source
                         uint32_t nbuckets;
@@ -854,8 +858,9 @@ namespace trinity_amd {
                                 rows.emplace_back(size_t(x.nbuckets) + 1, 0u);
                         }
                 }
-                FacetCounter *facet_counter() override { return this; }
-                void bind(IndexSource *src) {
+                DeviceConsumer *device_consumer() override { return this; }
+                bool on_device() const override { return device; }
+                void bind(IndexSource *src) override {
                         bound.assign(facets.size(), nullptr);
                         for (size_t k = 0; k < facets.size(); ++k) {
                                 for (const DeviceColumn *c : facets[k].columns)
@@ -879,8 +884,9 @@ namespace trinity_amd {
                                 out.push_back(tri_facet{bound[k]->handle(), facets[k].nbuckets, 0});
                         return out;
                 }
+                void install(tri_batch *b) override { const auto s = specs(); check(tri_batch_set_facets(b, s.data(), s.size())); }
                 // ... and the rows of the batch's query q added to the counter's
-                void read(tri_batch *b, const size_t q, const size_t nq) {
+                void read(tri_batch *b, const size_t q, const size_t nq) override {
                         std::vector<uint32_t> all;
                         for (size_t k = 0; k < facets.size(); ++k) {
                                 const size_t w = size_t(facets[k].nbuckets) + 1;
@@ -904,10 +910,10 @@ namespace trinity_amd {
         };
 
         // The application's consider(id) / consider(ids, cnt) when it lists the first K matches by an attribute — (value ascending, docID ascending), or descending:
-        // (value descending, docID ascending); order_rows.hpp — and the device form of the same: a DocumentsOnly exec_query recognises the filter (column_order())
+        // (value descending, docID ascending); order_rows.hpp — and the device form of the same: a DocumentsOnly exec_query recognises the filter (device_consumer())
         // and, with device == true, sets the order on its batch and reads the row back (tri_batch_ordered) instead of delivering the docID set; device = false keeps
         // the replay through consider(), for comparison.  columns: one per source the filter may run against (a collection: one per source); exec_query binds it first.
-        struct ColumnOrder : public MatchedIndexDocumentsFilter {
+        struct ColumnOrder : public MatchedIndexDocumentsFilter, public DeviceConsumer {
                 std::vector<const DeviceColumn *> columns; // one per source
                 uint32_t topk;
                 bool descending, device;
@@ -919,8 +925,9 @@ namespace trinity_amd {
                         if (topk < 1 || topk > TRI_ORDER_MAX_TOPK)
                                 throw invalid_argument("ColumnOrder: topk 1 .. TRI_ORDER_MAX_TOPK");
                 }
-                ColumnOrder *column_order() override { return this; }
-                void bind(IndexSource *src) {
+                DeviceConsumer *device_consumer() override { return this; }
+                bool on_device() const override { return device; }
+                void bind(IndexSource *src) override {
                         bound = nullptr;
                         for (const DeviceColumn *c : columns)
                                 if (c && c->source() == src)
@@ -936,8 +943,9 @@ namespace trinity_amd {
                 }
                 // the device form: the spec for tri_batch_set_order ...
                 tri_order spec() const { return tri_order{bound->handle(), topk, descending ? 1u : 0u, 0u}; }
+                void install(tri_batch *b) override { const tri_order s = spec(); check(tri_batch_set_order(b, &s)); }
                 // ... and the row of the batch's query q merged into the list
-                void read(tri_batch *b, const size_t q, const size_t nq) {
+                void read(tri_batch *b, const size_t q, const size_t nq) override {
                         std::vector<uint32_t> d(nq * topk), v(nq * topk), c(nq);
                         check(tri_batch_ordered(b, d.data(), v.data(), c.data()));
                         std::vector<uint64_t> row;
@@ -971,10 +979,10 @@ namespace trinity_amd {
         // The application's consider(id) / consider(ids, cnt) when it adds up an attribute of the matches — the price range, the average rating per category, revenue
         // per brand: row k has stats[k].nbuckets + 1 records (one without a group column), and the record of bucket min(group, nbuckets) takes every considered
         // document's value: count, sum, min, max (stats_rows.hpp) — and the device form of the same: a DocumentsOnly exec_query recognises the counter
-        // (stats_counter()) and, with device == true, sets the stats on its batch and reads the rows back (tri_batch_stats) instead of delivering the docID set;
+        // (device_consumer()) and, with device == true, sets the stats on its batch and reads the rows back (tri_batch_stats) instead of delivering the docID set;
         // device = false keeps the replay through consider(), for comparison.  A stat lists one column per source the counter may run against (a collection: one
         // per source); exec_query binds the counter to its source first.
-        struct StatsCounter : public MatchedIndexDocumentsFilter {
+        struct StatsCounter : public MatchedIndexDocumentsFilter, public DeviceConsumer {
                 struct Stat {
                         std::vector<const DeviceColumn *> groups; // one per source; empty: ungrouped, one bucket (nbuckets 0)
                         uint32_t nbuckets;
@@ -994,8 +1002,9 @@ namespace trinity_amd {
                                 rows.emplace_back(size_t(x.nbuckets) + 1);
                         }
                 }
-                StatsCounter *stats_counter() override { return this; }
-                void bind(IndexSource *src) {
+                DeviceConsumer *device_consumer() override { return this; }
+                bool on_device() const override { return device; }
+                void bind(IndexSource *src) override {
                         const auto of = [src](const std::vector<const DeviceColumn *> &cols) {
                                 const DeviceColumn *out = nullptr;
                                 for (const DeviceColumn *c : cols)
@@ -1027,8 +1036,9 @@ namespace trinity_amd {
                                 out.push_back(tri_stat{bound_group[k] ? bound_group[k]->handle() : nullptr, bound_value[k]->handle(), stats[k].nbuckets, 0});
                         return out;
                 }
+                void install(tri_batch *b) override { const auto s = specs(); check(tri_batch_set_stats(b, s.data(), s.size())); }
                 // ... and the rows of the batch's query q combined into the counter's
-                void read(tri_batch *b, const size_t q, const size_t nq) {
+                void read(tri_batch *b, const size_t q, const size_t nq) override {
                         for (size_t k = 0; k < stats.size(); ++k) {
                                 const size_t w = size_t(stats[k].nbuckets) + 1;
                                 std::vector<uint64_t> sums(nq * w);
@@ -1334,39 +1344,14 @@ namespace trinity_amd {
                 // a filter the device holds (DeviceDocumentsFilter) is installed with the batch — tri_batch_set_filters — and asked nothing here; a plain host
                 // filter is asked per replayed document
                 tri_filter *const onDevice = f ? f->device_filter() : nullptr;
-                // a facet counter runs against this source; on the device when nothing but the device decides which documents count (DocumentsOnly, no host filter)
-                FacetCounter *const fc = matchesFilter ? matchesFilter->facet_counter() : nullptr;
-                if (fc) {
-                        fc->bind(src);
-                        if (fc->device && (flags & unsigned(ExecFlags::DocumentsOnly)) && (!f || onDevice)) {
-                                const auto specs = fc->specs();
+                // a facet counter, a column order or a stats counter runs against this source; on the device when nothing but the device decides which documents
+                // count (DocumentsOnly, no host filter)
+                if (DeviceConsumer *const dc = matchesFilter ? matchesFilter->device_consumer() : nullptr) {
+                        dc->bind(src);
+                        if (dc->on_device() && (flags & unsigned(ExecFlags::DocumentsOnly)) && (!f || onDevice)) {
                                 auto b = run_batch(src, {root}, flags, 0, nullptr, onDevice ? std::vector<tri_filter *>{onDevice} : std::vector<tri_filter *>{},
-                                                   [&](tri_batch *bt, const std::vector<uint32_t> &, const std::vector<tri_query> &) { check(tri_batch_set_facets(bt, specs.data(), specs.size())); });
-                                fc->read(b.get(), 0, 1);
-                                return;
-                        }
-                }
-                // ... and so does a column order
-                ColumnOrder *const co = matchesFilter ? matchesFilter->column_order() : nullptr;
-                if (co) {
-                        co->bind(src);
-                        if (co->device && (flags & unsigned(ExecFlags::DocumentsOnly)) && (!f || onDevice)) {
-                                const tri_order spec = co->spec();
-                                auto b = run_batch(src, {root}, flags, 0, nullptr, onDevice ? std::vector<tri_filter *>{onDevice} : std::vector<tri_filter *>{},
-                                                   [&](tri_batch *bt, const std::vector<uint32_t> &, const std::vector<tri_query> &) { check(tri_batch_set_order(bt, &spec)); });
-                                co->read(b.get(), 0, 1);
-                                return;
-                        }
-                }
-                // ... and so does a stats counter
-                StatsCounter *const sc = matchesFilter ? matchesFilter->stats_counter() : nullptr;
-                if (sc) {
-                        sc->bind(src);
-                        if (sc->device && (flags & unsigned(ExecFlags::DocumentsOnly)) && (!f || onDevice)) {
-                                const auto specs = sc->specs();
-                                auto b = run_batch(src, {root}, flags, 0, nullptr, onDevice ? std::vector<tri_filter *>{onDevice} : std::vector<tri_filter *>{},
-                                                   [&](tri_batch *bt, const std::vector<uint32_t> &, const std::vector<tri_query> &) { check(tri_batch_set_stats(bt, specs.data(), specs.size())); });
-                                sc->read(b.get(), 0, 1);
+                                                   [&](tri_batch *bt, const std::vector<uint32_t> &, const std::vector<tri_query> &) { dc->install(bt); });
+                                dc->read(b.get(), 0, 1);
                                 return;
                         }
                 }

@@ -12,6 +12,7 @@
 // direct.  At 16 KB that bounds nothing — ten workgroups a CU fit, the registers allow eight waves a SIMD —; past 20 KB a workgroup's LDS, not its registers, would set the
 // occupancy of the direct path too: raise FACET_LDS_COUNTERS knowing that (profiles/facet_kernel_resources.txt).
 #pragma once
+#include "docset_walk.hpp" // (docset_task, docset_for_each: the task preamble and the walk of its documents)
 
 // counter of facet k that document d falls into (a docID the column does not cover is never read: overflow)
 __device__ __forceinline__ uint32_t facet_bucket(const DevFacets &f, const uint32_t k, const uint32_t d) {
@@ -33,35 +34,22 @@ __device__ __forceinline__ void facet_count(const DevFacets &f, const uint32_t q
         }
 }
 
-// the documents of the task, each handed to facet_count once
+// the documents of the task (docset_walk.hpp), each handed to facet_count once
 template <bool LDS>
 __device__ __forceinline__ void facet_walk(const DevFacets &f, const DevQuery &q, const DevTask &tk, const uint32_t c, const uint32_t *__restrict__ out, uint32_t *__restrict__ rows,
                                            uint32_t *lds) {
-        const uint32_t *p = out + tk.out_off;
-        if (q.form != RESULT_BITMAP) {
-                for (uint32_t i = threadIdx.x; i < c; i += FACET_WG)
-                        facet_count<LDS>(f, q.qid, rows, lds, p[i]);
-                return;
-        }
-        const uint32_t nw = (tk.tile_end - tk.tile_begin) * SPAN_WORDS;
-        for (uint32_t i = threadIdx.x; i < nw; i += FACET_WG)
-                for (uint32_t m = p[i]; m; m &= m - 1u)
-                        facet_count<LDS>(f, q.qid, rows, lds, (tk.tile_begin * SPAN_WORDS + i) * 32u + (uint32_t)__builtin_ctz(m));
+        docset_for_each<FACET_WG>(q, tk, c, out, [&](const uint32_t d) { facet_count<LDS>(f, q.qid, rows, lds, d); });
 }
 
 __global__ __launch_bounds__(FACET_WG) void k_facet(const DevQuery *__restrict__ plan, const DevTask *__restrict__ tasks, const uint32_t *__restrict__ counts,
                                                     const uint32_t *__restrict__ out, const DevFacets f, uint32_t *__restrict__ rows) {
         __shared__ uint32_t lds[FACET_LDS_COUNTERS];
         const uint32_t tix = blockIdx.x, tid = threadIdx.x;
-        const DevTask tk = tasks[tix];
-        if (task_onepass(tk.kind) && tk.kind != TASK_FUSED_GEN)
-                return; // (a one-pass scored task keeps no docID set; uniform)
-        const DevQuery q = plan[tk.slot];
-        if (q.qid == 0xffffffffu)
-                return; // (a hidden phrase query — a leaf of a TASK_TREE query: no caller query, no row; uniform)
-        const uint32_t c = counts[tix];
-        if (!c)
-                return; // (uniform)
+        DevTask tk;
+        DevQuery q;
+        uint32_t c;
+        if (docset_task(plan, tasks, counts, tix, tk, q, c) != DOCSET_WALK)
+                return; // (a hidden phrase query, a one-pass task, no matches: no row to count into; uniform)
         const uint32_t per_query = f.per_query;
         if (per_query > FACET_LDS_COUNTERS || c < FACET_SHORT_SEGMENT) { // (uniform)
                 facet_walk<false>(f, q, tk, c, out, rows, nullptr);

@@ -22,6 +22,7 @@
 // LDS: ORDER_WAVES * ORDER_BUF * 8 = 16 KB a workgroup, static — nine workgroups a CU fit, the registers allow eight: the register count decides the
 // occupancy (profiles/order_kernel_resources.txt).  No scratch.
 #pragma once
+#include "docset_walk.hpp" // (docset_task, docset_for_each: the task preamble and the walk of its documents)
 
 static_assert(ORDER_WG == ORDER_WAVES * 64 && ORDER_TILE == 64, "a wave offers one document per lane");
 static_assert(ORDER_PRUNE_AT + ORDER_TILE == ORDER_BUF && ORDER_PRUNE_AT >= ORDER_MAX_TOPK && ORDER_BUF % 64 == 0,
@@ -96,12 +97,13 @@ __global__ __launch_bounds__(ORDER_WG) void k_order(const DevQuery *__restrict__
                                                     const uint32_t *__restrict__ out, const DevOrder o, uint64_t *__restrict__ list_keys, uint32_t *__restrict__ list_counts) {
         __shared__ OrderShared sh;
         const uint32_t tix = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-        const DevTask tk = tasks[tix];
-        const DevQuery q = plan[tk.slot];
-        if (q.qid == 0xffffffffu)
-                return; // (a hidden phrase query — a leaf of a TASK_TREE query: no caller query, no list any group names; uniform)
-        const uint32_t c = counts[tix];
-        if ((task_onepass(tk.kind) && tk.kind != TASK_FUSED_GEN) || !c) { // (a one-pass scored task keeps no docID set; no matches: an empty list; uniform)
+        DevTask tk;
+        DevQuery q;
+        uint32_t c;
+        const DocsetCase what = docset_task(plan, tasks, counts, tix, tk, q, c);
+        if (what == DOCSET_HIDDEN)
+                return; // (no caller query, no list any group names; uniform)
+        if (what == DOCSET_EMPTY) { // (a one-pass scored task keeps no docID set; no matches: an empty list; uniform)
                 if (tid == 0)
                         list_counts[tix] = 0;
                 return;

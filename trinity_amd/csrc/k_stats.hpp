@@ -14,6 +14,7 @@
 // The LDS planes are static — (STATS_LDS_BUCKETS + STATS_MAX) records of 20 bytes, 16 080 bytes —: every workgroup reserves them, also one that returns at once; see
 // k_facet.hpp on why they stay under 16 KB (profiles/stats_kernel_resources.txt).
 #pragma once
+#include "docset_walk.hpp" // (docset_task, docset_for_each: the task preamble and the walk of its documents)
 
 struct StatsLds { // record i < STATS_LDS_BUCKETS: a bucket of a grouped stat (DevStats::lds_off); record STATS_LDS_BUCKETS + k: ungrouped stat k, where the waves meet
         unsigned long long sums[STATS_LDS_BUCKETS + STATS_MAX];
@@ -73,26 +74,18 @@ __device__ __forceinline__ void stats_take(const DevStats &s, const uint32_t qid
         }
 }
 
-// the documents of the task, each handed to stats_take once
+// the documents of the task (docset_walk.hpp), each handed to stats_take once
 template <bool LDS>
 __device__ __forceinline__ void stats_walk(const DevStats &s, const DevQuery &q, const DevTask &tk, const uint32_t c, const uint32_t *__restrict__ out, uint32_t *__restrict__ blk,
                                            StatsLds &l, StatsAcc &a) {
-        const uint32_t *p = out + tk.out_off;
-        if (q.form != RESULT_BITMAP) {
-                for (uint32_t i = threadIdx.x; i < c; i += STATS_WG)
-                        stats_take<LDS>(s, q.qid, blk, l, a, p[i]);
-                return;
-        }
-        const uint32_t nw = (tk.tile_end - tk.tile_begin) * SPAN_WORDS;
-        for (uint32_t i = threadIdx.x; i < nw; i += STATS_WG)
-                for (uint32_t m = p[i]; m; m &= m - 1u)
-                        stats_take<LDS>(s, q.qid, blk, l, a, (tk.tile_begin * SPAN_WORDS + i) * 32u + (uint32_t)__builtin_ctz(m));
+        docset_for_each<STATS_WG>(q, tk, c, out, [&](const uint32_t d) { stats_take<LDS>(s, q.qid, blk, l, a, d); });
 }
 
 __global__ __launch_bounds__(STATS_WG) void k_stats(const DevQuery *__restrict__ plan, const DevTask *__restrict__ tasks, const uint32_t *__restrict__ counts,
                                                     const uint32_t *__restrict__ out, const DevStats s, uint32_t *__restrict__ blk) {
         __shared__ StatsLds l;
         const uint32_t tix = blockIdx.x, tid = threadIdx.x;
+        // (docset_task's cases in the kernel's own text: with the shared preamble the compiler spills two more SGPRs here — DESIGN.md §34)
         const DevTask tk = tasks[tix];
         if (task_onepass(tk.kind) && tk.kind != TASK_FUSED_GEN)
                 return; // (a one-pass scored task keeps no docID set; uniform)

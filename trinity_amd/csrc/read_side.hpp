@@ -445,32 +445,28 @@ extern "C" int tri_batch_topk_device(tri_batch *b, void **docids, void **scores,
 extern "C" int tri_batch_facets(tri_batch *b, size_t k, uint32_t *counts, size_t cap) {
         if (const int rc = read_check(b, counts != nullptr, __func__, 0, false))
                 return rc;
-        if (!b->facets.n)
-                return fail(TRI_ERR_INVALID, "%s: no facets are set (tri_batch_set_facets)", __func__);
-        if (k >= b->facets.n)
+        if (b->facets.n && k >= b->facets.n) // (none set: consumer_ready says so)
                 return fail(TRI_ERR_INVALID, "%s: facet %zu of %u", __func__, k, b->facets.n);
-        if (!b->synced || !b->facet_done)
-                return fail(TRI_ERR_INVALID, "%s: tri_batch_sync first (a run that follows tri_batch_set_facets)", __func__);
+        if (const int rc = consumer_ready(b, CONSUMER_FACETS, __func__, "tri_batch_set_facets"))
+                return rc;
         const size_t need = b->nq * ((size_t)b->facets.nb[k] + 1);
         if (cap < need)
                 return fail(TRI_ERR_INVALID, "%s: the rows need %zu counters, %zu given", __func__, need, cap);
-        return ReadBack(b->dev).copy(counts, b->d_facet_rows + b->facets.rows_off[k], need * 4).done();
+        return ReadBack(b->dev).copy(counts, b->facet_rows() + b->facets.rows_off[k], need * 4).done();
 }
 
 // stats of a column (tri_batch_set_stats; k_stats.hpp): one stat's four planes of the whole batch: each lies in caller query order — ONE read-back copy per plane asked for
 extern "C" int tri_batch_stats(tri_batch *b, size_t k, uint64_t *sums, uint32_t *counts, uint32_t *mins, uint32_t *maxs, size_t cap) {
         if (const int rc = read_check(b, sums || counts || mins || maxs, __func__, 0, false))
                 return rc;
-        if (!b->stats.n)
-                return fail(TRI_ERR_INVALID, "%s: no stats are set (tri_batch_set_stats)", __func__);
-        if (k >= b->stats.n)
+        if (b->stats.n && k >= b->stats.n) // (none set: consumer_ready says so)
                 return fail(TRI_ERR_INVALID, "%s: stat %zu of %u", __func__, k, b->stats.n);
-        if (!b->synced || !b->stats_done)
-                return fail(TRI_ERR_INVALID, "%s: tri_batch_sync first (a run that follows tri_batch_set_stats)", __func__);
+        if (const int rc = consumer_ready(b, CONSUMER_STATS, __func__, "tri_batch_set_stats"))
+                return rc;
         const size_t need = b->nq * ((size_t)b->stats.nb[k] + 1);
         if (cap < need)
                 return fail(TRI_ERR_INVALID, "%s: the rows need %zu records, %zu given", __func__, need, cap);
-        const uint32_t *base = b->d_stats_rows.get() + b->stats.off[k];
+        const uint32_t *base = b->stats_rows() + b->stats.off[k];
         return ReadBack(b->dev).copy(sums, base, need * 8).copy(counts, base + 2 * need, need * 4).copy(mins, base + 3 * need, need * 4).copy(maxs, base + 4 * need, need * 4).done();
 }
 
@@ -494,10 +490,8 @@ namespace {
 extern "C" int tri_batch_ordered(tri_batch *b, uint32_t *docids, uint32_t *values, uint32_t *counts) {
         if (const int rc = read_check(b, docids && values && counts, __func__, 0, false))
                 return rc;
-        if (!b->order_on)
-                return fail(TRI_ERR_INVALID, "%s: no order is set (tri_batch_set_order)", __func__);
-        if (!b->synced || !b->order_done)
-                return fail(TRI_ERR_INVALID, "%s: tri_batch_sync first (a run that follows tri_batch_set_order)", __func__);
+        if (const int rc = consumer_ready(b, CONSUMER_ORDER, __func__, "tri_batch_set_order"))
+                return rc;
         return ordered_rows(b->dev, b->order_keys(b->order_lists), b->order_counts(b->order_lists), b->nq, b->order.topk, b->order.flip != 0, docids, values, counts);
 }
 

@@ -65,6 +65,11 @@ extern "C" int tri_abi_version(void) { return TRI_ABI_VERSION; }
 // the planner shares with the kernels (dev_structs.hpp)
 #include "planner.hpp"
 
+// the consumers of a batch's finished docID sets (consumers.hpp), in the order a run enqueues them; the read-only option that holds the device time of each one's
+// last run (its events' span, read at tri_batch_sync)
+enum Consumer { CONSUMER_FACETS, CONSUMER_ORDER, CONSUMER_STATS, CONSUMER_COUNT };
+static const char *const CONSUMER_LAST_US[CONSUMER_COUNT] = {"facet_last_us", "order_last_us", "stats_last_us"};
+
 struct tri_dev {
         int device;
         hipStream_t stream, stream2; // stream2: the candidate-tile kernel when the two matching kernels run side by side
@@ -74,9 +79,7 @@ struct tri_dev {
         int cus;
         tri_options opt;
         uint64_t rich_write_last_us = 0, rank_last_us = 0; // the last ranked batch's WRITE pass and rank pass (tri_dev_get_option, read-only)
-        uint64_t facet_last_us = 0;                        // the last faceted run's row zeroing + k_facet (read at tri_batch_sync)
-        uint64_t stats_last_us = 0;                        // the last run with stats: the rows' initialisation + k_stats (read at tri_batch_sync)
-        uint64_t order_last_us = 0;                        // the last ordered run's k_order + k_order_merge rounds (read at tri_batch_sync)
+        uint64_t consumer_last_us[CONSUMER_COUNT] = {};    // per consumer: its last run's initialisation + kernels (facets: row zeroing + k_facet; order: k_order + merge rounds)
         uint64_t crank_merge_last_us = 0;                  // the last ranked collection's merge of its parts' lists (k_rank_merge_sources)
         int refs = 0;         // indexes and batches alive on this handle ...
         bool closing = false; // ... tri_dev_close with some left: the handle goes with the last of them
@@ -422,20 +425,19 @@ struct tri_batch : BatchPlan {
         Pooled<uint8_t> d_filter_tab;
         Pooled<uint32_t> d_filter_rows;
         Pooled<uint8_t> d_rank_block; // tri_batch_set_ranker (k_rich_rank.hpp): ONE block, rank_block()'s sections
-        // tri_batch_set_facets (k_facet.hpp): the specs as the kernel takes them (the columns by reference), ONE pooled row block ([facet][caller query][nbuckets + 1]
-        // counters, zeroed and recounted by every run) and the events around the run's zeroing + kernel (option facet_last_us)
-        Pooled<uint32_t> d_facet_rows;
-        PooledEvent facet_ev[2];
-        // tri_batch_set_order (k_order.hpp): ONE pooled block — the tasks' partial lists, the merge's two intermediate levels and the rows ([caller query][topk] keys),
-        // then a length per list and row —, the merge's groups (they depend on the plan alone: laid out by the first setter) and the events around the run's kernels
-        // (option order_last_us)
-        Pooled<uint64_t> d_order_block;
-        // tri_batch_set_stats (k_stats.hpp): ONE pooled row block — per stat four planes (sums u64, counts, mins, maxs u32), each [caller query][nbuckets + 1], initialised
-        // and aggregated again by every run — and the events around the run's initialisation + kernel (option stats_last_us)
-        Pooled<uint32_t> d_stats_rows;
-        PooledEvent stats_ev[2];
-        DevMem<DevOrderGroup> d_order_groups;
-        PooledEvent order_ev[2];
+        // the consumers of the finished docID sets (consumers.hpp: tri_batch_set_facets / _order / _stats), one slot each: ONE pooled block, the events around the
+        // run's initialisation + kernels (option *_last_us), and where its lifecycle stands.  The blocks:
+        //   facets  [facet][caller query][nbuckets + 1] counters, zeroed and recounted by every run (k_facet.hpp)
+        //   order   the tasks' partial lists, the merge's two intermediate levels and the rows ([caller query][topk] keys), then a length per list and row (k_order.hpp)
+        //   stats   per stat four planes (sums u64, counts, mins, maxs u32), each [caller query][nbuckets + 1], initialised and aggregated again by every run (k_stats.hpp)
+        struct ConsumerSlot {
+                Pooled<uint64_t> block;
+                PooledEvent ev[2];
+                bool on = false;                // a spec stands
+                bool ran = false, done = false; // the last run consumed with the spec that stands; ... and tri_batch_sync has awaited it
+                uint32_t launches = 0;          // kernels per run of the spec that stands: 1, 1 + the merge's rounds, 1
+        } consumers[CONSUMER_COUNT];
+        DevMem<DevOrderGroup> d_order_groups; // the order's merge groups (they depend on the plan alone: laid out by the first setter)
         // ---- VIEWS: plain pointers into the buffers above, released with them
         // a section of the plan (a Span of BatchPlan: planner_types.hpp, for_each_section) on the device — the block's copy opens the arena
         template <class T>
@@ -479,23 +481,23 @@ struct tri_batch : BatchPlan {
         // tri_batch_set_ranker: the spec, and the caller's program (kept by default-mode batches: the ranker's weights come one per program token)
         bool rank_on = false, rank_done = false;
         tri_ranker rank{};
-        DevFacets facets{};                       // the specs; facets.n == 0: none
-        size_t facet_counters = 0;                // counters of d_facet_rows
-        bool facet_ran = false, facet_done = false; // the last run counted with the specs that stand; ... and tri_batch_sync has awaited it
-        DevStats stats{};                         // tri_batch_set_stats: the specs as the kernel takes them (the columns by reference); stats.n == 0: none
-        size_t stats_words = 0;                   // 32-bit words of d_stats_rows
-        bool stats_ran = false, stats_done = false; // the last run aggregated with the specs that stand; ... and tri_batch_sync has awaited it
+        // the consumers' specs as the kernels take them (the columns by reference), each next to its slot's typed view
+        DevFacets facets{};        // (n == 0: none)
+        size_t facet_counters = 0; // counters of the facets' block
+        uint32_t *facet_rows() const { return reinterpret_cast<uint32_t *>(consumers[CONSUMER_FACETS].block.get()); }
+        DevStats stats{};       // (n == 0: none)
+        size_t stats_words = 0; // 32-bit words of the stats' block
+        uint32_t *stats_rows() const { return reinterpret_cast<uint32_t *>(consumers[CONSUMER_STATS].block.get()); }
         struct OrderRound {
                 uint32_t first_group, ngroups; // of d_order_groups
         };
-        DevOrder order{};                          // the spec as the kernel takes it (the column by reference); order_on: one stands
-        bool order_on = false, order_laid_out = false;
-        std::vector<OrderRound> order_rounds;      // round r reads the tasks' lists (r == 0) or level (r - 1) & 1, and writes rows and level r & 1
-        size_t order_level[2] = {0, 0};            // lists of the two intermediate levels
-        size_t order_lists = 0;                    // lists of d_order_block ahead of its rows: tasks + both levels
-        bool order_ran = false, order_done = false; // the last run selected with the spec that stands; ... and tri_batch_sync has awaited it
-        uint64_t *order_keys(const size_t list) const { return d_order_block.get() + list * order.topk; }
-        uint32_t *order_counts(const size_t list) const { return reinterpret_cast<uint32_t *>(d_order_block.get() + (order_lists + nq) * order.topk) + list; }
+        DevOrder order{};
+        bool order_laid_out = false;
+        std::vector<OrderRound> order_rounds; // round r reads the tasks' lists (r == 0) or level (r - 1) & 1, and writes rows and level r & 1
+        size_t order_level[2] = {0, 0};       // lists of the two intermediate levels
+        size_t order_lists = 0;               // lists of the order's block ahead of its rows: tasks + both levels
+        uint64_t *order_keys(const size_t list) const { return consumers[CONSUMER_ORDER].block.get() + list * order.topk; }
+        uint32_t *order_counts(const size_t list) const { return reinterpret_cast<uint32_t *>(consumers[CONSUMER_ORDER].block.get() + (order_lists + nq) * order.topk) + list; }
         std::vector<uint32_t> h_prog;
         std::vector<tri_query> h_queries;
         tri_batch_info info{};
@@ -634,18 +636,11 @@ extern "C" int tri_dev_get_option(tri_dev *d, const char *name, uint64_t *value)
                 *value = !strcmp(name, "rich_write_last_us") ? d->rich_write_last_us : d->rank_last_us;
                 return TRI_OK;
         }
-        if (!strcmp(name, "facet_last_us")) { // (... of the last faceted run's row zeroing and k_facet, tri_batch_sync)
-                *value = d->facet_last_us;
-                return TRI_OK;
-        }
-        if (!strcmp(name, "stats_last_us")) { // (... of the last run's stats: the rows' initialisation and k_stats, tri_batch_sync)
-                *value = d->stats_last_us;
-                return TRI_OK;
-        }
-        if (!strcmp(name, "order_last_us")) { // (... of the last ordered run's k_order and k_order_merge rounds, tri_batch_sync)
-                *value = d->order_last_us;
-                return TRI_OK;
-        }
+        for (int i = 0; i < CONSUMER_COUNT; ++i) // (... of the last run of each docset consumer: facets, order, stats, tri_batch_sync)
+                if (!strcmp(name, CONSUMER_LAST_US[i])) {
+                        *value = d->consumer_last_us[i];
+                        return TRI_OK;
+                }
         if (!strcmp(name, "crank_merge_last_us")) { // (... and of the last ranked collection's merge kernel, tri_cbatch_sync)
                 *value = d->crank_merge_last_us;
                 return TRI_OK;
@@ -1838,79 +1833,8 @@ static int run_query_counts(tri_batch *b) {
         return TRI_OK;
 }
 
-// tri_batch_set_facets: the rows zeroed and counted behind the kernels that complete the docID sets (every stage above; k_facet reads the device-side task
-// counts), ahead of the run's end event.  A batch without facets enqueues nothing
-static int run_facets(tri_batch *b) {
-        b->facet_ran = b->facet_done = false;
-        if (!b->facets.n)
-                return TRI_OK;
-        tri_dev *dev = b->dev;
-        HIP_TRY(hipEventRecord(b->facet_ev[0], dev->stream));
-        HIP_TRY(hipMemsetAsync(b->d_facet_rows, 0, b->facet_counters * 4, dev->stream));
-        if (!b->tasks.empty()) {
-                hipLaunchKernelGGL(k_facet, dim3((uint32_t)b->tasks.size()), dim3(FACET_WG), 0, dev->stream, (const DevQuery *)b->dev_at(b->plan), (const DevTask *)b->dev_at(b->tasks),
-                                   (const uint32_t *)b->d_counts, (const uint32_t *)b->d_out, b->facets, b->d_facet_rows.get());
-                HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(b->facet_ev[1], dev->stream));
-        b->facet_ran = true;
-        return TRI_OK;
-}
-
-// tri_batch_set_order: every task's best keys selected into its partial list, then a query's lists folded into its row, round after round — behind the kernels that
-// complete the docID sets (k_order reads the device-side task counts), ahead of the run's end event.  A batch without an order enqueues nothing
-static int run_order(tri_batch *b) {
-        b->order_ran = b->order_done = false;
-        if (!b->order_on)
-                return TRI_OK;
-        tri_dev *dev = b->dev;
-        const uint32_t k = b->order.topk;
-        const size_t ntasks = b->tasks.size(), rows = b->order_lists;
-        HIP_TRY(hipEventRecord(b->order_ev[0], dev->stream));
-        if (b->tasks.empty()) { // (no query has a task: every row is empty)
-                HIP_TRY(hipMemsetAsync(b->order_keys(rows), 0, b->nq * (size_t)k * 8, dev->stream));
-                HIP_TRY(hipMemsetAsync(b->order_counts(rows), 0, b->nq * 4, dev->stream));
-        } else {
-                hipLaunchKernelGGL(k_order, dim3((uint32_t)ntasks), dim3(ORDER_WG), 0, dev->stream, (const DevQuery *)b->dev_at(b->plan), (const DevTask *)b->dev_at(b->tasks),
-                                   (const uint32_t *)b->d_counts, (const uint32_t *)b->d_out, b->order, b->order_keys(0), b->order_counts(0));
-                HIP_TRY(hipGetLastError());
-                const size_t level_at[2] = {ntasks, ntasks + b->order_level[0]};
-                for (size_t r = 0; r < b->order_rounds.size(); ++r) {
-                        const tri_batch::OrderRound &round = b->order_rounds[r];
-                        const size_t from = r ? level_at[(r - 1) & 1] : 0, to = level_at[r & 1];
-                        hipLaunchKernelGGL(k_order_merge<false>, dim3(round.ngroups), dim3(ORDER_WG), 0, dev->stream, (const DevOrderLists *)nullptr,
-                                           DevOrderLists{b->order_keys(from), b->order_counts(from)}, (const DevOrderGroup *)b->d_order_groups + round.first_group, 0u, k, b->order_keys(to),
-                                           b->order_counts(to), b->order_keys(rows), b->order_counts(rows));
-                        HIP_TRY(hipGetLastError());
-                }
-        }
-        HIP_TRY(hipEventRecord(b->order_ev[1], dev->stream));
-        b->order_ran = true;
-        return TRI_OK;
-}
-
-// tri_batch_set_stats: the rows initialised (the mins planes to 0xffffffff, everything else to 0) and aggregated behind the kernels that complete the docID sets
-// (k_stats reads the device-side task counts), ahead of the run's end event.  A batch without stats enqueues nothing
-static int run_stats(tri_batch *b) {
-        b->stats_ran = b->stats_done = false;
-        if (!b->stats.n)
-                return TRI_OK;
-        tri_dev *dev = b->dev;
-        HIP_TRY(hipEventRecord(b->stats_ev[0], dev->stream));
-        HIP_TRY(hipMemsetAsync(b->d_stats_rows, 0, b->stats_words * 4, dev->stream));
-        for (uint32_t k = 0; k < b->stats.n; ++k) {
-                const size_t records = b->nq * ((size_t)b->stats.nb[k] + 1);
-                HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(b->d_stats_rows.get() + b->stats.off[k] + 3 * records), (int)0xffffffffu, records, dev->stream));
-        }
-        if (!b->tasks.empty()) {
-                hipLaunchKernelGGL(k_stats, dim3((uint32_t)b->tasks.size()), dim3(STATS_WG), 0, dev->stream, (const DevQuery *)b->dev_at(b->plan), (const DevTask *)b->dev_at(b->tasks),
-                                   (const uint32_t *)b->d_counts, (const uint32_t *)b->d_out, b->stats, b->d_stats_rows.get());
-                HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipEventRecord(b->stats_ev[1], dev->stream));
-        b->stats_ran = true;
-        return TRI_OK;
-}
+// the consumers of the finished docID sets — tri_batch_set_facets / _order / _stats, their columns, run_consumers, sync_consumers, consumer_ready
+#include "consumers.hpp"
 
 extern "C" int tri_batch_run(tri_batch *b) {
         if (!b)
@@ -1959,11 +1883,7 @@ extern "C" int tri_batch_run(tri_batch *b) {
         }
         if (const int rc = run_query_counts(b))
                 return rc;
-        if (const int rc = run_facets(b))
-                return rc;
-        if (const int rc = run_order(b))
-                return rc;
-        if (const int rc = run_stats(b))
+        if (const int rc = run_consumers(b))
                 return rc;
         HIP_TRY(hipEventRecord(b->ev[EV_END], dev->stream));
         return TRI_OK;
@@ -2328,24 +2248,7 @@ extern "C" int tri_batch_sync(tri_batch *b) {
         report_tasktimes(b);
 #endif
         read_stage_times(b);
-        if (b->facet_ran) { // (both events precede EV_END)
-                float ms = 0;
-                if (hipEventElapsedTime(&ms, b->facet_ev[0], b->facet_ev[1]) == hipSuccess)
-                        dev->facet_last_us = (uint64_t)(ms * 1000.0f);
-                b->facet_done = true;
-        }
-        if (b->stats_ran) { // (both events precede EV_END)
-                float ms = 0;
-                if (hipEventElapsedTime(&ms, b->stats_ev[0], b->stats_ev[1]) == hipSuccess)
-                        dev->stats_last_us = (uint64_t)(ms * 1000.0f);
-                b->stats_done = true;
-        }
-        if (b->order_ran) { // (both events precede EV_END)
-                float ms = 0;
-                if (hipEventElapsedTime(&ms, b->order_ev[0], b->order_ev[1]) == hipSuccess)
-                        dev->order_last_us = (uint64_t)(ms * 1000.0f);
-                b->order_done = true;
-        }
+        sync_consumers(b);
         int rc;
         if ((rc = account_matches(b)) || (rc = rich_write_pass(b)))
                 return rc;
@@ -2818,7 +2721,7 @@ static int cbatch_order_prepare(tri_cbatch *c) {
         const tri_batch *p0 = c->parts[0];
         bool any = false;
         for (const tri_batch *p : c->parts)
-                any |= p->order_on;
+                any |= p->consumers[CONSUMER_ORDER].on;
         if (!any) {
                 c->order_why = "no order is set on the parts (tri_batch_set_order)";
                 return TRI_OK;
@@ -2826,7 +2729,7 @@ static int cbatch_order_prepare(tri_cbatch *c) {
         char why[160];
         for (size_t i = 0; i < c->parts.size(); ++i) {
                 const tri_batch *p = c->parts[i];
-                if (!p->order_on)
+                if (!p->consumers[CONSUMER_ORDER].on)
                         snprintf(why, sizeof why, "part %zu has no order (tri_batch_set_order)", i);
                 else if (p->order.topk != p0->order.topk)
                         snprintf(why, sizeof why, "part %zu's order has topk %u, part 0's has %u", i, p->order.topk, p0->order.topk);
@@ -2865,7 +2768,7 @@ static int cbatch_order_merge(tri_cbatch *c) {
                 return TRI_OK;
         for (size_t i = 0; i < c->parts.size(); ++i) { // (an order replaced or removed between the run and the sync: the part selected nothing into the table's block)
                 const tri_batch *p = c->parts[i];
-                if (!p->order_on || !p->order_done || p->order_keys(p->order_lists) != c->order_src[i].keys) {
+                if (!p->consumers[CONSUMER_ORDER].on || !p->consumers[CONSUMER_ORDER].done || p->order_keys(p->order_lists) != c->order_src[i].keys) {
                         c->ordered = false;
                         c->order_why = "part " + std::to_string(i) + "'s order was replaced after tri_cbatch_run";
                         return TRI_OK;
@@ -3079,9 +2982,6 @@ extern "C" int tri_gather_results(tri_batch *b, tri_comm *c, void *counts_all, v
 // the encoders, commit and merge on the device: tri_encode_*, tri_commit_*, tri_merge_* and the scratch they allocate from
 #include "write_side.hpp"
 #include "isect_side.hpp"
-#include "facet_side.hpp"
-#include "stats_side.hpp"
-#include "order_side.hpp"
 #include "perc_side.hpp"
 
 #ifdef TRI_PROF
