@@ -1,8 +1,8 @@
 """GPU tests of the index's PLANE CACHE across a stream of batches (run with -m gpu on an MI355X): growth, reuse, overlap.
 
 Every other GPU test handles a batch as create, run, sync, read, close, on an index whose plane cache is in whatever state earlier tests left it.  The engine's callers
-keep several batches in flight on one index, and the cache (tri_index::d_pcache, d_pcache_hi and the phrase rank records) is mutable state shared by all of them:
-fit_plane_cache grows it without draining the engine stream, run_plane_rows builds only the rows whose parts are missing, run_phrases adds rank records row by row,
+keep several batches in flight on one index, and the cache (tri_index::planes: plane 0, the high region and the phrase rank records) is mutable state shared by all of them:
+PlaneCache::fit grows it without draining the engine stream, run_plane_rows builds only the rows whose parts are missing, run_phrases adds rank records row by row,
 tri_index_set_masked swaps the mask between runs.  A wrong copy length, a stale `built` bit or a mis-ordered event there gives wrong docID sets or scores, not a crash.
 
 Each test here drives a SEQUENCE of batches over ONE FRESHLY UPLOADED index of the `stream` corpus (tests/structured.py: twelve head terms of pairwise distinct
@@ -254,7 +254,7 @@ def growth_sequence(st):
 
 @pytest.mark.parametrize("codec", [1, 2])
 def test_growth_keeps_what_was_built(stream, codec):
-    """Rows built at capacity 2 are read at capacity 5 and 12 WITHOUT a rebuild (fit_plane_cache's copy of plane 0, its `built` bits kept), only the new rows are decoded
+    """Rows built at capacity 2 are read at capacity 5 and 12 WITHOUT a rebuild (PlaneCache::fit's copy of plane 0, its `built` bits kept), only the new rows are decoded
     at each growth, and the oldest batch, run again after both growths, decodes nothing and answers the same."""
     st = stream(codec, (2, 5, FULL))
     dA, dB, dC, again = growth_sequence(st)

@@ -282,6 +282,8 @@ static hipError_t event_get(tri_dev *dev, hipEvent_t *e) {
 
 // the owning handles over the calls above: DevMem, Pooled, Pinned, PooledEvent, DevRef
 #include "owners.hpp"
+// the index's plane cache: its rows' bookkeeping, its buffers, its growth (PlaneRows, PlaneCache)
+#include "plane_cache.hpp"
 
 // An arena's sections, each named ONCE: carve(view, bytes) points `view` at the next section and moves on by `bytes`, rounded up to `align`.  Without a base
 // (the sizing pass) no view is touched and only `at` advances; `have` == false: the object lacks the section — a null view, no room taken.
@@ -322,31 +324,7 @@ struct tri_index : HostIndex {
         DevMem<uint4> d_blk_rec;
         DevMem<uint32_t> d_masked; // bitmap over docIDs of the masked documents (nullptr: none); max_doc / 32 + 2 words
         DevMem<DevTerm> d_terms;
-        // ---- the term planes live with the index (they are a function of its lists alone): row r = the planes of the term of df rank r, built
-        //      by k_term_planes the first time a batch's run wants them and kept — a caller that compiles a batch per step does not decode the
-        //      same head terms step after step.  Two regions, built BY NEED (dev_structs.hpp: PL_HI): d_pcache holds every row's PLANE 0 (plw
-        //      words a row: all a DocumentsOnly batch reads), d_pcache_hi the rows' HIGH parts (nested planes 1 .. 3 + level words, PL_HI * plw
-        //      words a row) — allocated by the first scored batch that reads planes, a row's part built when such a batch names the row.  pc_cap
-        //      rows + one all-zero row (index pc_cap) in each region; pc_built[r]: bit 0 plane 0, bit 1 the high part, bit 2 the rank records — the build has been
-        //      enqueued on the engine stream (every later kernel of the stream sees it).  Grown (rows moved on the upload stream) when a batch is
-        //      planned with more eligible terms than it holds.
-        Pooled<uint32_t> d_pcache, d_pcache_hi; // (pooled, like the four below: tri_batch_create grows them without a device-wide synchronisation)
-        uint32_t pc_cap = 0, pc_plw = 0;
-        std::vector<uint8_t> pc_built;
-        // ... and what k_phrase needs to find a head term's hits WITHOUT walking its blocks (round 5): per row a RANK DIRECTORY over plane 0 — a 64-byte record per docID group g of 256 documents at d_prank[(row * (plw / 8) + g) * 16]:
-        // the posting index of the group's first document and the group's eight plane-0 words, filled by k_term_planes —, and per posting the hits locator and frequency entry
-        // phrase_locate_block would compute (d_phs[hs_off[row] + posting]; k_term_hits; GOOGLE, lists of full blocks).  d_term_row[term] = its row once both are there
-        Pooled<uint32_t> d_prank;
-        DevMem<uint32_t> d_term_row;
-        Pooled<unsigned long long> d_phs;
-        Pooled<uint64_t> d_hs_off;
-        Pooled<uint32_t> d_ph_pairs;      // (term, row) pairs of the rows whose hits entries were built, appended run after run (a row is built once: 2 * pc_cap words)
-        size_t ph_pairs_n = 0;
-        std::vector<uint64_t> hs_off;     // [pc_cap + 1]: prefix sums of the rows' document counts (row = df rank)
-        std::vector<uint8_t> ph_built;    // [pc_cap]: the row's hits entries have been enqueued
-        std::vector<uint32_t> rank_term;  // [pc_cap]: the term of df rank r
-        PooledEvent ev_pc_ready;                                // the last growth's move of the rows (upload stream): every run waits for it
-        std::vector<std::pair<Pooled<void>, PooledEvent>> pc_retired; // outgrown row buffers and the upload-stream point their last readers precede
+        PlaneCache planes; // the term planes of the head terms, built by need and kept from batch to batch (plane_cache.hpp)
         ~tri_index() { // also runs when tri_index_upload fails half-way; the members release themselves behind it
                 if (dev)
                         hipSetDevice(dev->device);
@@ -1013,150 +991,6 @@ extern "C" int tri_decode_hits_at(tri_index *ix, const uint32_t *terms, const ui
 }
 
 // ------------------------------------------------------------------------------------------ host: batches
-// The index's plane cache holds a row for every term the batch could name (row = df rank < plane_rows), plus an all-zero row: what a
-// k_planes slot WITHOUT term planes reads (so its sweep needs no select).  Grown WITHOUT draining the engine stream (round 4 synchronised
-// it here: a stall in the serving loop whenever a batch was planned with more eligible terms): the rows move on the upload stream behind
-// everything the engine stream holds so far (runs that read or build the old rows), later runs wait for the move's event (tri_batch_run),
-// and the old buffers are retired — pooled again once that point has passed.  Everything a growth needs is taken before the index is
-// touched, in local owners, and the index's members change hands behind the last call that can fail: an error anywhere leaves the index as it was and
-// hands back what was taken.
-static int fit_plane_cache(tri_batch *b, const bool planes_tasks) {
-        tri_index *ix = b->ix;
-        tri_dev *dev = b->dev;
-        const uint32_t want = std::max<uint32_t>(1, b->plane_rows);
-        // (rows whose readers are through go back to the pool: no call here waits for the device)
-        for (size_t i = 0; i < ix->pc_retired.size();)
-                if (hipEventQuery(ix->pc_retired[i].second) == hipSuccess)
-                        ix->pc_retired.erase(ix->pc_retired.begin() + (long)i);
-                else
-                        ++i;
-        // (does this batch read the rows' HIGH parts — a scored batch whose one-pass kernel or scorers read planes?)
-        b->planes_hi = planes_tasks || !b->splane.empty();
-        if (want <= ix->pc_cap && b->plw == ix->pc_plw && (!b->planes_hi || ix->d_pcache_hi))
-                return TRI_OK;
-        const size_t row = (size_t)b->plw * 4, row_hi = (size_t)PL_HI * b->plw * 4, groups = b->plw / 8;
-        const bool resize = want > ix->pc_cap || b->plw != ix->pc_plw; // (else: only the high region is new)
-        const bool new_hi = (b->planes_hi || ix->d_pcache_hi) && (resize || !ix->d_pcache_hi);
-        const bool same_plw = ix->d_pcache && b->plw == ix->pc_plw;
-        const uint32_t cap = std::max(want, b->plw == ix->pc_plw ? ix->pc_cap : 0u);
-        // the rank directories and hits entries of the rows (k_phrase's rank path): sized for every row the cache can hold, moved like the rows
-        std::vector<uint64_t> hs;
-        std::vector<uint32_t> rt;
-        if (resize) {
-                hs.assign(cap + 1, 0);
-                rt.assign(cap, 0xffffffffu);
-                for (size_t t = 0; t < ix->terms.size(); ++t)
-                        if (ix->df_rank[t] < cap)
-                                rt[ix->df_rank[t]] = (uint32_t)t;
-                for (uint32_t r = 0; r < cap; ++r)
-                        hs[r + 1] = hs[r] + (rt[r] != 0xffffffffu ? ix->terms[rt[r]].documents : 0u);
-        }
-        // the buffers this growth replaces, each retired on an event of its own (the rank directories go with the rows: same readers, and the copies below read them)
-        const size_t n_outgrown = (resize && ix->d_prank ? 4 : 0) + (resize && ix->d_pcache ? 1 : 0) + (new_hi && ix->d_pcache_hi ? 1 : 0);
-        // ---- take every buffer and event first
-        Pooled<uint32_t> fresh, fresh_hi, pairs, prank;
-        Pooled<unsigned long long> phs;
-        Pooled<uint64_t> hso;
-        DevMem<uint32_t> term_row;
-        PooledEvent drained, ready;
-        std::vector<PooledEvent> retire(n_outgrown);
-        hipError_t e = hipSuccess;
-        auto take = [&](auto &buf, const size_t bytes) { e = e == hipSuccess ? buf.alloc(dev, bytes) : e; };
-        if (resize)
-                take(fresh, ((size_t)cap + 1) * row + 64);
-        if (new_hi)
-                take(fresh_hi, ((size_t)cap + 1) * row_hi + 64);
-        if (resize) {
-                take(pairs, (size_t)cap * 8 + POOL_MIN_BYTES);
-                take(prank, (size_t)cap * groups * PL_RANK_WORDS * 4 + 64);
-                take(phs, (hs[cap] + 8) * 8);
-                take(hso, ((size_t)cap + 1) * 8 + POOL_MIN_BYTES);
-                if (e == hipSuccess && !ix->d_term_row)
-                        e = term_row.alloc((ix->terms.size() + 1) * 4);
-        }
-        if (e == hipSuccess)
-                e = drained.take(dev);
-        if (e == hipSuccess && !ix->ev_pc_ready)
-                e = ready.take(dev);
-        for (PooledEvent &r : retire)
-                if (e == hipSuccess)
-                        e = r.take(dev);
-        if (e != hipSuccess)
-                return fail(e == hipErrorOutOfMemory ? TRI_ERR_NOMEM : TRI_ERR_DEVICE, "tri_batch_create: growing the plane cache: %s", hipGetErrorString(e));
-        // ---- then the rows move: from the index's buffers, which stay in place, into the fresh ones
-        const hipEvent_t pc_ready = ready ? ready : ix->ev_pc_ready;
-        uint32_t *const d_term_row = term_row ? term_row : ix->d_term_row;
-        const int rc = [&]() -> int {
-                HIP_TRY(hipEventRecord(drained, dev->stream));
-                HIP_TRY(hipStreamWaitEvent(dev->stream_up, drained, 0));
-                if (fresh) {
-                        if (same_plw)
-                                HIP_TRY(hipMemcpyAsync(fresh, ix->d_pcache, (size_t)ix->pc_cap * row, hipMemcpyDeviceToDevice, dev->stream_up));
-                        HIP_TRY(hipMemsetAsync((uint8_t *)fresh.get() + (size_t)cap * row, 0, row + 64, dev->stream_up));
-                }
-                if (fresh_hi) {
-                        if (same_plw && ix->d_pcache_hi)
-                                HIP_TRY(hipMemcpyAsync(fresh_hi, ix->d_pcache_hi, (size_t)ix->pc_cap * row_hi, hipMemcpyDeviceToDevice, dev->stream_up));
-                        HIP_TRY(hipMemsetAsync((uint8_t *)fresh_hi.get() + (size_t)cap * row_hi, 0, row_hi + 64, dev->stream_up));
-                }
-                if (resize) {
-                        if (same_plw && ix->d_prank) {
-                                HIP_TRY(hipMemcpyAsync(pairs, ix->d_ph_pairs, ix->ph_pairs_n * 8, hipMemcpyDeviceToDevice, dev->stream_up));
-                                HIP_TRY(hipMemcpyAsync(prank, ix->d_prank, (size_t)ix->pc_cap * groups * PL_RANK_WORDS * 4, hipMemcpyDeviceToDevice, dev->stream_up));
-                                HIP_TRY(hipMemcpyAsync(phs, ix->d_phs, ix->hs_off[ix->pc_cap] * 8, hipMemcpyDeviceToDevice, dev->stream_up));
-                        }
-                        HIP_TRY(hipMemcpyAsync(hso, hs.data(), ((size_t)cap + 1) * 8, hipMemcpyHostToDevice, dev->stream_up)); // (hs outlives the copy: it becomes the member hs_off below)
-                        if (term_row || !same_plw)
-                                HIP_TRY(hipMemsetAsync(d_term_row, 0xff, (ix->terms.size() + 1) * 4, dev->stream_up));
-                }
-                HIP_TRY(hipEventRecord(pc_ready, dev->stream_up));
-                // the buffers this growth replaces are retired on events recorded on the UPLOAD stream, behind the copies that read them — that point is past
-                // the engine stream's earlier readers too (stream_up waits for `drained`).  (Round 5 retired them on events of the engine stream recorded
-                // BEFORE the copies were enqueued: the next tri_batch_create could pool a buffer the copy had not read yet.)
-                for (PooledEvent &r : retire)
-                        HIP_TRY(hipEventRecord(r, dev->stream_up));
-                return TRI_OK;
-        }();
-        if (rc) {
-                hipStreamSynchronize(dev->stream_up); // (the fresh buffers go back to the pool: no copy queued above may still be writing them)
-                return rc;
-        }
-        // ---- nothing below can fail: the index takes the fresh buffers, and what a member held is retired on the next event
-        size_t nret = 0;
-        auto swap_in = [&](auto &member, auto &with) {
-                if (member)
-                        ix->pc_retired.emplace_back(Pooled<void>(member.release(), FreePooled{dev}), std::move(retire[nret++]));
-                member = std::move(with);
-        };
-        if (resize) {
-                if (!same_plw)
-                        ix->pc_built.clear();
-                if (!(same_plw && ix->d_prank)) { // (no rank directory was there to move)
-                        ix->ph_built.clear();
-                        ix->ph_pairs_n = 0;
-                }
-                ix->hs_off = std::move(hs); // (a row's offset depends on the rows before it alone: what was built stays where it was)
-                swap_in(ix->d_prank, prank), swap_in(ix->d_phs, phs), swap_in(ix->d_hs_off, hso), swap_in(ix->d_ph_pairs, pairs);
-                swap_in(ix->d_pcache, fresh);
-                if (term_row)
-                        ix->d_term_row = std::move(term_row);
-                ix->rank_term = std::move(rt);
-                ix->ph_built.resize(cap, 0);
-        }
-        if (new_hi) {
-                if (!(same_plw && ix->d_pcache_hi))
-                        for (auto &bb : ix->pc_built)
-                                bb &= (uint8_t)~2u; // (no row has its high part yet)
-                swap_in(ix->d_pcache_hi, fresh_hi);
-        }
-        if (ready)
-                ix->ev_pc_ready = std::move(ready);
-        ix->pc_cap = cap;
-        ix->pc_plw = b->plw;
-        ix->pc_built.resize(cap, 0);
-        return TRI_OK;
-}
-
 // tri_batch_create = the host planner (planner.hpp: lowering, execution classes, tasks, term planes, schedule — on the device handle's
 // host threads) + the plan's way to the device: ONE pinned block, ONE arena, ONE copy on the upload stream.  Everything a steady caller
 // needs per batch comes from the handle's pools (arena, pinned block, output regions, events): no hipMalloc, no hipFree, no device
@@ -1304,9 +1138,11 @@ static int create_buffers(tri_batch *b, const PlanInput &in, Lap &&lap) {
         tri_dev *dev = b->dev;
         const uint64_t off = b->out_capacity;
         const bool planes_tasks = b->n_planes + b->n_planes8 != 0, scored = batch_scored(b);
-        if (!b->plane_terms.empty() || planes_tasks)
-                if (const int rc = fit_plane_cache(b, planes_tasks))
+        if (!b->plane_terms.empty() || planes_tasks) {
+                b->planes_hi = planes_tasks || !b->splane.empty(); // (a scored batch whose one-pass kernel or scorers read planes)
+                if (const int rc = b->ix->planes.fit(dev, *b->ix, b->plane_rows, b->plw, b->planes_hi))
                         return rc;
+        }
         if (planes_tasks) {
                 const uint64_t wgs = std::min<uint64_t>(std::max(b->n_planes, b->n_planes8), (uint64_t)dev->cus * PLK_WGS_PER_CU);
                 HIP_TRY(b->d_sparse.alloc(dev, (2 * wgs * b->sparse_cap + 64) * 4)); // (per workgroup: the lists' entries, then their frequencies)
@@ -1450,6 +1286,15 @@ static void tri_launch_matching(const tri_batch *b, const int kernel, const int 
 // where the rows' source pointers lie in d_filter_tab: behind the row ids of the plan's slots
 static size_t filter_tab_ptrs_off(const tri_batch *b) { return (b->plan.size() * 4 + 15) & ~(size_t)15; }
 
+// A launch with a row per gridDim.y, cut to the limit of 65535: launch(y0, ny) enqueues rows y0 .. y0 + ny, cut after cut; the first error ends it
+template <class Launch>
+static int for_grid_y(const uint32_t n, Launch &&launch) {
+        for (uint32_t y0 = 0; y0 < n; y0 += 65535u)
+                if (const int rc = launch(y0, std::min(65535u, n - y0)))
+                        return rc;
+        return TRI_OK;
+}
+
 // a batch with filters: the rows its queries select from — every named filter OR-ed with the index's masked documents AS THEY STAND NOW (the set a batch
 // sees is the one in place when it runs) — in one launch, before anything reads them (timed with the plane rows)
 static int run_filter_rows(tri_batch *b) {
@@ -1458,12 +1303,12 @@ static int run_filter_rows(tri_batch *b) {
         tri_dev *dev = b->dev;
         const size_t n4 = filter_words(b->ix) / 4;
         const uint32_t nrows = (uint32_t)b->filter_rows.size();
-        for (uint32_t y0 = 0; y0 < nrows; y0 += 65535u) { // (gridDim.y <= 65535)
-                hipLaunchKernelGGL(k_filter_rows, dim3((unsigned)std::min<size_t>((n4 + FILTER_WG - 1) / FILTER_WG, 1024), std::min(65535u, nrows - y0)), dim3(FILTER_WG), 0, dev->stream,
+        return for_grid_y(nrows, [&](const uint32_t y0, const uint32_t ny) -> int {
+                hipLaunchKernelGGL(k_filter_rows, dim3((unsigned)std::min<size_t>((n4 + FILTER_WG - 1) / FILTER_WG, 1024), ny), dim3(FILTER_WG), 0, dev->stream,
                                    (const uint4 *const *)(b->d_filter_tab + filter_tab_ptrs_off(b)) + y0, (const uint4 *)b->ix->d_masked.get(), (uint4 *)b->d_filter_rows.get() + (size_t)y0 * n4, n4);
                 HIP_TRY(hipGetLastError());
-        }
-        return TRI_OK;
+                return TRI_OK;
+        });
 }
 
 // the head terms the batch's queries share: the rows of the index's plane cache that no earlier run has built are decoded now — once for the
@@ -1471,35 +1316,25 @@ static int run_filter_rows(tri_batch *b) {
 static int run_plane_rows(tri_batch *b) {
         tri_dev *dev = b->dev;
         tri_index *ix = b->ix;
-        b->info.term_planes_decoded_bytes = 0;
-        if (!b->plane_terms.empty()) {
-                std::vector<uint32_t> build;
-                const uint8_t needs = b->planes_hi ? 3u : 1u; // (bit 0: plane 0; bit 1: the row's high part — scored batches only)
-                for (const uint32_t term : b->plane_terms) {
-                        const uint32_t row = ix->df_rank[term];
-                        if (row < ix->pc_cap && ((ix->pc_built[row] & needs) != needs || dev->opt.planes_rebuild)) {
-                                build.push_back(term);
-                                build.push_back(row);
-                                b->info.term_planes_decoded_bytes += ix->docbytes[term];
-                        }
-                }
-                if (!build.empty()) {
-                        HIP_TRY(hipMemcpyAsync(b->d_build, build.data(), build.size() * 4, hipMemcpyHostToDevice, dev->stream)); // (pageable source: staged before the call returns)
-                        const uint32_t nrows = (uint32_t)(build.size() / 2), nwin = b->plw / PL_WORDS;
-                        for (uint32_t y0 = 0; y0 < nrows; y0 += 65535u) { // (gridDim.y <= 65535)
-                                const uint32_t ny = std::min(65535u, nrows - y0);
-                                if (b->planes_hi) // (a row that gains its high part is decoded whole again: plane 0 is rewritten with the words it holds)
-                                        TRI_LAUNCH(k_term_planes, ix->codec, dim3(nwin, ny), dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
-                                                   ix->d_blk_doff, ix->d_win, ix->d_terms, (const uint32_t *)b->d_build + 2 * (size_t)y0, ix->d_pcache, (size_t)b->plw, ix->d_pcache_hi,
-                                                   (size_t)PL_HI * b->plw, b->plw, (uint32_t *)nullptr);
-                                else // plane 0 alone, P0_GROUP windows to a workgroup (the rank records: built when a phrase batch asks for them, run_phrases)
-                                        TRI_LAUNCH(k_term_plane0, ix->codec, dim3((nwin + P0_GROUP - 1) / P0_GROUP, ny), dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off,
-                                                   ix->d_blk_rec, ix->d_blk_doff, ix->d_win, ix->d_terms, (const uint32_t *)b->d_build + 2 * (size_t)y0, ix->d_pcache, b->plw, (uint32_t *)nullptr);
-                                HIP_TRY(hipGetLastError());
-                        }
-                        for (size_t i = 1; i < build.size(); i += 2)
-                                ix->pc_built[build[i]] |= needs;
-                }
+        PlaneCache &pc = ix->planes;
+        const std::vector<uint32_t> build = pc.missing_rows(*ix, b->plane_terms.data(), b->plane_terms.size(), b->planes_hi, dev->opt.planes_rebuild, b->info.term_planes_decoded_bytes);
+        if (!build.empty()) {
+                HIP_TRY(hipMemcpyAsync(b->d_build, build.data(), build.size() * 4, hipMemcpyHostToDevice, dev->stream)); // (pageable source: staged before the call returns)
+                const uint32_t nwin = b->plw / PL_WORDS;
+                const int rc = for_grid_y((uint32_t)(build.size() / 2), [&](const uint32_t y0, const uint32_t ny) -> int {
+                        if (b->planes_hi) // (a row that gains its high part is decoded whole again: plane 0 is rewritten with the words it holds)
+                                TRI_LAUNCH(k_term_planes, ix->codec, dim3(nwin, ny), dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
+                                           ix->d_blk_doff, ix->d_win, ix->d_terms, (const uint32_t *)b->d_build + 2 * (size_t)y0, pc.plane0(), (size_t)b->plw, pc.high(),
+                                           (size_t)PL_HI * b->plw, b->plw, (uint32_t *)nullptr);
+                        else // plane 0 alone, P0_GROUP windows to a workgroup (the rank records: built when a phrase batch asks for them, run_phrases)
+                                TRI_LAUNCH(k_term_plane0, ix->codec, dim3((nwin + P0_GROUP - 1) / P0_GROUP, ny), dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off,
+                                           ix->d_blk_rec, ix->d_blk_doff, ix->d_win, ix->d_terms, (const uint32_t *)b->d_build + 2 * (size_t)y0, pc.plane0(), b->plw, (uint32_t *)nullptr);
+                        HIP_TRY(hipGetLastError());
+                        return TRI_OK;
+                });
+                if (rc)
+                        return rc;
+                pc.mark_built(build, b->planes_hi);
         }
         HIP_TRY(hipEventRecord(b->ev[EV_PLANE_ROWS], dev->stream));
         return TRI_OK;
@@ -1552,7 +1387,7 @@ static int run_matching(tri_batch *b) {
         if (b->n_dense) {
                 tri_launch_matching(b, FK_AND_DENSE, 0, [](auto c) { return k_and_dense<c.value>; }, dim3(std::min<uint32_t>(b->n_dense, (uint32_t)dev->cus * dense_wgs)), dim3(DENSE_WG), dev->stream, match_bytes, ix->d_blk_last,
                            match_off, ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->sched) + trip::sched_first(*b, TASK_DENSE), b->dev_at(b->qterms), b->n_dense,
-                           b->d_ticket + TICKET_DENSE_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->dev_opt(b->qplane), (const uint32_t *)ix->d_pcache, b->plw);
+                           b->d_ticket + TICKET_DENSE_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->dev_opt(b->qplane), (const uint32_t *)ix->planes.plane0(), b->plw);
                 HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(b->ev[EV_DENSE], dev->stream));
@@ -1563,7 +1398,7 @@ static int run_matching(tri_batch *b) {
                 const uint32_t pset_wgs = TRI_PSET_WAVES * 256 / PSET_WG;
                 tri_launch_matching(b, FK_PSETS, 0, [](auto c) { return k_psets<c.value>; }, dim3(std::min<uint32_t>(b->n_pset, (uint32_t)dev->cus * (overlap && dev->opt.overlap_dense_wgs ? std::min<uint32_t>(dense_wgs, pset_wgs) : pset_wgs))),
                            dim3(PSET_WG), dev->stream, units, pset_sched, b->n_pset, b->d_ticket + TICKET_PSET_WORD, (const uint32_t *)b->dev_at(b->qterms), (const uint32_t *)b->dev_opt(b->qplane), b->d_out,
-                           b->d_counts, ix->d_masked, (const uint32_t *)ix->d_pcache, b->plw, (const uint32_t *)b->d_scat_off, (const uint32_t *)b->d_scat_cnt,
+                           b->d_counts, ix->d_masked, (const uint32_t *)ix->planes.plane0(), b->plw, (const uint32_t *)b->d_scat_off, (const uint32_t *)b->d_scat_cnt,
                            (const uint32_t *)b->d_scat_docs);
                 HIP_TRY(hipGetLastError());
         }
@@ -1573,14 +1408,14 @@ static int run_matching(tri_batch *b) {
                 // its units run behind k_psets' in pset_sched[]
                 tri_launch_matching(b, FK_PROBE, 0, [](auto c) { return k_probe<c.value>; }, dim3(std::min<uint32_t>((b->n_probe + PROBE_WG / 64 - 1) / (PROBE_WG / 64), (uint32_t)dev->cus * (TRI_PROBE_WAVES * 256 / PROBE_WG))),
                            dim3(PROBE_WG), dev->stream, match_bytes, ix->d_blk_last, match_off, ix->d_terms, units, pset_sched + b->n_pset, b->n_probe, b->d_ticket + TICKET_PROBE_WORD,
-                           (const uint32_t *)b->dev_at(b->qterms), (const uint32_t *)b->dev_opt(b->qplane), b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)ix->d_pcache, b->plw);
+                           (const uint32_t *)b->dev_at(b->qterms), (const uint32_t *)b->dev_opt(b->qplane), b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)ix->planes.plane0(), b->plw);
                 HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(b->ev[EV_PROBE], dev->stream));
         if (b->n_cand)
                 tri_launch_matching(b, FK_AND, 0, [](auto c) { return k_and<c.value>; }, dim3(std::min<uint32_t>(b->n_cand, (uint32_t)dev->cus * cand_wgs)), dim3(AND_WG), cand_stream, match_bytes, ix->d_blk_last, match_off,
                            ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->sched) + trip::sched_first(*b, TASK_CAND), b->dev_at(b->qterms), b->dev_at(b->cand_q),
-                           b->d_ticket + TICKET_CAND_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->dev_opt(b->qplane), (const uint32_t *)ix->d_pcache, b->plw);
+                           b->d_ticket + TICKET_CAND_WORD, b->d_out, b->d_counts, ix->d_masked, (const uint32_t *)b->dev_opt(b->qplane), (const uint32_t *)ix->planes.plane0(), b->plw);
         HIP_TRY(hipGetLastError());
         if (overlap) {
                 HIP_TRY(hipEventRecord(dev->ev_join, dev->stream2));
@@ -1626,7 +1461,7 @@ static int run_planes(tri_batch *b) {
                            dim3(std::min<uint32_t>(np, (uint32_t)dev->cus * PLK_WGS_PER_CU)), dim3(PLK_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec,
                            ix->d_blk_doff, ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->fused), b->dev_at(b->tasks), (const uint32_t *)b->dev_at(b->sched) + trip::sched_first(*b, kind), b->dev_at(b->sterms),
                            b->dev_at(b->sweights), np, b->d_ticket + TICKET_PLANES_WORD + 2 * wide, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, ix->d_masked,
-                           b->similarity, (const uint32_t *)ix->d_pcache, (const uint32_t *)ix->d_pcache_hi, b->plw, ix->pc_cap, b->d_sparse, b->sparse_cap, b->d_qthr);
+                           b->similarity, (const uint32_t *)ix->planes.plane0(), (const uint32_t *)ix->planes.high(), b->plw, ix->planes.cap(), b->d_sparse, b->sparse_cap, b->d_qthr);
                 HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(b->ev[EV_PLANES], dev->stream));
@@ -1637,46 +1472,34 @@ static int run_planes(tri_batch *b) {
 static int run_phrases(tri_batch *b) {
         tri_dev *dev = b->dev;
         tri_index *ix = b->ix;
-        if (!b->ptasks.empty() && ix->codec == TRI_CODEC_GOOGLE && ix->d_prank && ix->pc_cap) {
+        PlaneCache &pc = ix->planes;
+        if (!b->ptasks.empty() && ix->codec == TRI_CODEC_GOOGLE) {
                 // the phrases' head terms are located by RANK in plane 0 (k_phrase.hpp): rows (plane 0 + rank directory) and per-posting hits entries of the
                 // phrase terms that have none yet are built now — once for the index
-                std::vector<uint32_t> hits_build, hits_only; // (term, row) pairs: the rows that also need their rank records FIRST, then the ones that have them
-                uint32_t max_blocks = 0;
-                for (size_t i = 0; i < b->pterms.size(); ++i) {
-                        const uint32_t term = b->pterms[i], r = ix->df_rank[term];
-                        if (r >= ix->pc_cap || ix->ph_built[r])
-                                continue;
-                        const DevTerm &t = ix->terms[term];
-                        if (!(t.flags & TERM_FULL_BLOCKS) || !t.documents)
-                                continue;
-                        ix->ph_built[r] = 1;
-                        max_blocks = std::max(max_blocks, t.nblocks);
-                        std::vector<uint32_t> &dst = (ix->pc_built[r] & 4u) ? hits_only : hits_build; // (bit 2: the row's rank records — with them plane 0, if it is not there yet)
-                        ix->pc_built[r] |= 5u;
-                        dst.push_back(term);
-                        dst.push_back(r);
-                }
-                const uint32_t nrows_build = (uint32_t)(hits_build.size() / 2);
-                hits_build.insert(hits_build.end(), hits_only.begin(), hits_only.end());
-                if (!hits_build.empty()) {
-                        uint32_t *d_pairs = ix->d_ph_pairs + 2 * ix->ph_pairs_n; // (every row is built once: the pairs of all runs fit 2 * pc_cap words)
-                        HIP_TRY(hipMemcpyAsync(d_pairs, hits_build.data(), hits_build.size() * 4, hipMemcpyHostToDevice, dev->stream)); // (pageable source: staged before the call returns)
-                        ix->ph_pairs_n += hits_build.size() / 2;
-                        // the rows without rank records: plane 0 + records in ONE launch over the list's head (round 5 launched a grid per row: 711 launches, 11 ms, the
-                        // first time cfg4's phrases met an index)
-                        for (uint32_t y0 = 0; y0 < nrows_build; y0 += 65535u) {
-                                const dim3 grid((b->plw / PL_WORDS + P0_GROUP - 1) / P0_GROUP, std::min(65535u, nrows_build - y0));
-                                TRI_LAUNCH(k_term_plane0, ix->codec, grid, dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec, ix->d_blk_doff, ix->d_win,
-                                           ix->d_terms, (const uint32_t *)d_pairs + 2 * (size_t)y0, ix->d_pcache, b->plw, ix->d_prank);
-                                HIP_TRY(hipGetLastError());
-                        }
-                        const uint32_t npairs = (uint32_t)(hits_build.size() / 2);
-                        for (uint32_t y0 = 0; y0 < npairs; y0 += 65535u) { // (gridDim.y <= 65535: a small index at a high plane_div makes almost every term eligible)
-                                hipLaunchKernelGGL(k_term_hits, dim3((max_blocks + 255) / 256, std::min(65535u, npairs - y0)), dim3(256), 0, dev->stream, ix->d_index, ix->d_blk_off,
-                                                   ix->d_blk_hits, ix->d_terms, (const uint32_t *)d_pairs + 2 * (size_t)y0, (const uint64_t *)ix->d_hs_off, ix->d_phs, ix->d_term_row);
-                                HIP_TRY(hipGetLastError());
-                        }
-                }
+                PhraseRows pr;
+                const uint32_t *d_pairs = nullptr;
+                if (const int rc = pc.phrase_rows(*ix, b->pterms.data(), b->pterms.size(), dev->stream, pr, &d_pairs))
+                        return rc;
+                // plane 0 + rank records in ONE launch over the list (a grid per row was 711 launches, 11 ms, the first time cfg4's phrases met an index)
+                const uint32_t npairs = (uint32_t)(pr.pairs.size() / 2);
+                int rc = for_grid_y(npairs, [&](const uint32_t y0, const uint32_t ny) -> int {
+                        const dim3 grid((b->plw / PL_WORDS + P0_GROUP - 1) / P0_GROUP, ny);
+                        TRI_LAUNCH(k_term_plane0, ix->codec, grid, dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec, ix->d_blk_doff, ix->d_win,
+                                   ix->d_terms, d_pairs + 2 * (size_t)y0, pc.plane0(), b->plw, pc.rank());
+                        HIP_TRY(hipGetLastError());
+                        return TRI_OK;
+                });
+                if (rc)
+                        return rc;
+                // (a small index at a high plane_div makes almost every term eligible)
+                rc = for_grid_y(npairs, [&](const uint32_t y0, const uint32_t ny) -> int {
+                        hipLaunchKernelGGL(k_term_hits, dim3((pr.max_blocks + 255) / 256, ny), dim3(256), 0, dev->stream, ix->d_index, ix->d_blk_off, ix->d_blk_hits, ix->d_terms,
+                                           d_pairs + 2 * (size_t)y0, (const uint64_t *)pc.hits_off(), pc.hits(), pc.term_row());
+                        HIP_TRY(hipGetLastError());
+                        return TRI_OK;
+                });
+                if (rc)
+                        return rc;
         }
         if (!b->ptasks.empty()) {
                 const uint32_t np = (uint32_t)b->ptasks.size();
@@ -1684,8 +1507,8 @@ static int run_phrases(tri_batch *b) {
                            ix->d_blk_hits, ix->d_hdir, ix->d_blk_last, ix->d_blk_off, ix->d_win, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->ptasks), np, b->dev_at(b->phrases), b->dev_at(b->pterms),
                            b->d_ticket + TICKET_PHRASE_WORD, b->d_out, b->d_counts, b->d_pscore,
                            (b->flags & TRI_FLAG_ACCUMULATED_SCORE) ? 65535u : 1u, // exec.cpp:296 trackCnt
-                           b->similarity, (const uint32_t *)ix->d_pcache, ix->pc_plw, (const uint32_t *)ix->d_prank, (const unsigned long long *)ix->d_phs,
-                           (const uint64_t *)ix->d_hs_off, ix->codec == TRI_CODEC_GOOGLE ? (const uint32_t *)ix->d_term_row : nullptr);
+                           b->similarity, (const uint32_t *)pc.plane0(), pc.plw(), (const uint32_t *)pc.rank(), (const unsigned long long *)pc.hits(),
+                           (const uint64_t *)pc.hits_off(), ix->codec == TRI_CODEC_GOOGLE ? (const uint32_t *)pc.term_row() : nullptr);
                 HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipEventRecord(b->ev[EV_PHRASE], dev->stream));
@@ -1702,13 +1525,15 @@ static int run_trees(tri_batch *b) {
                 const uint32_t nchunks = (plw + TREE_CHUNK_WORDS - 1) / TREE_CHUNK_WORDS;
                 const uint32_t *tsched = b->dev_at(b->sched) + trip::sched_first(*b, TASK_TREE);
                 const uint32_t *d_tree = b->dev_at(b->tree);
-                for (uint32_t y0 = 0; y0 < nterms; y0 += 65535u) { // (gridDim.y <= 65535)
-                        const dim3 grid(plw / PL_WORDS, std::min(65535u, nterms - y0));
-                        TRI_LAUNCH(k_term_planes, ix->codec, grid, dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec, ix->d_blk_doff, ix->d_win,
+                int rc = for_grid_y(nterms, [&](const uint32_t y0, const uint32_t ny) -> int {
+                        TRI_LAUNCH(k_term_planes, ix->codec, dim3(plw / PL_WORDS, ny), dim3(AND_WG), dev->stream, ix->d_index, ix->d_blk_last, ix->d_blk_off, ix->d_blk_rec, ix->d_blk_doff, ix->d_win,
                                    ix->d_terms, (const uint32_t *)b->d_tree_build + 2 * (size_t)y0, b->d_tree_rows, (size_t)PL_PLANES * plw, b->d_tree_rows + plw,
                                    (size_t)PL_PLANES * plw, plw, (uint32_t *)nullptr); // (a tree row keeps its two parts side by side: plane k at k * plw)
                         HIP_TRY(hipGetLastError());
-                }
+                        return TRI_OK;
+                });
+                if (rc)
+                        return rc;
                 if (nhid) {
                         HIP_TRY(hipMemsetAsync(b->d_tree_prows, 0, (size_t)nhid * plw * 4, dev->stream));
                         hipLaunchKernelGGL(k_tree_gather, dim3(nhid), dim3(TREE_WG), 0, dev->stream, b->dev_at(b->plan), b->dev_at(b->tasks), b->dev_at(b->tree_hidden), b->d_out,
@@ -1719,9 +1544,7 @@ static int run_trees(tri_batch *b) {
                 double *tscores = !scored_run ? nullptr : b->topk ? (double *)b->d_tree_scores : (double *)b->d_all_scores;
                 // the section's narrow records first (k_tree.hpp), then its wide ones (k_tree_wide.hpp: split_tree_section put them last); k_tree_expand reads no record
                 const uint32_t n_narrow = b->n_tree - b->n_tree_wide;
-                for (uint32_t y0 = 0; y0 < b->n_tree;) {
-                        const bool wide = y0 >= n_narrow;
-                        const uint32_t ny = std::min(65535u, (wide ? b->n_tree : n_narrow) - y0);
+                const auto eval = [&](const bool wide, const uint32_t y0, const uint32_t ny) -> int {
                         const dim3 grid(nchunks, ny);
                         uint32_t *qbits = b->d_tree_qbits + (size_t)y0 * plw, *cc = b->d_tree_cc + (size_t)y0 * nchunks;
 #define TREE_EVAL_ARGS b->dev_at(b->plan), b->dev_at(b->tasks), tsched + y0, d_tree, (const uint32_t *)b->d_tree_rows, (const uint32_t *)b->d_tree_prows, (const uint32_t *)ix->d_masked, qbits, cc, plw, filter_sel(b)
@@ -1745,8 +1568,12 @@ static int run_trees(tri_batch *b) {
 #undef TREE_LEAVES_ARGS
                         }
                         HIP_TRY(hipGetLastError());
-                        y0 += ny;
-                }
+                        return TRI_OK;
+                };
+                if ((rc = for_grid_y(n_narrow, [&](const uint32_t y0, const uint32_t ny) { return eval(false, y0, ny); })))
+                        return rc;
+                if ((rc = for_grid_y(b->n_tree_wide, [&](const uint32_t y0, const uint32_t ny) { return eval(true, n_narrow + y0, ny); })))
+                        return rc;
                 if (scored_run && b->topk) {
                         hipLaunchKernelGGL(k_tree_topk, dim3(b->n_tree), dim3(AND_WG), 0, dev->stream, tsched, b->dev_at(b->tasks), (const uint32_t *)b->d_out, (const uint32_t *)b->d_counts,
                                            (const double *)tscores, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts);
@@ -1812,7 +1639,7 @@ static int run_scores(tri_batch *b) {
                            ix->d_blk_off, ix->d_terms, b->dev_at(b->plan), b->dev_at(b->tasks), (const uint32_t *)b->d_score_order, b->dev_at(b->sterms), b->dev_at(b->sweights), nlegacy,
                            b->d_ticket + TICKET_SCORE_WORD, b->d_out, b->d_counts, b->topk, b->d_part_docs, b->d_part_scores, b->d_part_counts, b->d_all_scores, b->d_pscore,
                            b->similarity, ix->d_win, b->dev_opt(b->splane),
-                           (const uint32_t *)ix->d_pcache_hi, b->plw); // (the scorers read the level words: the rows' high parts)
+                           (const uint32_t *)ix->planes.high(), b->plw); // (the scorers read the level words: the rows' high parts)
         }
         HIP_TRY(hipGetLastError());
         const uint32_t nqs = (uint32_t)b->plan.size();
@@ -1869,8 +1696,8 @@ extern "C" int tri_batch_run(tri_batch *b) {
         }
 #endif
         HIP_TRY(hipStreamWaitEvent(dev->stream, b->ev[EV_UP], 0)); // the plan's copy (upload stream) has arrived
-        if (b->ix->ev_pc_ready)
-                HIP_TRY(hipStreamWaitEvent(dev->stream, b->ix->ev_pc_ready, 0)); // ... and so have the plane cache's rows, should it have been grown since
+        if (b->ix->planes.ready())
+                HIP_TRY(hipStreamWaitEvent(dev->stream, b->ix->planes.ready(), 0)); // ... and so have the plane cache's rows, should it have been grown since
         HIP_TRY(hipEventRecord(b->ev[EV_START], dev->stream));
         if (b->tasks.empty()) {
                 for (int e = EV_PLANE_ROWS; e <= EV_TREE; ++e)
