@@ -48,7 +48,9 @@ extern "C" {
                                 (order by a column: per query the first topk documents of its docID set by a column's value, selected on the device; no existing struct grew);
                                 within 9: tri_batch_set_stats / tri_batch_stats / tri_cbatch_stats, read-only option stats_last_us
                                 (stats of a column: per query and bucket the count, sum, min and max of a value column over the docID set, aggregated on the device; no existing
-                                struct grew) */
+                                struct grew);
+                                within 9: tri_filters_from_columns / tri_filter_bitmap (column predicates as document filters: RANGE / SET clauses over resident columns
+                                become drop bitmaps on the device; any filter's bitmap read back; no existing struct grew) */
 
 /* status codes */
 #define TRI_OK 0
@@ -426,6 +428,48 @@ int tri_batch_set_stats(tri_batch *, const tri_stat *stats, size_t n /* 0: clear
 int tri_batch_stats(tri_batch *, size_t k, uint64_t *sums, uint32_t *counts, uint32_t *mins, uint32_t *maxs /* each [nq][nbuckets_k + 1], caller query order; NULL: skipped */,
                     size_t cap /* records */);
 /* (tri_cbatch_stats is declared with the collection's calls below) */
+
+/* ---- column predicates as document filters ----------------------------------------------------------
+ * exec_query's IndexDocumentsFilter (matches.h:190-201; tested before consider(): exec.cpp:1133-1150) where the application's rule reads the documents' attributes —
+ * "price between 10 and 50, in stock, category in {3, 17, 40}" — and those attributes are columns already resident in HBM (tri_column_create): the predicates
+ * become drop bitmaps on the device, in one launch that reads every distinct column once; no docID list crosses PCIe.
+ *
+ * tri_filters_from_columns (matches.h:190-201 / exec.cpp:1133-1150): for each document d in 1 .. max_doc predicate p HOLDS when every one (any == 0) or at least
+ * one (any != 0) of its clauses holds; a clause holds where its test is true (negate == 0) or false (negate != 0).  RANGE: lo <= values[d] <= hi, unsigned, both ends
+ * inclusive, lo > hi true for no document.  SET: values[d] is one of set[0 .. nset); a value at or above TRI_FACET_MAX_BUCKETS is in no set.
+ * mode TRI_FILTER_KEEP: the documents where p holds are the only ones a query may match; TRI_FILTER_DROP: they are dropped.  In both, whatever the `also`
+ * filter drops is dropped as well.  out[i] is an ordinary tri_filter — the lifetime rules of tri_filter_create, used in tri_batch_set_filters and in the parts
+ * of a tri_cbatch like one — that does not reference the columns, the `also` filters or the caller's arrays once the call has returned; the call returns when
+ * all np bitmaps stand, and produces all np filters or none.
+ * TRI_ERR_INVALID, nothing allocated, out untouched, the message naming the predicate and the clause: a null argument (preds, out, a predicate's clauses, a
+ * clause's column, a SET's set with nset != 0), np of 0 or above TRI_PREDS_MAX, a column or an `also` filter of another index, more than TRI_PRED_MAX_COLUMNS
+ * distinct columns across the call, nclauses out of range, an unknown kind, a SET value at or above TRI_FACET_MAX_BUCKETS, a non-zero reserved field, a bad mode.
+ * TRI_ERR_NOMEM, out untouched, when the handle's pool cannot supply the np bitmaps.
+ * tri_filter_bitmap (matches.h:190-201 / exec.cpp:1133-1150: what filter(id) answers, for every id at once): the drop bitmap of ANY filter, however it was made —
+ * bit d & 31 of words[d >> 5] is document d, set: dropped.  *nwords receives the extent ((max_doc / 131072 + 2) * 4096 words), also when the call is refused
+ * for cap below it (TRI_ERR_INVALID, nothing written to words).  Bit 0 and the bits past max_doc are unspecified: no kernel tests them.  One device-to-host copy
+ * behind the engine stream. */
+#define TRI_PRED_MAX_CLAUSES 8   /* per predicate */
+#define TRI_PRED_MAX_COLUMNS 8   /* distinct columns per call */
+#define TRI_PREDS_MAX        256 /* predicates per call */
+#define TRI_CLAUSE_RANGE 0       /* lo <= values[d] <= hi, unsigned, both ends inclusive; lo > hi: holds for no document */
+#define TRI_CLAUSE_SET   1       /* values[d] is one of set[0 .. nset); every set value < TRI_FACET_MAX_BUCKETS */
+typedef struct tri_clause {
+        tri_column *column;
+        uint32_t kind, negate;   /* negate != 0: the clause holds where the test fails */
+        uint32_t lo, hi;         /* RANGE */
+        const uint32_t *set;     /* SET: any order, duplicates allowed, nset == 0 legal (holds for no document) */
+        uint32_t nset, reserved; /* reserved 0 */
+} tri_clause;
+typedef struct tri_predicate {
+        const tri_clause *clauses;
+        uint32_t nclauses;       /* 1 .. TRI_PRED_MAX_CLAUSES */
+        uint32_t any;            /* 0: every clause holds (AND); != 0: at least one (OR) */
+        const tri_filter *also;  /* optional, same index: what it drops the result drops too */
+        uint64_t reserved;       /* 0 */
+} tri_predicate;
+int tri_filters_from_columns(tri_index *, const tri_predicate *preds, size_t np, int mode, tri_filter **out /* [np] */);
+int tri_filter_bitmap(const tri_filter *, uint32_t *words, size_t cap /* words */, size_t *nwords);
 
 /* ---- postings decode (codec seam) -----------------------------------------------------------------
  * Replaces Codecs::PostingsListIterator::next() driven to exhaustion (google_codec.cpp:777-819,

@@ -34,7 +34,7 @@ def hipcc():
 
 
 def build_hip(force=False):
-    if force or _newer(LIB_HIP, _deps(HIP_SRCS) + [os.path.join(PKG, "csrc", "host", n) for n in ("result_rows.hpp", "isect_rows.hpp", "perc_lower.hpp", "facet_rows.hpp", "order_rows.hpp", "stats_rows.hpp")]):  # (read_side.hpp's host transforms, isect_side.hpp's replay, perc_side.hpp's lowering, read_side.hpp's sum of a collection's facet rows, split of an ordered row's keys and combine of a collection's stats rows)
+    if force or _newer(LIB_HIP, _deps(HIP_SRCS) + [os.path.join(PKG, "csrc", "host", n) for n in ("result_rows.hpp", "isect_rows.hpp", "perc_lower.hpp", "facet_rows.hpp", "order_rows.hpp", "stats_rows.hpp", "column_pred.hpp")]):  # (read_side.hpp's host transforms, isect_side.hpp's replay, perc_side.hpp's lowering, read_side.hpp's sum of a collection's facet rows, split of an ordered row's keys, combine of a collection's stats rows, colfilter_side.hpp's validation of column predicates)
         cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-o", LIB_HIP] + HIP_SRCS + ["-ldl"]
         subprocess.run(cmd, check=True)
     return LIB_HIP
@@ -230,10 +230,27 @@ def build_mirror_stats_test(force=False):
     return MIRROR_STATS_BIN
 
 
+MIRROR_COLFILTER_SRC = os.path.join(ROOT, "tests", "cpp", "host_mirror_colfilter_test.cpp")
+MIRROR_COLFILTER_BIN = os.path.join(ROOT, "tests", "cpp", "host_mirror_colfilter_test")
+
+
+def build_mirror_colfilter_test(force=False):
+    """ColumnPredicateFilter of the operator surface (csrc/host/trinity_gpu.hpp: an IndexDocumentsFilter over DeviceColumns, built on the device through
+    tri_filters_from_columns, and answered on the host through column_pred.hpp) compiled into its driver; in-tree, so that it travels to the GPU box, where
+    tests/test_host_mirror_colfilter.py runs it."""
+    deps = [MIRROR_COLFILTER_SRC, os.path.join(PKG, "csrc", "host", "trinity_gpu.hpp"), os.path.join(PKG, "csrc", "host", "column_pred.hpp"), os.path.join(PKG, "csrc", "host", "google_encoder.hpp"),
+            os.path.join(ROOT, "include", "trinity_hip.h")]  # fmt: skip
+    if force or _newer(MIRROR_COLFILTER_BIN, deps):
+        build_hip()
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-o", MIRROR_COLFILTER_BIN, MIRROR_COLFILTER_SRC, "-L" + PKG, "-ltrinity_hip", "-Wl,-rpath,$ORIGIN/../../trinity_amd"]
+        subprocess.run(cmd, check=True)
+    return MIRROR_COLFILTER_BIN
+
+
 def build_all(force=False):
     return (build_hip(force), build_host(force), build_mirror_test(force), build_mirror_write_test(force), build_mirror_filter_test(force), build_mirror_wide_terms_test(force),
             build_mirror_hits_test(force), build_mirror_rank_test(force), build_mirror_collection_test(force), build_mirror_isect_test(force), build_mirror_perc_test(force), build_mirror_facets_test(force), build_mirror_order_test(force),
-            build_mirror_stats_test(force))
+            build_mirror_stats_test(force), build_mirror_colfilter_test(force))
 
 
 def kernels_stamp():

@@ -331,3 +331,31 @@ struct DevStats { // passed to the kernel BY VALUE: a run already queued keeps t
         uint32_t n, lds_records;          // stats; records per query of all grouped stats
         uint32_t ndocs, nq;               // entries of every column of the index (docs_cnt + 1): a docID at or past it is never read; caller queries
 };
+
+// ---- column predicates as document filters (k_filter_columns.hpp; tri_filters_from_columns): a predicate — up to COLFILTER_MAX_CLAUSES RANGE / SET clauses over
+//      the index's columns, all or any of them — becomes a filter's drop bitmap.  One launch serves every predicate of a call: a workgroup takes COLFILTER_CHUNK
+//      consecutive docIDs, stages each DISTINCT column's values for them in LDS once, and evaluates every predicate against the staged values
+constexpr uint32_t COLFILTER_CHUNK = 2048;                             // docIDs a workgroup owns: 64 bitmap words per predicate; the bitmap's extent is a multiple of it
+constexpr uint32_t COLFILTER_WG = 256;                                 // threads of a workgroup: COLFILTER_CHUNK / 4 / COLFILTER_WG 16-byte loads a thread and column
+constexpr uint32_t COLFILTER_WAVES = COLFILTER_WG / 64;                // each wave owns COLFILTER_WAVE_DOCS consecutive docIDs of the chunk ...
+constexpr uint32_t COLFILTER_WAVE_DOCS = COLFILTER_CHUNK / COLFILTER_WAVES;
+constexpr uint32_t COLFILTER_WAVE_WORDS = COLFILTER_WAVE_DOCS / 32;    // ... and stores their words of a predicate in ONE instruction, a word a lane
+constexpr uint32_t COLFILTER_MAX_CLAUSES = 8;                          // == TRI_PRED_MAX_CLAUSES
+constexpr uint32_t COLFILTER_MAX_COLUMNS = 8;                          // == TRI_PRED_MAX_COLUMNS: 8 x COLFILTER_CHUNK x 4 bytes = 64 KB of LDS at the most
+constexpr uint32_t COLFILTER_MAX_PREDS = 256;                          // == TRI_PREDS_MAX
+constexpr uint32_t COLFILTER_RANGE = 0, COLFILTER_SET = 1;             // == TRI_CLAUSE_RANGE, TRI_CLAUSE_SET
+struct DevColClause { // 32 bytes, read wave-uniformly (scalar loads)
+        uint32_t col;    // which staged column (0 .. ncols - 1)
+        uint32_t kind;   // COLFILTER_RANGE / COLFILTER_SET
+        uint32_t negate; // 0 / 1
+        uint32_t lo, hi; // RANGE: lo <= v <= hi, unsigned.  SET: hi = the bits of the clause's bitset (a value at or above it is in no set; 0: the empty set)
+        uint32_t set_off; // SET: the bitset's first word in the call's bitset block
+        uint32_t pad[2];
+};
+struct DevColPred { // 32 bytes
+        uint32_t first_clause, nclauses;
+        uint32_t any; // 0: every clause holds; 1: at least one
+        uint32_t pad;
+        const uint32_t *also; // nullptr, or a drop bitmap of the same extent whose words are OR-ed in
+        uint32_t *out;        // the predicate's drop bitmap
+};

@@ -18,6 +18,7 @@
 #include "facet_rows.hpp"
 #include "order_rows.hpp"
 #include "stats_rows.hpp"
+#include "column_pred.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -832,6 +833,75 @@ namespace trinity_amd {
                 tri_column *handle() const { return h; }
                 IndexSource *source() const { return src; }
                 const std::vector<uint32_t> &values() const { return vals; }
+        };
+
+        // An IndexDocumentsFilter whose rule reads the documents' ATTRIBUTES: a predicate — 1 .. TRI_PRED_MAX_CLAUSES RANGE / SET clauses over DeviceColumns of one source,
+        // all of them or (any) at least one — evaluated on the device over the resident columns (tri_filters_from_columns: no docID list crosses PCIe).  keepOnly
+        // (the default): the documents the predicate holds for are the only ones a query may match; else they are disregarded.  `also`: a device filter of the same
+        // source whose disregarded documents this one disregards too.  filter(id) answers from the columns' host copies through column_pred.hpp — the same rule, for
+        // a caller that asks on the host and for the replay: with onDevice == false device_filter() is nullptr and exec_query asks filter() per replayed document.
+        // It belongs to its source and goes before it.  Like the tri_filter it wraps it does not reference its columns once it is built: the constructor copies the
+        // host values of the distinct columns its clauses name, so filter() and the replay stay valid after the DeviceColumns are gone.
+        class ColumnPredicateFilter final : public IndexDocumentsFilter {
+              public:
+                struct Clause {
+                        const DeviceColumn *column;
+                        uint32_t kind{TRI_CLAUSE_RANGE};
+                        bool negate{false};
+                        uint32_t lo{0}, hi{0};     // RANGE: lo <= value <= hi, unsigned
+                        std::vector<uint32_t> set; // SET: each below TRI_FACET_MAX_BUCKETS
+                        static Clause range(const DeviceColumn *c, const uint32_t lo, const uint32_t hi, const bool negate = false) { return Clause{c, TRI_CLAUSE_RANGE, negate, lo, hi, {}}; }
+                        static Clause among(const DeviceColumn *c, std::vector<uint32_t> values, const bool negate = false) { return Clause{c, TRI_CLAUSE_SET, negate, 0, 0, std::move(values)}; }
+                };
+
+              private:
+                tri_filter *h{nullptr};
+                std::vector<Clause> clauses;
+                std::vector<tri_clause> raw;
+                std::vector<std::pair<const tri_column *, std::vector<uint32_t>>> hostValues; // the distinct columns' values, copied: by handle
+                tri_predicate pred{};
+                IndexDocumentsFilter *const alsoHost;
+                const int mode;
+                const bool device;
+
+              public:
+                ColumnPredicateFilter(IndexSource *src, std::vector<Clause> cl, const bool any = false, const bool keepOnly = true, IndexDocumentsFilter *also = nullptr, const bool onDevice = true)
+                    : clauses(std::move(cl)), alsoHost{also}, mode{keepOnly ? TRI_FILTER_KEEP : TRI_FILTER_DROP}, device{onDevice} {
+                        for (const Clause &c : clauses) {
+                                if (!c.column || c.column->source() != src)
+                                        throw invalid_argument("ColumnPredicateFilter: a clause's column belongs to another source");
+                                raw.push_back(tri_clause{c.column->handle(), c.kind, c.negate ? 1u : 0u, c.lo, c.hi, c.set.empty() ? nullptr : c.set.data(), uint32_t(c.set.size()), 0});
+                                if (std::none_of(hostValues.begin(), hostValues.end(), [&](const auto &hv) { return hv.first == c.column->handle(); }))
+                                        hostValues.emplace_back(c.column->handle(), c.column->values());
+                        }
+                        for (Clause &c : clauses)
+                                c.column = nullptr; // (not kept: the columns may go before the filter)
+                        if (also && !also->device_filter())
+                                throw invalid_argument("ColumnPredicateFilter: the `also` filter has no device bitmap");
+                        pred = tri_predicate{raw.data(), uint32_t(raw.size()), any ? 1u : 0u, also ? also->device_filter() : nullptr, 0};
+                        check(tri_filters_from_columns(src->handle(), &pred, 1, mode, &h));
+                }
+                ~ColumnPredicateFilter() override { tri_filter_destroy(h); }
+                ColumnPredicateFilter(const ColumnPredicateFilter &) = delete;
+                bool filter(const docid_t id) override {
+                        const bool also = alsoHost && alsoHost->filter(id);
+                        return colpred::drops(pred, id, mode, also, [this](const tri_column *c) {
+                                for (const auto &hv : hostValues)
+                                        if (hv.first == c)
+                                                return hv.second.data();
+                                return static_cast<const uint32_t *>(nullptr); // (unreachable: the predicate names the copied columns alone)
+                        });
+                }
+                tri_filter *device_filter() override { return device ? h : nullptr; }
+                // the bitmap the device applies (tri_filter_bitmap): bit id & 31 of word id >> 5 set = document id is disregarded
+                std::vector<uint32_t> bitmap() const {
+                        size_t n = 0;
+                        uint32_t none = 0;
+                        tri_filter_bitmap(h, &none, 0, &n); // (refused for its capacity: leaves the extent)
+                        std::vector<uint32_t> words(n);
+                        check(tri_filter_bitmap(h, words.data(), words.size(), &n));
+                        return words;
+                }
         };
 
         // The application's consider(id) / consider(ids, cnt) when it counts the matches by attributes — row k has facets[k].nbuckets + 1 counters, and for every

@@ -513,6 +513,7 @@ struct tri_batch : BatchPlan {
 #include "k_stats.hpp"
 #include "k_commit.hpp"
 #include "k_lencode.hpp"
+#include "k_filter_columns.hpp" // (beside k_filter.hpp's own kernels: column predicates -> drop bitmaps)
 #include "filtered_kernels.hpp"
 
 // launch the instantiation of a codec-templated kernel that matches the uploaded segment: `pick` maps the codec (a std::integral_constant: the
@@ -2396,6 +2397,9 @@ extern "C" int tri_batch_set_filters(tri_batch *b, tri_filter *const *filters, s
         b->filter_rows = std::move(rows);
         return TRI_OK;
 }
+
+// column predicates as document filters (tri_filters_from_columns), and any filter's bitmap read back (tri_filter_bitmap)
+#include "colfilter_side.hpp"
 
 // ------------------------------------------------------------------------------------------ collections of segments
 // IndexSourcesCollection (index_source.cpp:3-30): a query runs over every source of the collection, each source masked by what the

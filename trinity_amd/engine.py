@@ -55,6 +55,15 @@ class TriStat(C.Structure):
     _fields_ = [("group", C.c_void_p), ("value", C.c_void_p), ("nbuckets", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TriClause(C.Structure):
+    _fields_ = [("column", C.c_void_p), ("kind", C.c_uint32), ("negate", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32), ("set", C.c_void_p), ("nset", C.c_uint32),
+                ("reserved", C.c_uint32)]  # fmt: skip
+
+
+class TriPredicate(C.Structure):
+    _fields_ = [("clauses", C.POINTER(TriClause)), ("nclauses", C.c_uint32), ("any", C.c_uint32), ("also", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 class TriIsectRequest(C.Structure):
     _fields_ = [("ngroups", C.c_uint32), ("reserved", C.c_uint32), ("stopwords_mask", C.c_uint64)]
 
@@ -166,6 +175,7 @@ ABI_SYMBOLS = [
     "tri_column_create", "tri_column_destroy", "tri_batch_set_facets", "tri_batch_facets", "tri_cbatch_facets",
     "tri_batch_set_order", "tri_batch_ordered", "tri_cbatch_ordered",
     "tri_batch_set_stats", "tri_batch_stats", "tri_cbatch_stats",
+    "tri_filters_from_columns", "tri_filter_bitmap",
 ]  # fmt: skip
 
 _hip = None
@@ -253,6 +263,8 @@ def hip_lib():
     L.tri_filter_destroy.argtypes = [vp]
     L.tri_filter_destroy.restype = None
     L.tri_batch_set_filters.argtypes = [vp, vp, C.c_size_t, vp]
+    L.tri_filters_from_columns.argtypes = [vp, C.POINTER(TriPredicate), C.c_size_t, C.c_int, C.POINTER(vp)]
+    L.tri_filter_bitmap.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.tri_batch_set_ranker.argtypes = [vp, vp, vp]
     L.tri_column_create.argtypes = [vp, vp, C.c_size_t, C.POINTER(vp)]
     L.tri_column_destroy.argtypes = [vp]
@@ -819,10 +831,74 @@ class Filter:
         _check(hip_lib().tri_filter_from_docset(batch.h, q, FILTER_KEEP if keep else FILTER_DROP, C.byref(f.h)))
         return f
 
+    @classmethod
+    def from_columns(cls, index, predicates, keep=True):
+        """One filter per Predicate, evaluated on the device over the index's resident columns in one launch (tri_filters_from_columns): by default the documents a
+        predicate holds for are the only ones a query may match; keep=False drops them.  All of them, or TrinityError and none."""
+        preds = list(predicates)
+        raw = (TriPredicate * max(1, len(preds)))()
+        alive = []  # the clause arrays and set arrays the structs point into
+        for r, p in zip(raw, preds):
+            cl = (TriClause * max(1, len(p.clauses)))()
+            for c, x in zip(cl, p.clauses):
+                c.column, c.kind, c.negate, c.lo, c.hi = x.column.h, x.kind, int(bool(x.negate)), x.lo, x.hi
+                if x.values is not None:
+                    v = np.ascontiguousarray(x.values, dtype=np.uint32)
+                    alive.append(v)
+                    c.set, c.nset = (v.ctypes.data if v.size else None), v.size
+            alive.append(cl)
+            r.clauses, r.nclauses, r.any, r.also = cl, len(p.clauses), int(bool(p.any)), (p.also.h if p.also is not None else None)
+        out = (C.c_void_p * max(1, len(preds)))()
+        _check(hip_lib().tri_filters_from_columns(index.h, raw, len(preds), FILTER_KEEP if keep else FILTER_DROP, out))
+        made = []
+        for h in out[: len(preds)]:
+            f = cls.__new__(cls)
+            f.index, f.h = index, C.c_void_p(h)
+            made.append(f)
+        return made
+
+    def bitmap(self):
+        """The filter's drop bitmap as the kernels read it (tri_filter_bitmap): u32 words, bit d & 31 of word d >> 5 set = document d is dropped.  Bit 0 and the bits
+        past the index's largest document are unspecified."""
+        n = C.c_size_t()
+        probe = np.zeros(1, dtype=np.uint32)
+        hip_lib().tri_filter_bitmap(self.h, probe.ctypes.data, 0, C.byref(n))  # (refused for its capacity: leaves the extent)
+        words = np.zeros(max(1, n.value), dtype=np.uint32)
+        _check(hip_lib().tri_filter_bitmap(self.h, words.ctypes.data, words.size, C.byref(n)))
+        return words[: n.value]
+
     def close(self):
         if self.h:
             hip_lib().tri_filter_destroy(self.h)
             self.h = C.c_void_p()
+
+
+CLAUSE_RANGE, CLAUSE_SET = 0, 1  # TRI_CLAUSE_RANGE, TRI_CLAUSE_SET
+PRED_MAX_CLAUSES, PRED_MAX_COLUMNS, PREDS_MAX = 8, 8, 256  # TRI_PRED_MAX_CLAUSES, TRI_PRED_MAX_COLUMNS, TRI_PREDS_MAX
+
+
+class Clause:
+    """One test of a column predicate (tri_clause).  Clause.range(column, lo, hi): lo <= values[d] <= hi, unsigned, both ends inclusive; Clause.among(column, values):
+    values[d] is one of `values` (each below FACET_MAX_BUCKETS).  negate=True: the clause holds where the test fails."""
+
+    def __init__(self, column, kind, lo=0, hi=0, values=None, negate=False):
+        self.column, self.kind, self.lo, self.hi, self.values, self.negate = column, kind, lo, hi, values, negate
+
+    @classmethod
+    def range(cls, column, lo, hi, negate=False):
+        return cls(column, CLAUSE_RANGE, lo=lo, hi=hi, negate=negate)
+
+    @classmethod
+    def among(cls, column, values, negate=False):
+        return cls(column, CLAUSE_SET, values=np.asarray(values, dtype=np.uint32), negate=negate)
+
+
+class Predicate:
+    """1 .. PRED_MAX_CLAUSES clauses (tri_predicate): it holds for a document when every clause does, or with any=True when at least one does.  also: a Filter of the
+    same index whose dropped documents the resulting filter drops too."""
+
+    def __init__(self, clauses, any=False, also=None):
+        self.clauses, self.any, self.also = list(clauses), any, also
 
 
 FACETS_MAX = 4  # TRI_FACETS_MAX
