@@ -61,6 +61,19 @@ extern "C" {
 #define TRI_ERR_NOMEM (-5)
 #define TRI_ERR_INTERNAL (-6)    /* the engine contradicts itself (a result block that does not add up): a bug, never a caller's error */
 
+/* docIDs.  A segment may hold any ascending docIDs 1 .. 2^32 - 2 (tri_index_upload refuses only block deltas that run past 2^32); the bitmaps over the docID
+ * space (term planes, masked documents, filters, result bitmaps) extend (max docID / 131072 + 2) * 4096 words, 512 MiB each at the top.  What the engine enforces
+ * or decides by the segment's largest docID:
+ *   - tri_isect_run: TRI_ERR_UNSUPPORTED for the whole call when the index's docIDs reach 2^31;
+ *   - AccumulatedScore top-K in one pass: the bit-plane kernel takes queries only on segments whose largest docID is below 0x7fff0000, the window-word kernel
+ *     only below 0xffffc000 (its last window would end past 2^32); from there on scored queries run match-then-score (tri_batch_info::cand_queries / dense_queries /
+ *     pset_queries instead of ::planes_queries / ::fused_queries);
+ *   - a query that only the window-word kernel takes (a matchsome or another general tree over at most eight distinct terms, in every mode) is LEFT OUT on a segment
+ *     whose largest docID is 0xffffc000 or more: tri_batch_query_status TRI_ERR_UNSUPPORTED, tri_last_error names the limit;
+ *   - DocumentsOnly unions of head terms and rare ones are scattered into a result bitmap only while the union's last document lies below 2^31 (4096 tasks of
+ *     four 131072-document windows); from there on they run as bitmap windows and their result is ascending docIDs (tri_batch_docset_bitmap: form 0).
+ * Only the third of these leaves a query out. */
+
 /* codecs (segment `id` file codec name: indexer.cpp:266-270, segment_index_source.cpp:172-179) */
 #define TRI_CODEC_GOOGLE 1
 #define TRI_CODEC_LUCENE 2

@@ -128,6 +128,8 @@ constexpr uint32_t PSET_UNIT_ROUND_SHIFT = 4, PSET_UNIT_ROUND_MASK = 15u; // Dev
 constexpr uint32_t PSET_ROUND_DOCS = 16384, PSET_STAGE_DOCS = 1024; // documents of a window a wave of k_psets owns (eight waves), docIDs its staging buffer holds
 constexpr uint32_t PSET_UNIT_SCATTER = 4u; // a UNION some of whose terms have no plane (qplane[] = PL_NONE for them), result a bitmap: the plane terms' words are OR-ed and stored,
                                            // then the other terms' documents of the task's range are set in the stored words one by one (k_psets.hpp: psets_scatter)
+constexpr uint32_t PSCAT_MAX_TASKS = 4096; // ... of a query of at most this many tasks (k_psets_prep counts a query's documents per task in LDS): 2^31 documents in tasks of
+                                           // PSET_TASK_WINDOWS windows.  route_cnf plans a union whose range needs more — a last document at or past 2^31 — as bitmap windows
 // ---- TASK_TREE: the query tree as the kernels read it (k_tree.hpp).  A record in the plan's tree[] words (DevQuery::fused_idx = its first word):
 //      TREE_HDR_WORDS header words { nnodes, 0... }, then nnodes DevTreeNode in POSTFIX order (children before parents, the root last)
 constexpr uint32_t TREE_MAX_NODES = 64;     // node values and "an iterator sits on the document" flags are bit sets in a 64-bit word

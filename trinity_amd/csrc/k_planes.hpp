@@ -74,6 +74,21 @@ __device__ __forceinline__ void write_rank_records(uint32_t *__restrict__ rec, c
         }
 }
 
+// The blocks of term t that reach plane windows [w, w + n) of a row, whose docIDs [w PL_W, (w + n) PL_W) are NOT formed in 32 bits: a row's extent — (max docID >> 17) + 2 bitmap windows, the
+// last one spare — ends at or past 2^32 for every max docID from 2^32 - 2^18 on, so the ends of its last windows, and the spare window's start, do not fit 32
+// bits (no planner rule keeps a segment with such docIDs from getting planes).  A range that starts at or past 2^32 holds no document (lo = hi = nblocks:
+// nothing is decoded, its words stay zero); one that ends there is reached by every block from lo on.
+constexpr uint32_t PL_SPACE_WINDOWS = (uint32_t)((1ull << 32) / PL_W); // plane windows of the whole docID space
+__device__ __forceinline__ BlockRange plane_block_range(const uint32_t *bl, const uint32_t *win, const DevTerm &t, const uint32_t w, const uint32_t n) {
+        if (w >= PL_SPACE_WINDOWS)
+                return {t.nblocks, t.nblocks};
+        const bool open = w + n >= PL_SPACE_WINDOWS; // (w + n <= a row's windows: far from wrapping itself)
+        BlockRange r = term_block_range(bl, win, t, w * PL_W, (open ? w : w + n) * PL_W);
+        if (open)
+                r.hi = t.nblocks;
+        return r;
+}
+
 // One workgroup per (plane row, window): the rows (<= 32 documents each) of the term that reach the window are decoded, one lane
 // per row, into LDS planes, which are then written out whole — every word of every plane is written by exactly one workgroup,
 // so the scratch region needs no clearing between launches.
@@ -99,7 +114,7 @@ __global__ __launch_bounds__(AND_WG) void k_term_planes(const uint8_t *__restric
         // rows that can hold documents of [w0, w0 + PL_W): first row whose last docID >= w0 ... first row whose last docID >= the next
         // window's first docID (it may still begin inside this one)
         // (a short list bisects its directory: planes are made for long ones, but the planner may be told to give every term one)
-        const BlockRange r = term_block_range(bl, win, t, w0, w0 + PL_W);
+        const BlockRange r = plane_block_range(bl, win, t, w, 1u);
         const uint32_t b_lo = uni(r.lo), b_hi = uni(min(r.hi, t.nblocks - 1));
         __syncthreads();
         if (b_lo < t.nblocks)
@@ -180,9 +195,10 @@ __global__ __launch_bounds__(AND_WG) void k_term_plane0(const uint8_t *__restric
                         rdir[i] = 0xffffffffu;
         const DevTerm t = terms[build[2 * blockIdx.y]];
         const uint32_t *bl = blk_last + t.first_block;
-        const uint32_t w0 = wfirst * PL_W, w1 = w0 + wn * PL_W; // (the planner keeps max docID below 2^31: no wrap)
-        // rows that can hold documents of [w0, w1): first row whose last docID >= w0 ... first row whose last docID >= w1 (it may still begin inside)
-        const BlockRange r = term_block_range(bl, win, t, w0, w1);
+        const uint32_t w0 = wfirst * PL_W; // (the decode's base; a group past 2^32 — the spare window of a row whose extent passes it — decodes nothing)
+        // rows that can hold documents of [w0, w1): first row whose last docID >= w0 ... first row whose last docID >= w1 (it may still begin inside);
+        // w1 = w0 + wn * PL_W reaches 2^32 in the last groups of a segment whose docIDs reach 2^32 - 2^18: plane_block_range counts in windows
+        const BlockRange r = plane_block_range(bl, win, t, wfirst, wn);
         const uint32_t b_lo = uni(r.lo), b_hi = uni(min(r.hi, t.nblocks - 1));
         __syncthreads();
         if (b_lo < t.nblocks)
@@ -1052,7 +1068,7 @@ __global__ __launch_bounds__(PLK_WG, (PLK_WGS_PER_CU * PLK_WG + 255) / 256) void
                 const uint32_t nslots = min(uni(fq.nslots), (uint32_t)NS), nreq = uni(fq.nreq), negs = uni(fq.negslots);
                 const uint32_t kk = min(lane, nslots - 1); // lane s (< nslots) of every wave looks after slot s, the lanes above mirror the last slot
                 const uint32_t wfirst = task.tile_begin, wend = task.tile_end;
-                const uint32_t d_lo = wfirst * PL_W, d_hi = wend * PL_W; // (the planner keeps max docID below 2^31: no wrap)
+                const uint32_t d_lo = wfirst * PL_W, d_hi = wend * PL_W; // (tasks_onepass plans k_planes only for a max docID below 0x7fff0000: no wrap here; no other kernel has such a rule)
                 {
                         const DevTerm myt = terms[fq.term[kk]];
                         sh.term[kk] = myt;

@@ -395,8 +395,10 @@ __global__ __launch_bounds__(PSET_WG, TRI_PSET_WAVES) void k_psets(const DevPset
 //      millions of docIDs, so each of the query's twenty tasks went term record -> block directory -> block bytes (five dependent round trips, one lane in 512 working),
 //      decoded the straddling row and kept next to nothing of it — 0.39 of k_psets' 0.96 ms for cfg5's five-way unions, for 0.06 % of their matches.
 constexpr int PSCAT_WG = 256;
-constexpr uint32_t PSCAT_MAX_TASKS = 4096; // tasks of a query: 2^31 documents / (PSET_TASK_WINDOWS windows of 2^17)
-static_assert((1ull << 31) / ((uint64_t)PSET_TASK_WINDOWS * SPAN_BITS) <= PSCAT_MAX_TASKS, "a query's tasks fit the workgroup's LDS counters");
+// (PSCAT_MAX_TASKS, dev_structs.hpp: the tasks of a scatter query.  Nothing in this file checks a docID against it: cnt[d / task_docs] below and the 32-bit
+//  nbits = out_cap * 32 hold because route_cnf — planner_tasks.hpp — makes no PSET_UNIT_SCATTER unit for a query of more tasks, that is for a union whose
+//  last document lies at or past 2^31; such a union runs as bitmap windows in k_and_dense.  docIDs up to 2^32 - 2 are legal in a segment.)
+// (no static_assert on the product: with -DTRI_PSET_TASK_WINDOWS=8 the task count alone would admit 2^32 bits, so route_cnf also asks for nwin * SPAN_BITS < 2^32)
 struct PscatShared {
         DevTerm term[MAX_QTERMS];   // the union's terms without a plane ...
         uint32_t nrows[MAX_QTERMS]; // ... and their rows (0: the term has a plane)

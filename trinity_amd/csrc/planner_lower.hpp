@@ -605,6 +605,13 @@ namespace trip {
         //      anyway), or when every other list is within a factor 32 of the lead (no block could be skipped) and there is
         //      enough work per docID window to keep 256 lanes busy; one pass (TASK_FUSED / TASK_PLANES) when such a query
         //      asks for a top-K, or is a general tree
+        // k_fused forms a window's end — w0 + W, wlast, a row's hint — in 32 bits (k_fused.hpp find_window), and W (14 or 28 cells) does not divide 2^32: on a segment
+        // whose last window of either width would end past 2^32 — a largest docID of FUSED_MAX_DOC or more — no query is given to it.  A scored CNF query then runs
+        // match-then-score; a truth-table query, which no other kernel takes, is left out by name (lower_query)
+        constexpr uint32_t FUSED_MAX_DOC = (uint32_t)((1ull << 32) / (2ull * FUS_W) * (2ull * FUS_W)); // (0xffffc000 at the default FUS_CELLS = 14)
+        static_assert(FUSED_MAX_DOC <= (1ull << 32) / FUS_W * FUS_W, "the wider window's bound is the lower one");
+        inline bool fused_windows_fit(const HostIndex &ix) { return ix.max_doc < FUSED_MAX_DOC; }
+
         inline void classify(const Ctx &C, Frag &f, Tmp &t, const uint64_t lead_docs) {
                 const HostIndex &ix = C.ix;
                 const tri_options &opt = C.env.opt;
@@ -660,6 +667,11 @@ namespace trip {
                         // anything else — a multi-word phrase below the root conjunction, more terms or leaves — over leaf bitmaps (k_tree.hpp)
                         if (!build_truth(S, root, tp))
                                 return hidden ? herr(f.err, TRI_ERR_INVALID, "query %zu: a phrase leaf that is not a phrase", qi) : lower_tree(C, f, qi, prog, plen, wq, root);
+                        if (!fused_windows_fit(ix)) { // (nothing of the query is recorded yet: left out cleanly)
+                                f.left_out.push_back(qi);
+                                herr(f.err, TRI_ERR_UNSUPPORTED, "query %zu: a truth-table query on a segment whose docIDs reach 0x%x (the window-word kernel's last window would end past 2^32)", qi, FUSED_MAX_DOC);
+                                return TRI_OK;
+                        }
                         truth = true;
                         S.gt = tp.slots; // (one group of every slot: the bookkeeping below — term list, cost, output bound — sees a union)
                         S.gs.assign({0u, (uint32_t)S.gt.size()});
@@ -697,7 +709,7 @@ namespace trip {
                 t.truth = truth;
                 if (truth)
                         slot_map_from_truth(C, f, t, tp, rich);
-                else if (C.scored && C.in.topk && S.qphrases.empty() && C.env.opt.fused)
+                else if (C.scored && C.in.topk && S.qphrases.empty() && C.env.opt.fused && fused_windows_fit(ix))
                         slot_map_from_cnf(C, f, t);
                 t.q.fused_idx = 0;
                 t.q.form = RESULT_DOCIDS;

@@ -133,7 +133,10 @@ namespace trip {
                         //  holds for the head terms alone holds for all of them, so a scatter union's result IS a bitmap)
                         const double N = std::max<double>(1.0, (double)ix.info.docs_cnt);
                         // (option scatter_bitmap_slack: such a union is run this way — and its result kept as a bitmap — from 1 / (32 x slack) of the documents on)
-                        r.pscatter = one_group && plane_df && std::min<double>(N, (double)plane_df) * (double)std::max<uint64_t>(1, opt.scatter_bitmap_slack) >= (double)nwin * SPAN_WORDS;
+                        // (k_psets_prep counts such a query's documents per task in PSCAT_MAX_TASKS LDS counters: a union whose range needs more tasks — its last
+                        //  document at or past 2^31 — is not run this way; it stays a bitmap-window query of k_and_dense)
+                        const bool fits = (nwin + PSET_TASK_WINDOWS - 1) / PSET_TASK_WINDOWS <= PSCAT_MAX_TASKS && (uint64_t)nwin * SPAN_BITS < (1ull << 32); // (... and its nbits = out_cap * 32 is a 32-bit product)
+                        r.pscatter = fits && one_group && plane_df && std::min<double>(N, (double)plane_df) * (double)std::max<uint64_t>(1, opt.scatter_bitmap_slack) >= (double)nwin * SPAN_WORDS;
                         r.pset = r.pscatter;
                 }
                 // a single lead list too short for a plane against lists that all have one: candidate tiles, every candidate tested with one
